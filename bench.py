@@ -160,6 +160,9 @@ def parse():
                     help="(-1 = on where one oracle step takes about a second: the workloads whose camera sums fit in LDS) compare the step of the LAST timed solve with ONE oracle step on the same FULL-SIZE inputs (16 threads; N > 1: the ranks' "
                          "shards of the step are gathered and assembled first) and report it as oracle_check.  Independent of --no-cpu-baseline: "
                          "the synthetic10M child and the one-GPU N = 8 validation run use it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the LAST timed step returned to its caller as DIR/<name>.npy (float64, at most "
+                         "64 MB in all; a larger vector is replaced by a fixed seeded sample of its entries; N > 1: one set of files per rank)")
     return ap.parse_args()
 
 
@@ -195,6 +198,21 @@ def make_solver(hs, bs, nelim, solver, device, comm=None, storage=0):
 
 
 RADIUS = 1e4  # Solver::Options::initial_trust_region_radius; D = sqrt(clamp(diag(J'J)) / RADIUS)
+DUMP_BYTES = 64_000_000   # --dump-outputs: every file of one run together
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: each array as out_dir/<name>.npy in float64, the smallest first.  An array larger than what is left of the budget
+    is replaced by a fixed sample of its entries: sorted indices drawn with seed 0, the same on every run of the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64).ravel() for k, v in arrays.items()}
+    left = budget - 1024 * len(arrays)   # (the .npy headers)
+    for name, a in sorted(arrays.items(), key=lambda kv: kv[1].size):
+        cap = max(left // a.itemsize, 0)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def step_min_bytes(solver_kind, n_obs, n_points, n_cameras, cg_iterations, s=8):
@@ -249,6 +267,7 @@ def timed_steps(solver, ptrs, steps, warmup, sync, step_kind="linear_solve", eta
         ls = r.linear_solver   # (the last step's summary; `r` is the stepper's result struct, which the next call would overwrite)
         last = sys.modules[type(solver).__module__].Summary(ls.residual_norm, ls.num_iterations, ls.termination_type,
                                                             ls.message.decode(errors="replace"))
+        last.model_cost_change = res[-1][2]   # (the step's other output to its caller)
         return el, [int(x[0]) for x in res], last
     t0 = time.perf_counter()
     for _ in range(steps):
@@ -495,6 +514,12 @@ def main():
     # ---- timed region: K LM linear solves, inputs resident in HBM -------------------
     elapsed, iters, last = timed_steps(solver, (tv, tb, tD, tx), args.steps, args.warmup, sync, args.step, args.eta)
     collectives_last_step = int(solver.info().collectives_last_step)   # (of the last timed step: read before any other leg runs a solve)
+    if args.dump_outputs:   # what the last timed step handed its caller (tx: before the phase-timing step below writes it again)
+        outs = {"step" if args.step == "lm_step" else "x": tx.cpu().numpy(), "residual_norm": [last.residual_norm],
+                "num_iterations": [last.num_iterations], "termination_type": [last.termination_type]}
+        if args.step == "lm_step":
+            outs["model_cost_change"] = [last.model_cost_change]
+        dump_outputs(args.dump_outputs, {(f"{k}_rank{rank}" if world > 1 else k): v for k, v in outs.items()}, DUMP_BYTES // world)
     if dist is not None:
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)

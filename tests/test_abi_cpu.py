@@ -53,8 +53,9 @@ def test_option_validation_before_device():
     with pytest.raises(hs.HipError) as e:
         hs.HipLinearSolver(hs.LinearSolverOptions(type=hs.CGNR, preconditioner_type=hs.SCHUR_JACOBI, max_num_iterations=5))
     assert "preconditioner_type" in str(e.value)
-    with pytest.raises(hs.HipError):
-        hs.HipLinearSolver(hs.LinearSolverOptions(type=3, max_num_iterations=5))  # DENSE_SCHUR: not this path
+    with pytest.raises(hs.HipError) as e:
+        hs.HipLinearSolver(hs.LinearSolverOptions(type=4, max_num_iterations=5))  # SPARSE_SCHUR: not this path (DENSE_SCHUR = 3 is)
+    assert "solver_type" in str(e.value)
 
 
 def test_product_does_not_import_the_oracle():

@@ -177,3 +177,31 @@ def test_round6_default_line_carries_what_the_review_asked_for():
     for c in cases:
         assert c["step_rel_diff_vs_oracle"] < 1e-9 and c["cpu_port"]["steps_per_s"] > 0 and c["steps_per_s"] == pytest.approx(1e3 / c["ms_per_step"], rel=1e-2)
     assert d["extra"]["synthetic10M"]["shard_ceiling"]["cases"][0]["ranks"] == 8
+
+
+def test_dump_outputs_stays_within_its_budget_and_repeats(tmp_path):
+    """bench.py --dump-outputs: float64 .npy files, at most 64 MB together; a vector larger than that becomes the same seeded sample of
+    its entries on every run (bench.dump_outputs in a child process: importing bench.py sets OpenMP variables for its CPU leg)."""
+    import subprocess
+    import sys
+    import numpy as np
+    code = f'''
+import sys; sys.path.insert(0, {ROOT!r})
+import numpy as np
+import bench
+for d in ("a", "b"):
+    bench.dump_outputs({str(tmp_path)!r} + "/" + d, {{"step": np.arange(10_000_000, dtype=np.float64), "model_cost_change": [2.5],
+                                                     "num_iterations": [7]}})
+'''
+    p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-1000:]
+    for d in ("a", "b"):
+        files = sorted(os.listdir(tmp_path / d))
+        assert files == ["model_cost_change.npy", "num_iterations.npy", "step.npy"]
+        assert sum(os.path.getsize(tmp_path / d / f) for f in files) <= 64_000_000
+    step = np.load(tmp_path / "a" / "step.npy")
+    assert step.dtype == np.float64 and 7_000_000 < step.size < 8_000_000
+    assert (np.diff(step) > 0).all() and step[0] >= 0 and step[-1] < 10_000_000 and (step == np.round(step)).all()   # sorted entries
+    assert np.array_equal(step, np.load(tmp_path / "b" / "step.npy"))
+    assert np.load(tmp_path / "a" / "model_cost_change.npy").tolist() == [2.5]
+    assert np.load(tmp_path / "a" / "num_iterations.npy").tolist() == [7.0]

@@ -1,4 +1,4 @@
-"""SURVEY.md §8(e) with PRODUCT code on real ranks: 2, 3, 4 and 8 processes, one rank each, sharded by point
+"""SURVEY.md §8(e) with PRODUCT code on real ranks: 2 to 5 processes, one rank each, sharded by point
 (ceres-solver_amd/partition.py), camera-space sums combined by the library's one-shot peer-to-peer all-reduce over
 hipIpc-mapped buffers.  The GPU box has one MI355X, so all ranks run on device 0 — the same code path (hipIpc
 mapping, system-scope flags, rank-ordered sums) that runs over xGMI between the GPUs of a node.  Rung (5) of the
@@ -13,10 +13,15 @@ from test_gpu_operators import rel
 
 pytestmark = pytest.mark.gpu
 
-WORLDS = (2, 3, 4, 8)   # the peer-to-peer all-reduce indexes [parity][source rank][cap] slots for world <= 8 (kernels_cg.hip)
+# The ranks share device 0 with this process, and at most six processes may hold a GPU at once: five ranks at most.  (The all-reduce's
+# slots for world <= 8 — [parity][source rank][cap], kernels_cg.hip — are reached in one process by the loop-back and ghost-peer
+# communicators of tests/test_gpu_lm_step.py.)
+MAX_RANKS = 5
+WORLDS = (2, 3, 4, MAX_RANKS)
 
 
 def run_ranks(scenario, WORLD=2, timeout=420):
+    assert WORLD <= MAX_RANKS, WORLD
     from multirank_worker import run_rank
     ctx = mp.get_context("spawn")
     pipes = [ctx.Pipe() for _ in range(WORLD)]
@@ -380,12 +385,13 @@ def test_sharded_solver_options_equal_the_single_rank_instance(hip, problems, WO
 
 @pytest.mark.parametrize("seed,WORLD,pk", [
     (52, 3, dict(num_e_blocks=40, num_f_blocks=2, max_rows_per_e=1, num_no_e_rows=3, static_sizes=(2, 3, 6), seed=52)),
-    (83, 8, dict(num_e_blocks=8, num_f_blocks=2, max_rows_per_e=1, num_no_e_rows=0, static_sizes=None, seed=83))])
+    (32, 4, dict(num_e_blocks=4, num_f_blocks=2, max_rows_per_e=1, num_no_e_rows=0, static_sizes=None, seed=32))])
 def test_ranks_agree_on_the_kernel_path(hip, oracle, problems, seed, WORLD, pk):
     """A shard of a GENERAL structure can look like bundle adjustment — each of its rows one point cell and one camera cell — while its
     neighbour's does not; the two kernel paths issue different sequences of exchanges, and ranks that chose for themselves waited for
     each other until the time-out (tools/fuzz_multirank.py --generic, seeds 52 and 83 among nine of 149).  ceres_hip_set_structure now
-    agrees on the path (and on the fused shape) over the ranks."""
+    agrees on the path (and on the fused shape) over the ranks.  (Seed 83 needs eight ranks; seed 32 on four ranks is the same kind of
+    case: one point per rank, and only rank 0's shard is eligible for the fused path — hip_solver.debug_plan.)"""
     solvers = [(hip.ITERATIVE_SCHUR, hip.SCHUR_JACOBI), (hip.CGNR, hip.JACOBI)]
     kw = dict(kind="general_fuzz", problem=pk, solvers=solvers, radius=1.0, max_it=3000, p2p_timeout=8)
     res = run_ranks([("g", kw)], WORLD, timeout=120)

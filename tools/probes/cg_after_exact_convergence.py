@@ -1,5 +1,6 @@
 import sys, os
-sys.path.insert(0,'/root/repo'); sys.path.insert(0,'/root/repo/tests')
+ROOT=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0,ROOT); sys.path.insert(0,os.path.join(ROOT,'tests'))
 import numpy as np, torch
 import __graft_entry__ as e
 pkg=e.load_package(); oracle=e.load_oracle(); hip=pkg.hip_solver; hip.load_library()

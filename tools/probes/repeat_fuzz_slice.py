@@ -1,6 +1,6 @@
 import sys, json, os
 sys.argv = [sys.argv[0]]
-ROOT='/root/repo'
+ROOT=os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, ROOT+'/tools'); sys.path.insert(0, ROOT+'/tests')
 import fuzz_parity as fz
 n_bad = 0
