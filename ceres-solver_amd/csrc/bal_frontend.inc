@@ -28,6 +28,7 @@ struct ceres_hip_bal {
          *d_scale = nullptr, *d_grad = nullptr, *d_parts = nullptr;
   double* h_parts = nullptr;  // pinned, kBalParts doubles
   int deferred_cost_parts = 0;  // an evaluation whose cost partials (d_parts[0 ..)) the next synchronising call collects
+  LossParams loss;              // ceres_hip_bal_set_loss: applies to every observation (kLossNone: the squared loss)
 };
 
 namespace {
@@ -53,7 +54,7 @@ int bal_evaluate_device(ceres_hip_bal* p, const double* d_state, bool jacobian, 
   BalEvalArgs A;
   A.n_rows = p->no; A.row_cam = p->d_row_cam; A.row_pt = p->d_row_pt; A.row_obs = p->d_row_obs;
   A.state = d_state; A.cam_base = 3 * int64_t(p->np); A.scale = d_scale;
-  A.residuals = d_residuals; A.values = jacobian ? p->d_vals : nullptr; A.partials = p->d_parts;
+  A.residuals = d_residuals; A.values = jacobian ? p->d_vals : nullptr; A.partials = p->d_parts; A.loss = p->loss;
   int nparts = 0;
   HIP_TRY(s, LaunchBalEvaluate(A, jacobian, &nparts, s->stream));
   if (defer) { p->deferred_cost_parts = nparts; return 0; }
@@ -95,6 +96,7 @@ void bal_set_camera_eval(ceres_hip_bal* p, bool on) {
   CamItems& I = p->s->cam_items;
   I.ev_cam_pack = on ? p->d_cam_pack : nullptr; I.ev_pt_pack = on ? p->d_pt_pack : nullptr;
   I.ev_pt = on ? p->d_cm_pt : nullptr; I.ev_obs = on ? p->d_cm_obs : nullptr;
+  I.ev_loss = p->loss;
 }
 
 // Cost, residuals and the (scaled) Jacobian at a device state vector, the Jacobian written STRAIGHT INTO THE TILES (kernels_evaluator.hip):
@@ -107,7 +109,7 @@ int bal_evaluate_into_tiles(ceres_hip_bal* p, const double* d_state, const doubl
   T.e.n_rows = p->no; T.e.row_cam = p->d_row_cam; T.e.row_pt = p->d_row_pt; T.e.row_obs = p->d_row_obs;
   T.e.state = d_state; T.e.cam_base = 3 * int64_t(p->np); T.e.scale = d_scale;
   const bool cam_eval = debug_flags == 0 && bal_camera_pass_evaluates(p);
-  T.e.residuals = p->d_res; T.e.values = cam_eval ? nullptr : p->d_vals; T.e.partials = p->d_parts;
+  T.e.residuals = p->d_res; T.e.values = cam_eval ? nullptr : p->d_vals; T.e.partials = p->d_parts; T.e.loss = p->loss;
   T.n_tiles = s->plan.n_tiles; T.slot_bpos = s->d_slot_bpos; T.slot_fpos = s->d_slot_fpos;
   T.J_out = s->d_J; T.tile_pitch = s->ops->tile_pitch; T.b_out = s->d_bt;
   T.slot_cam = p->d_slot_cam; T.slot_pt = p->d_slot_pt; T.slot_obs = p->d_slot_obs; T.pt_pack = p->d_pt_pack; T.cam_pack = p->d_cam_pack;
@@ -299,6 +301,41 @@ int ceres_hip_bal_get_row_order(const ceres_hip_bal* p, int32_t* row_observation
   return 0;
 }
 
+int ceres_hip_bal_set_loss(ceres_hip_bal* p, int32_t loss_type, double a, double b, double scale) {
+  auto invalid = [&](const std::string& why) {
+    (p ? p->err : g_create_error) = "ceres_hip_bal_set_loss: " + why;
+    return CERES_HIP_E_INVALID;
+  };
+  if (!p) return invalid("NULL problem handle");
+  static_assert(kLossTrivial == CERES_HIP_LOSS_TRIVIAL && kLossHuber == CERES_HIP_LOSS_HUBER && kLossSoftLOne == CERES_HIP_LOSS_SOFTLONE &&
+                kLossCauchy == CERES_HIP_LOSS_CAUCHY && kLossArctan == CERES_HIP_LOSS_ARCTAN && kLossTolerant == CERES_HIP_LOSS_TOLERANT &&
+                kLossTukey == CERES_HIP_LOSS_TUKEY, "device loss numbers are the ABI's");
+  if (loss_type < CERES_HIP_LOSS_TRIVIAL || loss_type > CERES_HIP_LOSS_TUKEY) return invalid("unknown loss_type " + std::to_string(loss_type));
+  if (!std::isfinite(scale) || scale <= 0.0) return invalid("scale must be finite and > 0");
+  const bool one_param = loss_type != CERES_HIP_LOSS_TRIVIAL && loss_type != CERES_HIP_LOSS_TOLERANT;
+  if (one_param && (!std::isfinite(a) || a <= 0.0)) return invalid("a must be finite and > 0");
+  if (loss_type == CERES_HIP_LOSS_TOLERANT) {
+    if (!std::isfinite(a) || a < 0.0) return invalid("a must be finite and >= 0 for the tolerant loss");
+    if (!std::isfinite(b) || b <= 0.0) return invalid("b must be finite and > 0 for the tolerant loss");
+  }
+  // the constants each loss's constructor derives (include/ceres/loss_function.h:131-330, I/loss_function.cc:134-137)
+  LossParams L;
+  L.type = loss_type; L.k = scale;
+  switch (loss_type) {
+    case CERES_HIP_LOSS_HUBER: L.a = a; L.b = a * a; break;
+    case CERES_HIP_LOSS_SOFTLONE:
+    case CERES_HIP_LOSS_CAUCHY: L.b = a * a; L.c = 1.0 / L.b; break;
+    case CERES_HIP_LOSS_ARCTAN: L.a = a; L.b = 1.0 / (a * a); break;
+    case CERES_HIP_LOSS_TOLERANT: L.a = a; L.b = b; L.c = b * std::log(1.0 + std::exp(-a / b)); break;
+    case CERES_HIP_LOSS_TUKEY: L.b = a * a; break;
+    default: break;
+  }
+  // the trivial loss unscaled IS the squared loss: the kernels' squared-loss instantiations run (a problem that never set a loss)
+  if (loss_type == CERES_HIP_LOSS_TRIVIAL && scale == 1.0) L = LossParams{};
+  p->loss = L;
+  return 0;
+}
+
 int ceres_hip_bal_evaluate(ceres_hip_bal* p, const double* state, double* cost, double* residuals, double* gradient,
                            double* jacobian_values) {
   if (!p || !state || !cost) return CERES_HIP_E_INVALID;
@@ -339,6 +376,7 @@ int ceres_hip_debug_bal_evaluate_tiles_timing(ceres_hip_bal* p, const double* st
     BalEvalTilesArgs T;   // (the launches alone: no copy of the partial sums, no synchronisation in between)
     T.debug_flags = flags;
     T.e.n_rows = p->no; T.e.state = p->d_x; T.e.cam_base = 3 * int64_t(p->np); T.e.residuals = p->d_res; T.e.values = p->d_vals; T.e.partials = p->d_parts;
+    T.e.loss = p->loss;   // (what ceres_hip_bal_minimize runs)
     T.n_tiles = s->plan.n_tiles; T.slot_bpos = s->d_slot_bpos; T.slot_fpos = s->d_slot_fpos;
     T.J_out = s->d_J; T.tile_pitch = s->ops->tile_pitch; T.b_out = s->d_bt;
     T.slot_cam = p->d_slot_cam; T.slot_pt = p->d_slot_pt; T.slot_obs = p->d_slot_obs; T.pt_pack = p->d_pt_pack; T.cam_pack = p->d_cam_pack;

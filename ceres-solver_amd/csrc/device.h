@@ -168,6 +168,16 @@ struct LmFuse {
   double* D_f = nullptr;
 };
 
+// The robust loss of the BAL front end (robust_loss.h; ceres_hip_bal_set_loss).  type: CERES_HIP_LOSS_* of include/ceres_hip.h, or
+// kLossNone; a, b, c: the constants the reference's constructor of that loss derives from its parameters (include/ceres/loss_function.h);
+// k: ScaledLoss's factor.  Kernels that take one are instantiated twice: kLossNone runs the squared-loss instantiation.
+constexpr int kLossNone = -1, kLossTrivial = 0, kLossHuber = 1, kLossSoftLOne = 2, kLossCauchy = 3, kLossArctan = 4, kLossTolerant = 5,
+              kLossTukey = 6;
+struct LossParams {
+  int32_t type = kLossNone;
+  double a = 0.0, b = 0.0, c = 0.0, k = 1.0;
+};
+
 // Work items of the camera-block kernel: <= kCamChunk consecutive observations of one camera.
 struct CamItems {
   const int32_t *cam = nullptr, *begin = nullptr, *end = nullptr;
@@ -178,6 +188,7 @@ struct CamItems {
   const double *ev_cam_pack = nullptr, *ev_pt_pack = nullptr;
   const int32_t* ev_pt = nullptr;
   const double2* ev_obs = nullptr;
+  LossParams ev_loss;   // the evaluated F cells are corrected by this loss (kLossNone: the squared loss)
 };
 struct CamGather {
   const double* parts = nullptr;          // nullptr: the blocks are already assembled in memory
@@ -543,6 +554,7 @@ struct BalEvalArgs {
   double* residuals = nullptr;        // 2 per row, or nullptr
   double* values = nullptr;           // E cell at 6 r, F cell at 6 n_rows + 18 r
   double* partials = nullptr;         // cost partial per workgroup (<= 2048)
+  LossParams loss;                    // cost = sum rho / 2, corrected residuals and Jacobian (kLossNone: the squared loss)
 };
 hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, hipStream_t stream);
 // The same in TILE order for the <2,3,9> fused path: the Jacobian lands in the solver's tiles (J_out, b_out: BalArgs' layout), the F

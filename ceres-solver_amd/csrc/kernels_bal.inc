@@ -61,6 +61,7 @@
 #endif
 #if CERES_HIP_NR == 2 && CERES_HIP_NE == 3 && CERES_HIP_NF == 9 && CERES_HIP_NS == 0
 #define CERES_HIP_IS_BAL_SHAPE 1
+#include "robust_loss.h"
 #include "snavely.h"
 #else
 #define CERES_HIP_IS_BAL_SHAPE 0
@@ -2879,7 +2880,9 @@ __global__ __launch_bounds__(256) void bal_camera_items_kernel(const double* __r
 // wrote: on die), the pixel and the point index from camera-major lists (20 bytes, coalesced) and M_o — instead of a 144-byte cell
 // of a 720 MB stream at 2.3x its size in line fetches (design/03: the over-fetch this pass could not shed while F came from memory).
 // The evaluator then writes NO caller-layout copy of the Jacobian at all.
-template <bool SCHUR>
+// ROBUST: the F cells are corrected by items.ev_loss before the column scaling, as the tile-order evaluator corrects its own
+// (robust_loss.h) — the blocks are then those of the Jacobian the solver holds.
+template <bool SCHUR, bool ROBUST>
 __global__ __launch_bounds__(256) void bal_camera_items_eval_kernel(CamItems items, const int32_t* __restrict__ cam_slot,
                                                                     const double* __restrict__ Mo, double* __restrict__ parts) {
   const int lane = threadIdx.x & 63;
@@ -2902,6 +2905,12 @@ __global__ __launch_bounds__(256) void bal_camera_items_eval_kernel(CamItems ite
     const double X3[3] = {p0.x, p0.y, p1.x};
     double res[2], jc[18], jp[6];
     snavely<true>(cam9, X3, o.x, o.y, res, jc, jp);
+    if constexpr (ROBUST) {
+      const double sq = res[0] * res[0] + res[1] * res[1];
+      double rho[3];
+      robust_rho(items.ev_loss, sq, rho);
+      robust_correct_jacobian<9>(robust_corrector(sq, rho), res[0], res[1], jc);
+    }
     double f0[NF], f1[NF];
 #pragma unroll
     for (int k = 0; k < NF; ++k) { f0[k] = jc[k] * cr[9 + k]; f1[k] = jc[9 + k] * cr[9 + k]; }
@@ -3684,8 +3693,11 @@ static hipError_t CameraItems(bool schur, const double* values, const CamItems& 
   const dim3 grid((items.count + 3) / 4);
   if (items.ev_cam_pack) {   // the F cells are evaluated, not read (values may be nullptr)
 #if CERES_HIP_IS_BAL_SHAPE
-    if (schur) hipLaunchKernelGGL((bal_camera_items_eval_kernel<true>), grid, dim3(256), 0, stream, items, cam_slot, Mo, parts);
-    else hipLaunchKernelGGL((bal_camera_items_eval_kernel<false>), grid, dim3(256), 0, stream, items, cam_slot, Mo, parts);
+    const bool robust = items.ev_loss.type != kLossNone;
+    if (schur && robust) hipLaunchKernelGGL((bal_camera_items_eval_kernel<true, true>), grid, dim3(256), 0, stream, items, cam_slot, Mo, parts);
+    else if (schur) hipLaunchKernelGGL((bal_camera_items_eval_kernel<true, false>), grid, dim3(256), 0, stream, items, cam_slot, Mo, parts);
+    else if (robust) hipLaunchKernelGGL((bal_camera_items_eval_kernel<false, true>), grid, dim3(256), 0, stream, items, cam_slot, Mo, parts);
+    else hipLaunchKernelGGL((bal_camera_items_eval_kernel<false, false>), grid, dim3(256), 0, stream, items, cam_slot, Mo, parts);
     return hipGetLastError();
 #else
     return hipErrorInvalidValue;

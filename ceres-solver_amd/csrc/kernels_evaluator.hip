@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "device.h"
+#include "robust_loss.h"
 #include "snavely.h"
 
 namespace chip {
@@ -31,7 +32,9 @@ __device__ __forceinline__ double wave_max_e(double v) {
   return v;
 }
 
-template <bool JAC>
+// ROBUST: A.loss applies (robust_loss.h) — cost rho / 2, the Jacobian corrected with the uncorrected residual, then the residual; the
+// Jacobi column scaling comes after the correction.  !ROBUST: the squared loss, as this kernel was before losses existed.
+template <bool JAC, bool ROBUST>
 __global__ __launch_bounds__(kVecBlock) void bal_evaluate_kernel(BalEvalArgs A) {
   __shared__ double sh[4];
   double cost = 0.0;
@@ -46,7 +49,22 @@ __global__ __launch_bounds__(kVecBlock) void bal_evaluate_kernel(BalEvalArgs A) 
 #pragma unroll
     for (int i = 0; i < 3; ++i) X[i] = ps[i];
     snavely<JAC>(cam, X, o.x, o.y, res, jc, jp);
-    cost += 0.5 * (res[0] * res[0] + res[1] * res[1]);
+    if constexpr (ROBUST) {
+      const double sq = res[0] * res[0] + res[1] * res[1];
+      double rho[3];
+      robust_rho(A.loss, sq, rho);
+      cost += 0.5 * rho[0];
+      if (JAC || A.residuals) {   // (cost only: no Corrector, I/residual_block.cc:175-178)
+        const RobustCorrector C = robust_corrector(sq, rho);
+        if constexpr (JAC) {
+          robust_correct_jacobian<9>(C, res[0], res[1], jc);
+          robust_correct_jacobian<3>(C, res[0], res[1], jp);
+        }
+        res[0] *= C.residual_scaling; res[1] *= C.residual_scaling;
+      }
+    } else {
+      cost += 0.5 * (res[0] * res[0] + res[1] * res[1]);
+    }
     if (A.residuals) reinterpret_cast<double2*>(A.residuals)[r] = make_double2(res[0], res[1]);
     if constexpr (JAC) {
       if (A.scale) {
@@ -133,7 +151,9 @@ __device__ __forceinline__ void issue_tile_rec(const BalEvalTilesArgs& T, const 
   for (int i = 0; i < 3; ++i) r.p[i] = pp[i];
 }
 
-template <int DBG, bool F_COPY>   // DBG: BalEvalTilesArgs::debug_flags, compile-time (a run-time flag's branches cost the static wait counts)
+// DBG: BalEvalTilesArgs::debug_flags, compile-time (a run-time flag's branches cost the static wait counts).  ROBUST: T.e.loss applies, as
+// in bal_evaluate_kernel (the corrected values go to the tiles, the b tiles, the residuals and the F copy; padding slots add no cost).
+template <int DBG, bool F_COPY, bool ROBUST>
 __global__ __launch_bounds__(kVecBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void bal_evaluate_tiles_kernel(BalEvalTilesArgs T) {
   static_assert(kVecBlock == 256, "four waves per workgroup");
   __shared__ double sh[4];
@@ -157,7 +177,7 @@ __global__ __launch_bounds__(kVecBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
   for (; tile < T.n_tiles; tile += stride) {
     TileRec rec1;
     TileIdx ix2;
-    issue_tile_rec(T, ix1, rec1);                                                           // tile + stride: its index words arrived an iteration ago
+    if constexpr (!ROBUST) issue_tile_rec(T, ix1, rec1);                                    // tile + stride: its index words arrived an iteration ago
     issue_tile_idx(T, tile + 2 * stride < last ? tile + 2 * stride : last, lane, ix2);
     const int64_t sl = tile * 64 + lane;
     const int bp = ix.bp;                      // 2 x row, -1: padding
@@ -167,6 +187,20 @@ __global__ __launch_bounds__(kVecBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
       const double cam9[9] = {rec.c[0].x, rec.c[0].y, rec.c[1].x, rec.c[1].y, rec.c[2].x, rec.c[2].y, rec.c[3].x, rec.c[3].y, rec.c[4].x};
       const double X3[3] = {rec.p[0].x, rec.p[0].y, rec.p[1].x};
       snavely<true>(cam9, X3, ix.obs.x, ix.obs.y, res, jc, jp);
+      if constexpr (ROBUST) {
+        const double sq = res[0] * res[0] + res[1] * res[1];
+        double rho[3];
+        robust_rho(A.loss, sq, rho);
+        cost += bp >= 0 ? 0.5 * rho[0] : 0.0;
+        const RobustCorrector C = robust_corrector(sq, rho);
+        // the next tile's records are requested here, after the loss, not at the top: the loss's transcendental functions need the
+        // registers those 24 doubles would hold (requested at the top, this instantiation spills); still ahead of this tile's stores, so
+        // that waiting for them is a wait for loads alone
+        issue_tile_rec(T, ix1, rec1);
+        robust_correct_jacobian<9>(C, res[0], res[1], jc);
+        robust_correct_jacobian<3>(C, res[0], res[1], jp);
+        res[0] *= C.residual_scaling; res[1] *= C.residual_scaling;
+      }
       const double sc[9] = {rec.c[4].y, rec.c[5].x, rec.c[5].y, rec.c[6].x, rec.c[6].y, rec.c[7].x, rec.c[7].y, rec.c[8].x, rec.c[8].y};
 #pragma unroll
       for (int j = 0; j < 9; ++j) { jc[j] *= sc[j]; jc[9 + j] *= sc[j]; }
@@ -179,7 +213,7 @@ __global__ __launch_bounds__(kVecBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
 #pragma unroll
       for (int j = 0; j < 6; ++j) jp[j] = 0.0;
     }
-    cost += 0.5 * (res[0] * res[0] + res[1] * res[1]);
+    if constexpr (!ROBUST) cost += 0.5 * (res[0] * res[0] + res[1] * res[1]);
     // (padding lanes store their zeros into their own slot of the b tile — which holds zeros — instead of skipping the store: a store
     // under a lane predicate may be branched over, and the compiler then counts on fewer stores in flight, so that its wait for the
     // NEXT tile's index words would cover ten of this tile's stores.  Not one shared dummy line: non-temporal stores of thousands of
@@ -269,8 +303,13 @@ hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, h
   int64_t g = (A.n_rows + kVecBlock - 1) / kVecBlock;
   const int grid = int(g < 1 ? 1 : (g > 2048 ? 2048 : g));
   *nparts = grid;
-  if (jacobian) hipLaunchKernelGGL(bal_evaluate_kernel<true>, dim3(grid), dim3(kVecBlock), 0, stream, A);
-  else hipLaunchKernelGGL(bal_evaluate_kernel<false>, dim3(grid), dim3(kVecBlock), 0, stream, A);
+  if (A.loss.type == kLossNone) {
+    if (jacobian) hipLaunchKernelGGL((bal_evaluate_kernel<true, false>), dim3(grid), dim3(kVecBlock), 0, stream, A);
+    else hipLaunchKernelGGL((bal_evaluate_kernel<false, false>), dim3(grid), dim3(kVecBlock), 0, stream, A);
+  } else {
+    if (jacobian) hipLaunchKernelGGL((bal_evaluate_kernel<true, true>), dim3(grid), dim3(kVecBlock), 0, stream, A);
+    else hipLaunchKernelGGL((bal_evaluate_kernel<false, true>), dim3(grid), dim3(kVecBlock), 0, stream, A);
+  }
   return hipGetLastError();
 }
 
@@ -280,9 +319,15 @@ hipError_t LaunchBalEvaluateTiles(const BalEvalTilesArgs& T, int64_t n_points, i
   const int64_t g = (T.n_tiles + 3) / 4;
   const int grid = int(g < 1 ? 1 : (g > 2048 ? 2048 : g));
   *nparts = grid;
-#define EVAL_TILES_CASE(D) case D: hipLaunchKernelGGL((bal_evaluate_tiles_kernel<D, true>), dim3(grid), dim3(kVecBlock), 0, stream, T); break;
+  const bool robust = T.e.loss.type != kLossNone;
+#define EVAL_TILES_CASE(D)                                                                                                    \
+  case D:                                                                                                                     \
+    if (robust) hipLaunchKernelGGL((bal_evaluate_tiles_kernel<D, true, true>), dim3(grid), dim3(kVecBlock), 0, stream, T);   \
+    else hipLaunchKernelGGL((bal_evaluate_tiles_kernel<D, true, false>), dim3(grid), dim3(kVecBlock), 0, stream, T);         \
+    break;
   if (!T.e.values) {
-    hipLaunchKernelGGL((bal_evaluate_tiles_kernel<0, false>), dim3(grid), dim3(kVecBlock), 0, stream, T);
+    if (robust) hipLaunchKernelGGL((bal_evaluate_tiles_kernel<0, false, true>), dim3(grid), dim3(kVecBlock), 0, stream, T);
+    else hipLaunchKernelGGL((bal_evaluate_tiles_kernel<0, false, false>), dim3(grid), dim3(kVecBlock), 0, stream, T);
   } else {
     switch (T.debug_flags) {
       EVAL_TILES_CASE(0) EVAL_TILES_CASE(1) EVAL_TILES_CASE(2) EVAL_TILES_CASE(3) EVAL_TILES_CASE(4) EVAL_TILES_CASE(7) EVAL_TILES_CASE(16)

@@ -198,6 +198,7 @@ ABI += [
     ("ceres_hip_debug_bal_evaluate_tiles_timing", c_int32, [c_void_p, _DP, c_int32, c_int32, _DP]),
     ("ceres_hip_bal_sizes", c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     ("ceres_hip_bal_get_row_order", c_int32, [c_void_p, POINTER(c_int32)]),
+    ("ceres_hip_bal_set_loss", c_int32, [c_void_p, c_int32, c_double, c_double, c_double]),
     ("ceres_hip_bal_evaluate", c_int32, [c_void_p, _DP, _DP, _DP, _DP, _DP]),
     ("ceres_hip_minimizer_default_options", None, [POINTER(CMinimizerOptions)]),
     ("ceres_hip_bal_minimize", c_int32, [c_void_p, POINTER(CMinimizerOptions), _DP, POINTER(CMinimizerSummary)]),
@@ -825,6 +826,10 @@ def debug_long_rounds(bs: BlockStructure, num_eliminate_blocks: int, renumber: b
 
 
 CONVERGENCE, MINIMIZER_NO_CONVERGENCE, MINIMIZER_FAILURE = 0, 1, 2
+# CERES_HIP_LOSS_* (include/ceres_hip.h): the robust losses of BalProblem.set_loss, by name
+LOSS_TRIVIAL, LOSS_HUBER, LOSS_SOFTLONE, LOSS_CAUCHY, LOSS_ARCTAN, LOSS_TOLERANT, LOSS_TUKEY = range(7)
+LOSSES = {"trivial": LOSS_TRIVIAL, "huber": LOSS_HUBER, "soft_l_one": LOSS_SOFTLONE, "cauchy": LOSS_CAUCHY, "arctan": LOSS_ARCTAN,
+          "tolerant": LOSS_TOLERANT, "tukey": LOSS_TUKEY}
 
 
 class BalProblem:
@@ -919,6 +924,16 @@ class BalProblem:
     def state_to_bal(self, state):
         a = _f64(state, self.num_parameters)
         return np.concatenate([a[3 * self.num_points:], a[:3 * self.num_points]])
+
+    def set_loss(self, kind, a=1.0, b=1.0, scale=1.0):
+        """The robust loss of every observation, ScaledLoss(kind(a[, b]), scale) (include/ceres/loss_function.h): "trivial", "huber",
+        "soft_l_one", "cauchy", "arctan", "tolerant" (a and b) or "tukey" — or a LOSS_* number.  bundle_adjuster --robustify is
+        set_loss("huber", 1.0).  In force for later evaluate / minimize calls until set again; "trivial" with scale 1 is the squared loss."""
+        if isinstance(kind, str):
+            if kind not in LOSSES:
+                raise ValueError(f"unknown loss kind {kind!r}: one of {', '.join(LOSSES)}")
+            kind = LOSSES[kind]
+        self._check(self._lib.ceres_hip_bal_set_loss(self._h, int(kind), float(a), float(b), float(scale)))
 
     def evaluate(self, state, residuals=False, gradient=False, jacobian=False):
         """Evaluator::Evaluate: returns (cost, residuals|None, gradient|None, jacobian values|None)."""

@@ -69,6 +69,12 @@ class HipBalProblem {
 
   int NumParameters() const { return int(num_parameters_); }   // Evaluator::NumParameters, I/evaluator.h:151
   int NumResiduals() const { return int(num_residuals_); }     // Evaluator::NumResiduals, :158
+  // The loss of every residual block, ScaledLoss(loss, scale): loss_type CERES_HIP_LOSS_*, a / b its constructor arguments
+  // (bundle_adjuster --robustify: SetLoss(CERES_HIP_LOSS_HUBER, 1.0)).  Applies to the later Evaluate / Minimize calls.
+  void SetLoss(int loss_type, double a, double b = 1.0, double scale = 1.0) {
+    if (ceres_hip_bal_set_loss(handle_, loss_type, a, b, scale) != CERES_HIP_OK)
+      throw std::invalid_argument(std::string(ceres_hip_bal_last_error(handle_)));
+  }
   // Evaluator::Evaluate (I/evaluator.h:116-124); residuals / gradient / jacobian values may be null
   bool Evaluate(const double* state, double* cost, double* residuals, double* gradient, double* jacobian_values) {
     return ceres_hip_bal_evaluate(handle_, state, cost, residuals, gradient, jacobian_values) == CERES_HIP_OK;

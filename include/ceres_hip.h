@@ -448,9 +448,29 @@ ceres_hip_solver* ceres_hip_bal_linear_solver(ceres_hip_bal* p);
 int ceres_hip_bal_sizes(const ceres_hip_bal* p, int64_t* num_parameters, int64_t* num_residuals, int64_t* num_jacobian_values);
 /* row_observation[r] = index of the observation residual row block r belongs to. */
 int ceres_hip_bal_get_row_order(const ceres_hip_bal* p, int32_t* row_observation);
+/* Robust losses (include/ceres/loss_function.h:131-330, internal/ceres/loss_function.cc:46-175).  Ceres has no enumeration of
+ * them: these numbers are this ABI's own.  a, b: the loss's constructor arguments (Tolerant takes both, the others a only). */
+#define CERES_HIP_LOSS_TRIVIAL 0   /* TrivialLoss: rho(s) = s                                  */
+#define CERES_HIP_LOSS_HUBER 1     /* HuberLoss(a)                                             */
+#define CERES_HIP_LOSS_SOFTLONE 2  /* SoftLOneLoss(a)                                          */
+#define CERES_HIP_LOSS_CAUCHY 3    /* CauchyLoss(a)                                            */
+#define CERES_HIP_LOSS_ARCTAN 4    /* ArctanLoss(a)                                            */
+#define CERES_HIP_LOSS_TOLERANT 5  /* TolerantLoss(a, b)                                       */
+#define CERES_HIP_LOSS_TUKEY 6     /* TukeyLoss(a)                                             */
+/* The loss of every observation of the problem — Problem::AddResidualBlock(cost, loss, camera, point) with one loss for all, as
+ * bundle_adjuster --robustify does (HuberLoss(1.0): examples/bundle_adjuster.cc:114,331) — wrapped in ScaledLoss(loss, scale).
+ * It stays in force for the later ceres_hip_bal_evaluate / ceres_hip_bal_minimize calls until set again; a problem that never sets
+ * one has the plain squared loss (as has CERES_HIP_LOSS_TRIVIAL with scale 1).  It is applied where Ceres applies it, in the
+ * Evaluator (internal/ceres/residual_block.cc:161-195, the Corrector of internal/ceres/corrector.cc:41-135), before the linear
+ * solver sees the Jacobian.  CERES_HIP_E_INVALID (message in ceres_hip_bal_last_error; of ceres_hip_bal_last_error(NULL) for a NULL
+ * handle) for an unknown loss_type or a non-finite or out-of-range parameter: a <= 0 for the one-parameter losses, a < 0 or b <= 0
+ * for TOLERANT, scale <= 0.  b is ignored by the other losses, a by TRIVIAL. */
+int ceres_hip_bal_set_loss(ceres_hip_bal* p, int32_t loss_type, double a, double b, double scale);
 /* Evaluator::Evaluate.  Host pointers; cost is required, the others may be NULL.  jacobian_values
  * is UNSCALED; gradient = J^T residuals.  Leaves the evaluated point loaded in the linear solver
- * (as ceres_hip_load_device would), so the ceres_hip_op_* entry points can be applied to it. */
+ * (as ceres_hip_load_device would), so the ceres_hip_op_* entry points can be applied to it.
+ * With a loss set (ceres_hip_bal_set_loss): cost = 1/2 sum rho(|r|^2), and residuals, jacobian_values (still unscaled) and
+ * gradient are the Corrector's: r~, J~ and J~^T r~ (= sum rho' J^T r). */
 int ceres_hip_bal_evaluate(ceres_hip_bal* p, const double* state, double* cost, double* residuals, double* gradient,
                            double* jacobian_values);
 /* Solver::Options of the trust-region loop (include/ceres/solver.h defaults in comments). */
