@@ -29,7 +29,15 @@ struct ceres_hip_bal {
   double* h_parts = nullptr;  // pinned, kBalParts doubles
   int deferred_cost_parts = 0;  // an evaluation whose cost partials (d_parts[0 ..)) the next synchronising call collects
   LossParams loss;              // ceres_hip_bal_set_loss: applies to every observation (kLossNone: the squared loss)
+  // ceres_hip_bal_set_inner_iterations (inner_iterations.inc): CERES_HIP_INNER_*, in force until set again; the lists it runs on; and
+  // what the last ceres_hip_bal_minimize did with them (ceres_hip_bal_inner_iteration_stats)
+  int32_t inner_blocks = 0;
+  double inner_tolerance = 1e-3;
+  struct BalInner* inner = nullptr;
+  int32_t inner_steps = 0, inner_groups_used = 0;
+  double inner_seconds = 0.0;
 };
+void bal_inner_free(ceres_hip_bal* p);
 
 namespace {
 
@@ -158,6 +166,8 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 
 }  // namespace
 
+#include "inner_iterations.inc"
+
 extern "C" {
 
 void ceres_hip_minimizer_default_options(ceres_hip_minimizer_options* o) {
@@ -184,6 +194,7 @@ ceres_hip_solver* ceres_hip_bal_linear_solver(ceres_hip_bal* p) { return p ? p->
 void ceres_hip_bal_destroy(ceres_hip_bal* p) {
   if (!p) return;
   if (p->h_parts) (void)hipHostFree(p->h_parts);
+  bal_inner_free(p);
   if (p->s) ceres_hip_destroy(p->s);  // frees every device allocation made through dev_alloc
   delete p;
 }
@@ -412,6 +423,18 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
   int invalid_run = 0, iteration = 0;
   double x_cost = 0, grad_max = 0;
   s->have_lm_diag = false;
+  // inner iterations (inner_iterations.inc): set or not, this call's statistics start from zero
+  const bool inner_set = p->inner_blocks != CERES_HIP_INNER_NONE;
+  bool inner_enabled = inner_set;   // (TrustRegionMinimizer::inner_iterations_are_enabled_: the tolerance may switch it off)
+  p->inner_steps = 0; p->inner_seconds = 0.0; p->inner_groups_used = 0;
+  if (inner_set) {
+    if (s->world > 1) {
+      p->err = "ceres_hip_bal_minimize: inner iterations are not supported on sharded handles";
+      return CERES_HIP_E_UNSUPPORTED;
+    }
+    BAL_TRY(p, bal_inner_plan(p));
+    p->inner_groups_used = p->inner->num_groups;
+  }
 
   auto log_iter = [&](const ceres_hip_iteration_summary& it) {
     if (S->num_iterations_logged < CERES_HIP_MAX_LOGGED_ITERATIONS) S->iterations[S->num_iterations_logged++] = it;
@@ -496,21 +519,61 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
     }
     invalid_run = 0;
     // delta = step .* scale; candidate = Plus(x, delta); |x|, |delta|; the candidate's cost — two kernels, ONE host round trip
-    int nparts = 0;
+    // (inner iterations set: |x - candidate| too, a third kernel in the same round trip — Ceres' step norm, whether or not an inner
+    // pass follows: ParameterToleranceReached, I/trust_region_minimizer.cc:726-748)
+    int nparts = 0, ndiff = 0;
     double xn = 0, dn = 0, cand_cost = 0;
+    constexpr int kDiffParts = kBalSecondParts + 2 * kMaxVecGrid;
+    static_assert(kDiffParts + kMaxVecGrid <= kBalParts, "room for the |x - candidate|^2 partials");
+    auto collect_diff = [&](int nd) {
+      double d = 0;
+      for (int i = 0; i < nd; ++i) d += p->h_parts[kDiffParts + i];
+      return d;
+    };
     {
       const auto te = std::chrono::steady_clock::now();
       static_assert(2 * kMaxVecGrid <= kBalParts - kBalSecondParts, "room for |x|^2 and |delta|^2 partials");
       HIP_TRY(s, LaunchBalCandidate(x, p->d_step, scale, p->d_delta, cand, n, p->d_parts + kBalSecondParts, &nparts, st));
+      if (inner_set) HIP_TRY(s, LaunchBalDiffNorm(x, cand, n, p->d_parts + kDiffParts, &ndiff, st));
       BAL_TRY(p, bal_evaluate_device(p, cand, false, nullptr, nullptr, &cand_cost, true));
       const int nc = p->deferred_cost_parts;
       HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
       HIP_TRY(s, hipMemcpyAsync(p->h_parts + kBalSecondParts, p->d_parts + kBalSecondParts, sizeof(double) * 2 * nparts, hipMemcpyDeviceToHost, st));
+      if (inner_set) HIP_TRY(s, hipMemcpyAsync(p->h_parts + kDiffParts, p->d_parts + kDiffParts, sizeof(double) * ndiff, hipMemcpyDeviceToHost, st));
       HIP_TRY(s, hipStreamSynchronize(st));
       for (int i = 0; i < nparts; ++i) { xn += p->h_parts[kBalSecondParts + i]; dn += p->h_parts[kBalSecondParts + nparts + i]; }
       for (int i = 0; i < nc; ++i) cand_cost += p->h_parts[i];
+      if (inner_set) dn = collect_diff(ndiff);
       p->deferred_cost_parts = 0;
       S->evaluation_seconds += seconds_since(te);
+    }
+    // DoInnerIterationsIfNeeded, I/trust_region_minimizer.cc:509-587: one coordinate-descent pass from the candidate, which always
+    // replaces it; its cost change boosts the model cost change
+    double model_cost_change = lr.model_cost_change;
+    bool inner_useful = false;
+    if (inner_enabled && std::isfinite(cand_cost)) {
+      const auto ti = std::chrono::steady_clock::now();
+      ++p->inner_steps;
+      double inner_cost = 0;
+      BAL_TRY(p, bal_inner_pass(p, cand));
+      HIP_TRY(s, LaunchBalDiffNorm(x, cand, n, p->d_parts + kDiffParts, &ndiff, st));
+      BAL_TRY(p, bal_evaluate_device(p, cand, false, nullptr, nullptr, &inner_cost, true));
+      const int nc = p->deferred_cost_parts;
+      HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
+      HIP_TRY(s, hipMemcpyAsync(p->h_parts + kDiffParts, p->d_parts + kDiffParts, sizeof(double) * ndiff, hipMemcpyDeviceToHost, st));
+      HIP_TRY(s, hipStreamSynchronize(st));
+      for (int i = 0; i < nc; ++i) inner_cost += p->h_parts[i];
+      p->deferred_cost_parts = 0;
+      if (std::isfinite(inner_cost)) {
+        dn = collect_diff(ndiff);
+        model_cost_change += cand_cost - inner_cost;
+        inner_useful = inner_cost < std::min(x_cost, cand_cost);
+        inner_enabled = 1.0 - inner_cost / cand_cost > p->inner_tolerance;
+        cand_cost = inner_cost;
+      } else {   // (the evaluation failed: Ceres keeps the candidate as it was — rebuilt here from x and the step)
+        HIP_TRY(s, LaunchBalCandidate(x, p->d_step, scale, p->d_delta, cand, n, p->d_parts + kBalSecondParts, &nparts, st));
+      }
+      p->inner_seconds += seconds_since(ti);
     }
     it.step_norm = std::sqrt(dn);
     if (one_success && it.step_norm <= o->parameter_tolerance * (std::sqrt(xn) + o->parameter_tolerance)) {
@@ -526,8 +589,8 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
       log_iter(it);
       break;
     }
-    it.relative_decrease = (x_cost - cand_cost) / lr.model_cost_change;  // TrustRegionStepEvaluator, monotonic
-    if (it.relative_decrease > o->min_relative_decrease) {  // HandleSuccessfulStep :829-845
+    it.relative_decrease = (x_cost - cand_cost) / model_cost_change;  // TrustRegionStepEvaluator, monotonic
+    if (inner_useful || it.relative_decrease > o->min_relative_decrease) {  // IsStepSuccessful :801-825; HandleSuccessfulStep :829-845
       std::swap(x, cand);
       one_success = true;
       BAL_TRY(p, eval_jacobian());

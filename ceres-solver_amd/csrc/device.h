@@ -581,6 +581,26 @@ hipError_t LaunchBalCandidate(const double* x, const double* step, const double*
 // partial maxima of |g_i / scale_i|
 hipError_t LaunchBalGradientMax(const double* g, const double* scale, int64_t n, double* partials, int* nparts, hipStream_t stream);
 hipError_t LaunchBalJacobiScale(const double* colnorm2, double* scale, int64_t n, hipStream_t stream);
+// partials[0..g) = |a - b|^2 partial sums (the outer loop's step norm |x - candidate| after an inner pass)
+hipError_t LaunchBalDiffNorm(const double* a, const double* b, int64_t n, double* partials, int* nparts, hipStream_t stream);
+
+// ---- inner iterations of the BAL front end (kernels_inner.hip; ceres_hip_bal_inner_iterate) ----
+// One launch solves a list of parameter blocks of ONE group, each with its own Levenberg-Marquardt loop (CoordinateDescentMinimizer::Solve,
+// I/coordinate_descent_minimizer.cc:213-240), all other blocks held at their values in `state`.  Block b's observations are the entries
+// [ptr[b], ptr[b+1]): `other` names the camera (a point's rows) or the point (a camera's camera-major entries), `obs` the pixel.
+enum InnerForm { kInnerPointLane = 0, kInnerPointWave = 1, kInnerCameraWave = 2 };
+struct InnerArgs {
+  double* state = nullptr;            // [3 n_p | 9 n_c], in / out (the blocks of the list are updated in place)
+  int64_t cam_base = 0;               // 3 n_p
+  const int32_t* blocks = nullptr;    // point or camera numbers to solve
+  int32_t n_blocks = 0;
+  const int32_t* ptr = nullptr;       // per point / camera: its entries
+  const int32_t* other = nullptr;
+  const double2* obs = nullptr;
+  int32_t* iterations = nullptr;      // per point / camera: the iterations its loop took (nullptr: not written)
+  LossParams loss;
+};
+hipError_t LaunchInnerBlocks(const InnerArgs& A, int form, hipStream_t stream);
 
 }  // namespace chip
 #endif

@@ -199,6 +199,11 @@ ABI += [
     ("ceres_hip_bal_sizes", c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64)]),
     ("ceres_hip_bal_get_row_order", c_int32, [c_void_p, POINTER(c_int32)]),
     ("ceres_hip_bal_set_loss", c_int32, [c_void_p, c_int32, c_double, c_double, c_double]),
+    ("ceres_hip_bal_set_inner_iterations", c_int32, [c_void_p, c_int32, c_double]),
+    ("ceres_hip_bal_inner_iterate", c_int32, [c_void_p, _DP, _DP, _DP, POINTER(c_int32)]),
+    ("ceres_hip_bal_inner_iteration_stats", c_int32, [c_void_p, POINTER(c_int32), _DP, POINTER(c_int32)]),
+    ("ceres_hip_debug_inner_iteration_ordering", c_int32, [c_int32, c_int32, c_int64, POINTER(c_int32), POINTER(c_int32), c_int32,
+                                                           POINTER(c_int32), POINTER(c_int32)]),
     ("ceres_hip_bal_evaluate", c_int32, [c_void_p, _DP, _DP, _DP, _DP, _DP]),
     ("ceres_hip_minimizer_default_options", None, [POINTER(CMinimizerOptions)]),
     ("ceres_hip_bal_minimize", c_int32, [c_void_p, POINTER(CMinimizerOptions), _DP, POINTER(CMinimizerSummary)]),
@@ -830,6 +835,26 @@ CONVERGENCE, MINIMIZER_NO_CONVERGENCE, MINIMIZER_FAILURE = 0, 1, 2
 LOSS_TRIVIAL, LOSS_HUBER, LOSS_SOFTLONE, LOSS_CAUCHY, LOSS_ARCTAN, LOSS_TOLERANT, LOSS_TUKEY = range(7)
 LOSSES = {"trivial": LOSS_TRIVIAL, "huber": LOSS_HUBER, "soft_l_one": LOSS_SOFTLONE, "cauchy": LOSS_CAUCHY, "arctan": LOSS_ARCTAN,
           "tolerant": LOSS_TOLERANT, "tukey": LOSS_TUKEY}
+# CERES_HIP_INNER_* (include/ceres_hip.h): the orderings of BalProblem.set_inner_iterations, by bundle_adjuster's
+# --blocks_for_inner_iterations name
+INNER_NONE, INNER_AUTOMATIC, INNER_CAMERAS, INNER_POINTS, INNER_CAMERAS_POINTS, INNER_POINTS_CAMERAS = range(6)
+INNER_BLOCKS = {None: INNER_NONE, "automatic": INNER_AUTOMATIC, "cameras": INNER_CAMERAS, "points": INNER_POINTS,
+                "cameras,points": INNER_CAMERAS_POINTS, "points,cameras": INNER_POINTS_CAMERAS}
+
+
+def inner_iteration_ordering(num_cameras, num_points, camera_index, point_index, blocks="automatic"):
+    """ceres_hip_debug_inner_iteration_ordering: (group of every block in state order — points, then cameras; -1 outside —, groups)."""
+    lib = load_library()
+    cam = np.ascontiguousarray(camera_index, dtype=np.int32)
+    pt = np.ascontiguousarray(point_index, dtype=np.int32)
+    kind = INNER_BLOCKS[blocks] if blocks is None or isinstance(blocks, str) else int(blocks)
+    out = np.empty(int(num_points) + int(num_cameras), dtype=np.int32)
+    ng = c_int32()
+    rc = lib.ceres_hip_debug_inner_iteration_ordering(int(num_cameras), int(num_points), cam.shape[0], cam.ctypes.data_as(POINTER(c_int32)),
+                                                      pt.ctypes.data_as(POINTER(c_int32)), kind, out.ctypes.data_as(POINTER(c_int32)), byref(ng))
+    if rc != 0:
+        raise HipError(f"ceres_hip_debug_inner_iteration_ordering: error {rc}")
+    return out, ng.value
 
 
 class BalProblem:
@@ -934,6 +959,31 @@ class BalProblem:
                 raise ValueError(f"unknown loss kind {kind!r}: one of {', '.join(LOSSES)}")
             kind = LOSSES[kind]
         self._check(self._lib.ceres_hip_bal_set_loss(self._h, int(kind), float(a), float(b), float(scale)))
+
+    def set_inner_iterations(self, blocks="automatic", tolerance=1e-3):
+        """Inner iterations after every trust-region step of minimize (Solver::Options::use_inner_iterations, inner_iteration_ordering,
+        inner_iteration_tolerance): blocks = "automatic", "cameras", "points", "cameras,points", "points,cameras" (bundle_adjuster's
+        --blocks_for_inner_iterations) or None (off) — or an INNER_* number.  In force until set again."""
+        if blocks is None or isinstance(blocks, str):
+            if blocks not in INNER_BLOCKS:
+                raise ValueError(f"unknown blocks {blocks!r}: one of {', '.join(str(k) for k in INNER_BLOCKS)}")
+            blocks = INNER_BLOCKS[blocks]
+        self._check(self._lib.ceres_hip_bal_set_inner_iterations(self._h, int(blocks), float(tolerance)))
+
+    def inner_iterate(self, state):
+        """One coordinate-descent pass at state.  Returns (state, cost_before, cost_after, block_iterations: per block in state order, -1
+        outside the ordering)."""
+        x = _f64(state, self.num_parameters).copy()
+        c0, c1 = np.zeros(1), np.zeros(1)
+        its = np.empty(self.num_points + self.num_cameras, dtype=np.int32)
+        self._check(self._lib.ceres_hip_bal_inner_iterate(self._h, _p(x), _p(c0), _p(c1), its.ctypes.data_as(POINTER(c_int32))))
+        return x, float(c0[0]), float(c1[0]), its
+
+    def inner_iteration_stats(self):
+        """Of the last minimize: (num_inner_iteration_steps, inner_iteration_seconds, groups of the ordering)."""
+        n, t, g = c_int32(), np.zeros(1), c_int32()
+        self._check(self._lib.ceres_hip_bal_inner_iteration_stats(self._h, byref(n), _p(t), byref(g)))
+        return n.value, float(t[0]), g.value
 
     def evaluate(self, state, residuals=False, gradient=False, jacobian=False):
         """Evaluator::Evaluate: returns (cost, residuals|None, gradient|None, jacobian values|None)."""

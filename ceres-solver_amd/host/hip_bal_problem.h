@@ -75,6 +75,20 @@ class HipBalProblem {
     if (ceres_hip_bal_set_loss(handle_, loss_type, a, b, scale) != CERES_HIP_OK)
       throw std::invalid_argument(std::string(ceres_hip_bal_last_error(handle_)));
   }
+  // Inner iterations (Solver::Options::use_inner_iterations / inner_iteration_ordering / inner_iteration_tolerance): blocks
+  // CERES_HIP_INNER_* (bundle_adjuster --blocks_for_inner_iterations), NONE switches them off.  Applies to the later Minimize calls.
+  void SetInnerIterations(int blocks, double tolerance = 1e-3) {
+    if (ceres_hip_bal_set_inner_iterations(handle_, blocks, tolerance) != CERES_HIP_OK)
+      throw std::invalid_argument(std::string(ceres_hip_bal_last_error(handle_)));
+  }
+  // One coordinate-descent pass (CoordinateDescentMinimizer::Minimize) at state, in / out; block_iterations may be null
+  bool InnerIterate(double* state, double* cost_before, double* cost_after, int32_t* block_iterations = nullptr) {
+    return ceres_hip_bal_inner_iterate(handle_, state, cost_before, cost_after, block_iterations) == CERES_HIP_OK;
+  }
+  // Of the last Minimize: Solver::Summary::num_inner_iteration_steps, inner_iteration_time_in_seconds; groups of the ordering
+  bool InnerIterationStats(int32_t* num_inner_iteration_steps, double* inner_iteration_seconds, int32_t* num_groups) const {
+    return ceres_hip_bal_inner_iteration_stats(handle_, num_inner_iteration_steps, inner_iteration_seconds, num_groups) == CERES_HIP_OK;
+  }
   // Evaluator::Evaluate (I/evaluator.h:116-124); residuals / gradient / jacobian values may be null
   bool Evaluate(const double* state, double* cost, double* residuals, double* gradient, double* jacobian_values) {
     return ceres_hip_bal_evaluate(handle_, state, cost, residuals, gradient, jacobian_values) == CERES_HIP_OK;

@@ -466,6 +466,34 @@ int ceres_hip_bal_get_row_order(const ceres_hip_bal* p, int32_t* row_observation
  * handle) for an unknown loss_type or a non-finite or out-of-range parameter: a <= 0 for the one-parameter losses, a < 0 or b <= 0
  * for TOLERANT, scale <= 0.  b is ignored by the other losses, a by TRIVIAL. */
 int ceres_hip_bal_set_loss(ceres_hip_bal* p, int32_t loss_type, double a, double b, double scale);
+/* Inner iterations (Solver::Options::use_inner_iterations, inner_iteration_ordering, inner_iteration_tolerance: include/ceres/solver.h:686-715;
+ * bundle_adjuster --inner_iterations --blocks_for_inner_iterations: examples/bundle_adjuster.cc:83-88, 190-243).  After every valid
+ * trust-region step ceres_hip_bal_minimize runs one coordinate-descent pass from the candidate (TrustRegionMinimizer::
+ * DoInnerIterationsIfNeeded, internal/ceres/trust_region_minimizer.cc:509-587): group by group, every block of a group is refined by its
+ * own small Levenberg-Marquardt solve with Ceres' DEFAULT minimizer options and every other block fixed
+ * (CoordinateDescentMinimizer, internal/ceres/coordinate_descent_minimizer.cc:130-240), the loss included.  `blocks` picks the
+ * ordering: */
+#define CERES_HIP_INNER_NONE 0            /* no inner iterations (the default)                                       */
+#define CERES_HIP_INNER_AUTOMATIC 1       /* CoordinateDescentMinimizer::CreateOrdering: recursive independent sets,
+                                             reversed; degree ties broken by state position (points, then cameras)   */
+#define CERES_HIP_INNER_CAMERAS 2         /* every camera in group 0 (points are not refined)                        */
+#define CERES_HIP_INNER_POINTS 3          /* every point in group 0 (cameras are not refined)                         */
+#define CERES_HIP_INNER_CAMERAS_POINTS 4  /* cameras in group 0, points in group 1                                    */
+#define CERES_HIP_INNER_POINTS_CAMERAS 5  /* points in group 0, cameras in group 1                                    */
+/* In force for the later ceres_hip_bal_minimize / ceres_hip_bal_inner_iterate calls until set again.  tolerance =
+ * inner_iteration_tolerance (Ceres' default 1e-3): once a pass improves the candidate's cost by a relative amount <= tolerance, the
+ * rest of that minimize call runs without them.  CERES_HIP_E_INVALID (message as for ceres_hip_bal_set_loss) for a NULL handle, an
+ * unknown `blocks`, or a negative or non-finite tolerance. */
+int ceres_hip_bal_set_inner_iterations(ceres_hip_bal* p, int32_t blocks, double tolerance);
+/* One pass (CoordinateDescentMinimizer::Minimize) at `state` (host, in / out) with the handle's ordering and loss; cost_before /
+ * cost_after: the cost at the state given and returned.  block_iterations (may be NULL): per block in state order (points, then cameras)
+ * the iterations its Levenberg-Marquardt loop took, -1 for a block outside the ordering.  Bit-for-bit reproducible.
+ * CERES_HIP_E_INVALID with CERES_HIP_INNER_NONE set; CERES_HIP_E_UNSUPPORTED on a sharded handle. */
+int ceres_hip_bal_inner_iterate(ceres_hip_bal* p, double* state, double* cost_before, double* cost_after, int32_t* block_iterations);
+/* Of the last ceres_hip_bal_minimize: Solver::Summary::num_inner_iteration_steps and inner_iteration_time_in_seconds
+ * (include/ceres/solver.h:864, 914), and the number of groups of the ordering it ran (0 without inner iterations). */
+int ceres_hip_bal_inner_iteration_stats(const ceres_hip_bal* p, int32_t* num_inner_iteration_steps, double* inner_iteration_seconds,
+                                        int32_t* num_groups);
 /* Evaluator::Evaluate.  Host pointers; cost is required, the others may be NULL.  jacobian_values
  * is UNSCALED; gradient = J^T residuals.  Leaves the evaluated point loaded in the linear solver
  * (as ceres_hip_load_device would), so the ceres_hip_op_* entry points can be applied to it.
@@ -552,6 +580,12 @@ int ceres_hip_debug_plan(const ceres_hip_block_structure* bs, int32_t num_elimin
                          int64_t* n_tiles, int32_t* slot_row, int32_t* slot_cam, int32_t* slot_pt,
                          uint32_t* slot_seg, int32_t* tile_kind, int32_t* tile_aux, int64_t slot_capacity,
                          char* why_not, int32_t why_capacity);
+
+/* Debug: the inner-iteration ordering of a BAL structure (pure host code; what a handle with ceres_hip_bal_set_inner_iterations(p,
+ * blocks, ...) runs): group_of_block[num_points + num_cameras] = the group of every block in state order (points, then cameras), -1 for a
+ * block outside the ordering; *num_groups.  blocks: CERES_HIP_INNER_AUTOMATIC .. CERES_HIP_INNER_POINTS_CAMERAS. */
+int ceres_hip_debug_inner_iteration_ordering(int32_t num_cameras, int32_t num_points, int64_t num_observations, const int32_t* camera_index,
+                                             const int32_t* point_index, int32_t blocks, int32_t* group_of_block, int32_t* num_groups);
 
 /* DenseCholesky::FactorAndSolve on a caller-supplied matrix (I/dense_cholesky.cc: what DENSE_SCHUR runs on its reduced system,
  * I/schur_complement_solver.cc:163-222): A is n x n row-major with its UPPER triangle authoritative, x = A^-1 b.  The blocked
