@@ -5,6 +5,7 @@
 //   ceres_hip_bal_evaluate  = Evaluator::Evaluate              I/evaluator.h:116-124
 //   ceres_hip_bal_minimize  = TrustRegionMinimizer::Minimize   I/trust_region_minimizer.cc:68-845
 //                             with LevenbergMarquardtStrategy  I/levenberg_marquardt_strategy.cc:69-157
+//                             or DoglegStrategy                I/dogleg_strategy.cc (dogleg.inc)
 // The loop below follows the reference statement by statement (the same restatement as
 // oracle/bal_harness.cc, which is what the parity tests compare it with); only the places
 // where vectors live differ: everything of size num_parameters / num_residuals stays in HBM.
@@ -36,6 +37,10 @@ struct ceres_hip_bal {
   struct BalInner* inner = nullptr;
   int32_t inner_steps = 0, inner_groups_used = 0;
   double inner_seconds = 0.0;
+  // ceres_hip_bal_set_trust_region_strategy (dogleg.inc): CERES_HIP_LEVENBERG_MARQUARDT / CERES_HIP_DOGLEG, in force until set again;
+  // the dogleg strategy's device vectors (a = gradient / diagonal, b = gn / diagonal) and partial sums, made on first use
+  int32_t tr_strategy = CERES_HIP_LEVENBERG_MARQUARDT, dogleg_type = CERES_HIP_TRADITIONAL_DOGLEG;
+  double *d_dl_a = nullptr, *d_dl_b = nullptr, *d_dl_parts = nullptr;
 };
 void bal_inner_free(ceres_hip_bal* p);
 
@@ -167,6 +172,7 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 }  // namespace
 
 #include "inner_iterations.inc"
+#include "dogleg.inc"
 
 extern "C" {
 
@@ -427,6 +433,13 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
   const bool inner_set = p->inner_blocks != CERES_HIP_INNER_NONE;
   bool inner_enabled = inner_set;   // (TrustRegionMinimizer::inner_iterations_are_enabled_: the tolerance may switch it off)
   p->inner_steps = 0; p->inner_seconds = 0.0; p->inner_groups_used = 0;
+  // the dogleg strategy (dogleg.inc): its radius is `radius`, its other state lives here
+  const bool dogleg = p->tr_strategy == CERES_HIP_DOGLEG;
+  DoglegState dl;
+  if (dogleg) {
+    dl.type = p->dogleg_type;
+    BAL_TRY(p, dogleg_alloc(p));
+  }
   if (inner_set) {
     if (s->world > 1) {
       p->err = "ceres_hip_bal_minimize: inner iterations are not supported on sharded handles";
@@ -485,17 +498,24 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
     if (radius <= o->min_trust_region_radius) { finish(CERES_HIP_CONVERGENCE, "Minimum trust region radius reached."); break; }
     ++iteration;
     ceres_hip_iteration_summary it{};
-    // LevenbergMarquardtStrategy::ComputeStep + the model cost change, on the device (f1)
-    ceres_hip_lm_options lo{};
-    lo.radius = radius; lo.min_diagonal = o->min_lm_diagonal; lo.max_diagonal = o->max_lm_diagonal; lo.eta = o->eta;
-    lo.reuse_diagonal = reuse_diagonal ? 1 : 0;
     ceres_hip_lm_result lr{};
     const auto t0 = std::chrono::steady_clock::now();
-    BAL_TRY(p, lm_step_loaded(s, &lo, p->d_step, &lr));
-    HIP_TRY(s, hipStreamSynchronize(st));
-    S->linear_solver_seconds += seconds_since(t0);
-    ++S->num_linear_solves;
-    reuse_diagonal = true;
+    if (dogleg) {   // DoglegStrategy::ComputeStep + the model cost change (dogleg.inc)
+      int solves = 0;
+      dl.radius = radius;
+      BAL_TRY(p, dogleg_step(p, dl, o, reuse_diagonal, p->d_step, &lr, &solves));
+      S->linear_solver_seconds += seconds_since(t0);
+      S->num_linear_solves += solves;
+    } else {   // LevenbergMarquardtStrategy::ComputeStep + the model cost change, on the device (f1)
+      ceres_hip_lm_options lo{};
+      lo.radius = radius; lo.min_diagonal = o->min_lm_diagonal; lo.max_diagonal = o->max_lm_diagonal; lo.eta = o->eta;
+      lo.reuse_diagonal = reuse_diagonal ? 1 : 0;
+      BAL_TRY(p, lm_step_loaded(s, &lo, p->d_step, &lr));
+      HIP_TRY(s, hipStreamSynchronize(st));
+      S->linear_solver_seconds += seconds_since(t0);
+      ++S->num_linear_solves;
+      reuse_diagonal = true;
+    }
     it.linear_solver_iterations = lr.linear_solver.num_iterations;
     it.linear_solver_termination = lr.linear_solver.termination_type;
     if (lr.linear_solver.termination_type == CERES_HIP_FATAL_ERROR) {
@@ -511,7 +531,8 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
         finish(CERES_HIP_MINIMIZER_FAILURE, "Too many consecutive invalid steps.");
         break;
       }
-      radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
+      if (dogleg) { dl.mu *= kDoglegMuIncrease; dl.reuse = false; }   // StepIsInvalid: the radius stays
+      else { radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true; }
       it.cost = x_cost; it.gradient_max_norm = grad_max; it.trust_region_radius = radius;
       ++S->num_unsuccessful_steps;
       log_iter(it);
@@ -594,14 +615,22 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
       std::swap(x, cand);
       one_success = true;
       BAL_TRY(p, eval_jacobian());
-      radius = radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * it.relative_decrease - 1.0, 3));
-      radius = std::min(o->max_trust_region_radius, radius);
+      if (dogleg) {   // StepAccepted(relative_decrease): no clamp to max_trust_region_radius
+        if (it.relative_decrease < 0.25) radius *= 0.5;
+        if (it.relative_decrease > 0.75) radius = std::max(radius, 3.0 * dl.step_norm);
+        dl.mu = std::max(kDoglegMinMu, 2.0 * dl.mu / kDoglegMuIncrease);
+        dl.reuse = false;
+      } else {
+        radius = radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * it.relative_decrease - 1.0, 3));
+        radius = std::min(o->max_trust_region_radius, radius);
+      }
       decrease_factor = 2.0;
       reuse_diagonal = false;
       it.step_is_successful = 1;
       ++S->num_successful_steps;
     } else {
-      radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
+      if (dogleg) { radius *= 0.5; dl.reuse = true; }   // StepRejected
+      else { radius /= decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true; }
       ++S->num_unsuccessful_steps;
     }
     it.cost = it.step_is_successful ? x_cost : cand_cost;

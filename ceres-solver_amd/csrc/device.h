@@ -584,6 +584,17 @@ hipError_t LaunchBalJacobiScale(const double* colnorm2, double* scale, int64_t n
 // partials[0..g) = |a - b|^2 partial sums (the outer loop's step norm |x - candidate| after an inner pass)
 hipError_t LaunchBalDiffNorm(const double* a, const double* b, int64_t n, double* partials, int* nparts, hipStream_t stream);
 
+// ---- dogleg trust region of the BAL front end (kernels_dogleg.hip; dogleg.inc) ----
+constexpr int kDoglegGrid = 256;   // workgroups (and partial sums per scalar) of the two kernels below
+// partials[5 q + k], q < *nparts: workgroup q's share of |J a|^2, (J a).(J b), |J b|^2, (J a).f, (J b).f (k = 0 .. 4), one walk over
+// the caller-layout values; f == nullptr: the last two are 0
+hipError_t LaunchJacobianGram(const GenStructure& G, const double* values, const double* a, const double* b, const double* f,
+                              double* partials, int* nparts, hipStream_t stream);
+// a = J^T f / dsq (the strategy's gradient over its diagonal sqrt(dsq)); partials[3 q + k]: |gradient|^2, gradient.gn, |gn|^2 with
+// gn = sqrt(dsq) * b
+hipError_t LaunchDoglegPrep(const double* dsq, const double* jtf, const double* b, double* a, int64_t n, double* partials, int* nparts,
+                            hipStream_t stream);
+
 // ---- inner iterations of the BAL front end (kernels_inner.hip; ceres_hip_bal_inner_iterate) ----
 // One launch solves a list of parameter blocks of ONE group, each with its own Levenberg-Marquardt loop (CoordinateDescentMinimizer::Solve,
 // I/coordinate_descent_minimizer.cc:213-240), all other blocks held at their values in `state`.  Block b's observations are the entries

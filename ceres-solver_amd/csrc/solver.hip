@@ -16,10 +16,12 @@
 #include <chrono>
 #include <climits>
 #include <cmath>
+#include <complex>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <numeric>
@@ -96,6 +98,7 @@ struct ceres_hip_solver {
   bool fail_flag_clean = false, nonfinite_clean = false;  // cleared together at the start of a solve: the per-operator memsets are skipped once
   bool have_lm_diag = false;
   bool lm_want_model_cost = false;  // op_back_substitute also accumulates the model cost change (fused <2,3,9> path)
+  bool lm_skip_model_cost = false;  // set by the caller of lm_step_loaded (the dogleg strategy): Schur solvers form no model cost change
   // LM step on the fused path: the last kernel that touches the solution writes the negated step and checks it for finiteness
   // (ITERATIVE_SCHUR: the back-substitution kernel; CGNR: the model-cost kernel, which then also replaces the copy-out of x)
   bool lm_negate_in_solve = false;
@@ -2592,7 +2595,7 @@ int lm_step_loaded(ceres_hip_solver* s, const ceres_hip_lm_options* o, double* d
   s->have_lm_diag = true;
   s->D = s->lm_D;
   s->have_D = true;
-  s->lm_want_model_cost = is_schur(s) && s->path == CERES_HIP_PATH_BAL && s->fused_grid < 2 * kMaxVecGrid;  // (< : room for the remainder rows' partial)
+  s->lm_want_model_cost = !s->lm_skip_model_cost && is_schur(s) && s->path == CERES_HIP_PATH_BAL && s->fused_grid < 2 * kMaxVecGrid;  // (< : room for the remainder rows' partial)
   s->backsub_cost_parts = 0;
   // fused <2,3,9> path, implicit solvers: negation + finite check ride in the last kernel that touches the solution
   s->lm_negate_in_solve = s->path == CERES_HIP_PATH_BAL && !s->opt.use_explicit_schur_complement && !is_dense_schur(s);
@@ -2650,7 +2653,7 @@ int lm_step_loaded(ceres_hip_solver* s, const ceres_hip_lm_options* o, double* d
   } else if (s->backsub_cost_parts > 0) {  // the back-substitution kernel already formed it
     parts_local = s->scalar_partials;
     n_local = s->backsub_cost_parts;
-  } else {
+  } else if (!s->lm_skip_model_cost) {
     TRY(enqueue_model_cost_change(s, dx, &parts_local, &n_local));  // rows are sharded: every rank holds a share
   }
   double* hp = s->h_pinned;
@@ -2802,7 +2805,34 @@ int ceres_hip_time_op(ceres_hip_solver* s, int32_t op, int32_t iters, double* av
   hipStream_t st = s->stream;
   const int64_t n = is_schur(s) ? h.num_cols_f : h.num_cols;
   std::function<int()> body;
+  struct DeviceScratch {   // (operands of the two probes that need vectors of their own)
+    double* p = nullptr;
+    ~DeviceScratch() { if (p) (void)hipFree(p); }
+  } tmp;
+  const int64_t nc = h.num_cols;
   switch (op) {
+    case CERES_HIP_TIMED_MODEL_COST:
+      if (s->world > 1) return fail(s, CERES_HIP_E_UNSUPPORTED, "model-cost probe on one rank only");
+      HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp.p), sizeof(double) * std::max<int64_t>(1, nc)));
+      HIP_TRY(s, LaunchSet(tmp.p, 1.0, nc, st));
+      body = [&] {
+        const double* parts = nullptr;
+        int np = 0;
+        return enqueue_model_cost_change(s, tmp.p, &parts, &np);
+      };
+      break;
+    case CERES_HIP_TIMED_JACOBIAN_GRAM:
+      if (s->world > 1) return fail(s, CERES_HIP_E_UNSUPPORTED, "Gram probe on one rank only");
+      TRY(require_caller_values(s, "the Gram probe"));
+      HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp.p), sizeof(double) * (2 * nc + 5 * kDoglegGrid)));
+      HIP_TRY(s, LaunchSet(tmp.p, 1.0, nc, st));
+      HIP_TRY(s, LaunchSet(tmp.p + nc, 0.5, nc, st));
+      body = [&] {
+        int np = 0;
+        HIP_TRY(s, LaunchJacobianGram(s->G, s->values, tmp.p, tmp.p + nc, s->have_b ? s->b : nullptr, tmp.p + 2 * nc, &np, st));
+        return 0;
+      };
+      break;
     case CERES_HIP_TIMED_JTJX:
       if (is_schur(s)) return fail(s, CERES_HIP_E_INVALID, "jtjx needs a CGNR instance");
       TRY(ensure_D_int(s));

@@ -105,6 +105,34 @@ int ceres_hip_op_jtb(ceres_hip_solver* s, double* y) {
   return down(s, y, s->scratch_vec, s->hs.num_cols);
 }
 
+// the dogleg strategy's one pass over J (kernels_dogleg.hip), on host vectors
+int ceres_hip_op_jacobian_gram(ceres_hip_solver* s, const double* a, const double* b, double* out) {
+  if (!s) return CERES_HIP_E_INVALID;
+  if (!a || !b || !out) return fail(s, CERES_HIP_E_INVALID, "ceres_hip_op_jacobian_gram: NULL argument");
+  TRY(require_loaded(s));
+  TRY(require_caller_values(s, "ceres_hip_op_jacobian_gram"));
+  if (s->world > 1) return fail(s, CERES_HIP_E_UNSUPPORTED, "ceres_hip_op_jacobian_gram: sharded instances hold a share of the rows");
+  HIP_TRY(s, hipSetDevice(s->opt.device));
+  const size_t nc = size_t(s->hs.num_cols);
+  double* tmp = nullptr;
+  HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(double) * (2 * nc + 5 * kDoglegGrid)));
+  int np = 0;
+  hipError_t e = hipMemcpyAsync(tmp, a, sizeof(double) * nc, hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(tmp + nc, b, sizeof(double) * nc, hipMemcpyHostToDevice, s->stream);
+  if (e == hipSuccess) e = LaunchJacobianGram(s->G, s->values, tmp, tmp + nc, s->have_b ? s->b : nullptr, tmp + 2 * nc, &np, s->stream);
+  std::vector<double> h(size_t(5) * kDoglegGrid);
+  if (e == hipSuccess) e = hipMemcpyAsync(h.data(), tmp + 2 * nc, sizeof(double) * 5 * np, hipMemcpyDeviceToHost, s->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+  (void)hipFree(tmp);
+  if (e != hipSuccess) return fail(s, CERES_HIP_E_HIP, "ceres_hip_op_jacobian_gram: %s", hipGetErrorString(e));
+  for (int k = 0; k < 5; ++k) {
+    double t = 0;
+    for (int q = 0; q < np; ++q) t += h[size_t(5) * q + k];   // fixed order: deterministic
+    out[k] = t;
+  }
+  return 0;
+}
+
 int ceres_hip_op_schur_init(ceres_hip_solver* s) {
   TRY(require_loaded(s));
   HIP_TRY(s, hipSetDevice(s->opt.device));

@@ -35,7 +35,7 @@ UNIQUE_ID_BYTES = 128
 IPC_HANDLE_BYTES = 64
 
 (TIMED_JTJX, TIMED_SX, TIMED_SCHUR_INIT, TIMED_SCHUR_JACOBI, TIMED_BACK_SUBSTITUTE, TIMED_PACK, TIMED_BLOCK_JACOBI, TIMED_COPY,
- TIMED_READ_STREAM, TIMED_CGNR_SETUP) = range(1, 11)
+ TIMED_READ_STREAM, TIMED_CGNR_SETUP, TIMED_MODEL_COST, TIMED_JACOBIAN_GRAM) = range(1, 13)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -120,6 +120,7 @@ ABI = [
     ("ceres_hip_op_squared_column_norm", c_int32, [c_void_p, _DP]),
     ("ceres_hip_op_jtjx", c_int32, [c_void_p, _DP, _DP]),
     ("ceres_hip_op_jtb", c_int32, [c_void_p, _DP]),
+    ("ceres_hip_op_jacobian_gram", c_int32, [c_void_p, _DP, _DP, _DP]),
     ("ceres_hip_op_schur_init", c_int32, [c_void_p]),
     ("ceres_hip_get_schur_rhs", c_int32, [c_void_p, _DP]),
     ("ceres_hip_get_ete_inverse", c_int32, [c_void_p, _DP, c_int64]),
@@ -202,6 +203,8 @@ ABI += [
     ("ceres_hip_bal_set_inner_iterations", c_int32, [c_void_p, c_int32, c_double]),
     ("ceres_hip_bal_inner_iterate", c_int32, [c_void_p, _DP, _DP, _DP, POINTER(c_int32)]),
     ("ceres_hip_bal_inner_iteration_stats", c_int32, [c_void_p, POINTER(c_int32), _DP, POINTER(c_int32)]),
+    ("ceres_hip_bal_set_trust_region_strategy", c_int32, [c_void_p, c_int32, c_int32]),
+    ("ceres_hip_debug_dogleg_subspace_minimum", c_int32, [_DP, _DP, c_double, _DP]),
     ("ceres_hip_debug_inner_iteration_ordering", c_int32, [c_int32, c_int32, c_int64, POINTER(c_int32), POINTER(c_int32), c_int32,
                                                            POINTER(c_int32), POINTER(c_int32)]),
     ("ceres_hip_bal_evaluate", c_int32, [c_void_p, _DP, _DP, _DP, _DP, _DP]),
@@ -603,6 +606,13 @@ class HipLinearSolver:
         self._check(self._lib.ceres_hip_op_jtb(self._h, _p(out)))
         return out
 
+    def op_jacobian_gram(self, a, b):
+        """ceres_hip_op_jacobian_gram: (|J a|^2, (J a).(J b), |J b|^2, (J a).f, (J b).f) on the loaded J and f, one pass over J."""
+        n = self._info.num_cols
+        out = np.full(5, np.nan)
+        self._check(self._lib.ceres_hip_op_jacobian_gram(self._h, _p(_f64(a, n, "a")), _p(_f64(b, n, "b")), _p(out)))
+        return out
+
     def schur_init(self):
         self._check(self._lib.ceres_hip_op_schur_init(self._h))
 
@@ -842,6 +852,29 @@ INNER_BLOCKS = {None: INNER_NONE, "automatic": INNER_AUTOMATIC, "cameras": INNER
                 "cameras,points": INNER_CAMERAS_POINTS, "points,cameras": INNER_POINTS_CAMERAS}
 
 
+# CERES_HIP_LEVENBERG_MARQUARDT / CERES_HIP_DOGLEG and CERES_HIP_{TRADITIONAL,SUBSPACE}_DOGLEG (include/ceres_hip.h), by bundle_adjuster's
+# --trust_region_strategy / --dogleg names (without the _dogleg suffix)
+LEVENBERG_MARQUARDT, DOGLEG = 0, 1
+TRADITIONAL_DOGLEG, SUBSPACE_DOGLEG = 0, 1
+TRUST_REGION_STRATEGIES = {"levenberg_marquardt": LEVENBERG_MARQUARDT, "dogleg": DOGLEG}
+DOGLEG_TYPES = {"traditional": TRADITIONAL_DOGLEG, "subspace": SUBSPACE_DOGLEG}
+# what ceres_hip_debug_dogleg_subspace_minimum returns besides 0: the cases that fall back to the traditional step
+DOGLEG_NO_ROOT, DOGLEG_COSINE = 1, 2
+
+
+def dogleg_subspace_minimum(B, g, radius):
+    """ceres_hip_debug_dogleg_subspace_minimum: (code, x) — the unscaled boundary minimiser x of 1/2 x'Bx + g'x for the 2x2 B, and 0,
+    DOGLEG_NO_ROOT or DOGLEG_COSINE."""
+    lib = load_library()
+    Bm = np.ascontiguousarray(B, dtype=np.float64).reshape(4)
+    gv = np.ascontiguousarray(g, dtype=np.float64).reshape(2)
+    x = np.zeros(2)
+    rc = lib.ceres_hip_debug_dogleg_subspace_minimum(_p(Bm), _p(gv), float(radius), _p(x))
+    if rc < 0:
+        raise HipError(f"ceres_hip_debug_dogleg_subspace_minimum: error {rc}")
+    return rc, x
+
+
 def inner_iteration_ordering(num_cameras, num_points, camera_index, point_index, blocks="automatic"):
     """ceres_hip_debug_inner_iteration_ordering: (group of every block in state order — points, then cameras; -1 outside —, groups)."""
     lib = load_library()
@@ -970,6 +1003,20 @@ class BalProblem:
             blocks = INNER_BLOCKS[blocks]
         self._check(self._lib.ceres_hip_bal_set_inner_iterations(self._h, int(blocks), float(tolerance)))
 
+    def set_trust_region_strategy(self, strategy="levenberg_marquardt", dogleg="traditional"):
+        """Solver::Options::trust_region_strategy_type and dogleg_type (bundle_adjuster --trust_region_strategy, --dogleg):
+        strategy = "levenberg_marquardt" or "dogleg", dogleg = "traditional" or "subspace" (read with "dogleg" only) — or the numbers.
+        DOGLEG needs an exact factorisation (DENSE_SCHUR here).  In force for later minimize calls until set again."""
+        if isinstance(strategy, str):
+            if strategy not in TRUST_REGION_STRATEGIES:
+                raise ValueError(f"unknown strategy {strategy!r}: one of {', '.join(TRUST_REGION_STRATEGIES)}")
+            strategy = TRUST_REGION_STRATEGIES[strategy]
+        if isinstance(dogleg, str):
+            if dogleg not in DOGLEG_TYPES:
+                raise ValueError(f"unknown dogleg type {dogleg!r}: one of {', '.join(DOGLEG_TYPES)}")
+            dogleg = DOGLEG_TYPES[dogleg]
+        self._check(self._lib.ceres_hip_bal_set_trust_region_strategy(self._h, int(strategy), int(dogleg)))
+
     def inner_iterate(self, state):
         """One coordinate-descent pass at state.  Returns (state, cost_before, cost_after, block_iterations: per block in state order, -1
         outside the ordering)."""
@@ -996,7 +1043,7 @@ class BalProblem:
         return float(cost[0]), r, g, v
 
     def minimize(self, state, **opts):
-        """TrustRegionMinimizer::Minimize (LEVENBERG_MARQUARDT).  Returns (state, CMinimizerSummary)."""
+        """TrustRegionMinimizer::Minimize (LEVENBERG_MARQUARDT, or what set_trust_region_strategy chose).  Returns (state, CMinimizerSummary)."""
         o = CMinimizerOptions()
         self._lib.ceres_hip_minimizer_default_options(byref(o))
         for k, val in opts.items():

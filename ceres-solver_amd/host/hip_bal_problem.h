@@ -81,6 +81,13 @@ class HipBalProblem {
     if (ceres_hip_bal_set_inner_iterations(handle_, blocks, tolerance) != CERES_HIP_OK)
       throw std::invalid_argument(std::string(ceres_hip_bal_last_error(handle_)));
   }
+  // Trust-region strategy (Solver::Options::trust_region_strategy_type, dogleg_type; bundle_adjuster --trust_region_strategy --dogleg):
+  // CERES_HIP_LEVENBERG_MARQUARDT, or CERES_HIP_DOGLEG with CERES_HIP_TRADITIONAL_DOGLEG / CERES_HIP_SUBSPACE_DOGLEG.  DOGLEG needs a
+  // DENSE_SCHUR problem (Ceres refuses it with iterative solvers).  Applies to the later Minimize calls.
+  void SetTrustRegionStrategy(int strategy, int dogleg_type = CERES_HIP_TRADITIONAL_DOGLEG) {
+    if (ceres_hip_bal_set_trust_region_strategy(handle_, strategy, dogleg_type) != CERES_HIP_OK)
+      throw std::invalid_argument(std::string(ceres_hip_bal_last_error(handle_)));
+  }
   // One coordinate-descent pass (CoordinateDescentMinimizer::Minimize) at state, in / out; block_iterations may be null
   bool InnerIterate(double* state, double* cost_before, double* cost_after, int32_t* block_iterations = nullptr) {
     return ceres_hip_bal_inner_iterate(handle_, state, cost_before, cost_after, block_iterations) == CERES_HIP_OK;

@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <random>
+#include <string>
 #include <thread>
 #include <vector>
 
@@ -260,15 +261,24 @@ int RunStreamedLmStep(const char* name, BlockSparseMatrix* A, const std::vector<
 
 }  // namespace
 
-// host_driver <problem.txt> [max_num_iterations]: BALProblem + Evaluator + TrustRegionMinimizer through the C++ mirror
-int RunBalFile(const char* filename, int max_it) {
+// host_driver <problem.txt> [max_num_iterations [traditional_dogleg|subspace_dogleg]]: BALProblem + Evaluator + TrustRegionMinimizer
+// through the C++ mirror (with a dogleg type: DENSE_SCHUR and the DOGLEG strategy, bundle_adjuster --trust_region_strategy=dogleg --dogleg)
+int RunBalFile(const char* filename, int max_it, const char* dogleg) {
   const BalData data = BalData::Read(filename);
   LinearSolver::Options o;
-  o.type = ITERATIVE_SCHUR;
+  o.type = dogleg ? DENSE_SCHUR : ITERATIVE_SCHUR;
   o.preconditioner_type = SCHUR_JACOBI;
   o.min_num_iterations = 0;
   o.max_num_iterations = 500;
   HipBalProblem problem(o, data);
+  if (dogleg) {
+    const std::string kind(dogleg);
+    if (kind != "traditional_dogleg" && kind != "subspace_dogleg") {
+      std::printf("FAIL unknown dogleg type %s\n", dogleg);
+      return 1;
+    }
+    problem.SetTrustRegionStrategy(CERES_HIP_DOGLEG, kind == "subspace_dogleg" ? CERES_HIP_SUBSPACE_DOGLEG : CERES_HIP_TRADITIONAL_DOGLEG);
+  }
   std::vector<double> x = data.State();
   double cost0 = 0;
   if (!problem.Evaluate(x.data(), &cost0, nullptr, nullptr, nullptr)) return 1;
@@ -279,9 +289,9 @@ int RunBalFile(const char* filename, int max_it) {
   double cost1 = 0;
   if (!problem.Evaluate(x.data(), &cost1, nullptr, nullptr, nullptr)) return 1;
   std::printf("bal parameters=%d residuals=%d initial_cost=%.17g evaluated_initial=%.17g final_cost=%.17g evaluated_final=%.17g "
-              "successful=%d unsuccessful=%d termination=%d message=%s\n",
+              "successful=%d unsuccessful=%d termination=%d linear_solves=%d message=%s\n",
               problem.NumParameters(), problem.NumResiduals(), s.initial_cost, cost0, s.final_cost, cost1, s.num_successful_steps,
-              s.num_unsuccessful_steps, s.termination_type, s.message);
+              s.num_unsuccessful_steps, s.termination_type, s.num_linear_solves, s.message);
   return 0;
 }
 
@@ -290,7 +300,7 @@ int main(int argc, char** argv) {
     std::printf("FAIL no gfx950 device visible (the library has no CPU path)\n");
     return 2;
   }
-  if (argc >= 2) return RunBalFile(argv[1], argc >= 3 ? std::atoi(argv[2]) : 10);
+  if (argc >= 2) return RunBalFile(argv[1], argc >= 3 ? std::atoi(argv[2]) : 10, argc >= 4 ? argv[3] : nullptr);
   int bad = 0, nelim = 0;
   std::vector<double> b, D;
   auto p2 = Problem2(&b, &D, &nelim);

@@ -294,6 +294,10 @@ int ceres_hip_op_squared_column_norm(ceres_hip_solver* s, double* x);
 int ceres_hip_op_jtjx(ceres_hip_solver* s, const double* x, double* y);
 /* y = A^T b     CgnrSolver::SolveImpl rhs                        I/cgnr_solver.cc:188-191       */
 int ceres_hip_op_jtb(ceres_hip_solver* s, double* y);
+/* out[5] = |J a|^2, (J a).(J b), |J b|^2, (J a).f, (J b).f on the loaded J and right-hand side f (f not loaded: the last two are 0);
+ * a, b: host vectors of num_cols.  One pass over the caller-layout values: what the dogleg strategy of ceres_hip_bal_minimize reads
+ * per Jacobian (DoglegStrategy's Cauchy point, subspace model and model cost change, I/dogleg_strategy.cc:185-199, 648-719). */
+int ceres_hip_op_jacobian_gram(ceres_hip_solver* s, const double* a, const double* b, double* out);
 
 /* ImplicitSchurComplement::Init: block_diagonal (E^T E + D_e^2)^-1 and
  * rhs = F^T (b - E (E^T E)^-1 E^T b)                             I/implicit_schur_complement.cc:49-97,179-204,251-276 */
@@ -494,6 +498,18 @@ int ceres_hip_bal_inner_iterate(ceres_hip_bal* p, double* state, double* cost_be
  * (include/ceres/solver.h:864, 914), and the number of groups of the ordering it ran (0 without inner iterations). */
 int ceres_hip_bal_inner_iteration_stats(const ceres_hip_bal* p, int32_t* num_inner_iteration_steps, double* inner_iteration_seconds,
                                         int32_t* num_groups);
+/* Trust-region strategy of ceres_hip_bal_minimize (Solver::Options::trust_region_strategy_type, dogleg_type: include/ceres/solver.h;
+ * bundle_adjuster --trust_region_strategy --dogleg).  In force for the later ceres_hip_bal_minimize calls until set again; a handle that
+ * never set it runs LEVENBERG_MARQUARDT.  DOGLEG follows DoglegStrategy (I/dogleg_strategy.cc): the Gauss-Newton step of
+ * (J^T J + mu diag(J^T J)) with mu from 1e-8, the Cauchy point, and their traditional interpolation or the minimum of the model on the
+ * 2-D subspace they span; a rejected step reuses both (no linear solve), an invalid one multiplies mu by 10 and keeps the radius.
+ * dogleg_type is read only with CERES_HIP_DOGLEG.  CERES_HIP_E_INVALID for a NULL handle, an unknown value, or DOGLEG on an
+ * ITERATIVE_SCHUR or CGNR handle (Ceres' own message, I/solver.cc:431-438); CERES_HIP_E_UNSUPPORTED for DOGLEG on a sharded handle. */
+#define CERES_HIP_LEVENBERG_MARQUARDT 0
+#define CERES_HIP_DOGLEG 1
+#define CERES_HIP_TRADITIONAL_DOGLEG 0
+#define CERES_HIP_SUBSPACE_DOGLEG 1
+int ceres_hip_bal_set_trust_region_strategy(ceres_hip_bal* p, int32_t strategy, int32_t dogleg_type);
 /* Evaluator::Evaluate.  Host pointers; cost is required, the others may be NULL.  jacobian_values
  * is UNSCALED; gradient = J^T residuals.  Leaves the evaluated point loaded in the linear solver
  * (as ceres_hip_load_device would), so the ceres_hip_op_* entry points can be applied to it.
@@ -536,7 +552,8 @@ typedef struct ceres_hip_minimizer_summary {
   ceres_hip_iteration_summary iterations[CERES_HIP_MAX_LOGGED_ITERATIONS];
   char message[256];
 } ceres_hip_minimizer_summary;
-/* TrustRegionMinimizer::Minimize with LEVENBERG_MARQUARDT, monotonic steps.  state: host, in/out. */
+/* TrustRegionMinimizer::Minimize with LEVENBERG_MARQUARDT, or DOGLEG as ceres_hip_bal_set_trust_region_strategy chose; monotonic
+ * steps.  state: host, in/out. */
 int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* options, double* state,
                            ceres_hip_minimizer_summary* summary);
 /* Timing probe of the evaluator that writes the solver's tiles (what ceres_hip_bal_minimize runs per Jacobian evaluation on the
@@ -558,6 +575,8 @@ int ceres_hip_debug_bal_evaluate_tiles_timing(ceres_hip_bal* p, const double* st
 #define CERES_HIP_TIMED_COPY 8 /* plain device copy of the values array: HBM ceiling probe */
 #define CERES_HIP_TIMED_CGNR_SETUP 10 /* CGNR per-step set-up on the <2,3,9> path (re-layout + J^T b + JACOBI blocks) */
 #define CERES_HIP_TIMED_READ_STREAM 9 /* read-only pass over the packed tiles, same loads as the fused kernels */
+#define CERES_HIP_TIMED_MODEL_COST 11 /* -(J x)'(f + J x / 2) as the LM step forms it where nothing else does (fused path: the kJx pass) */
+#define CERES_HIP_TIMED_JACOBIAN_GRAM 12 /* the dogleg strategy's pass over J: what ceres_hip_op_jacobian_gram launches, on device vectors */
 int ceres_hip_time_op(ceres_hip_solver* s, int32_t op, int32_t iters, double* avg_ms);
 /* Per-phase event timings (ms) of the most recent ceres_hip_solve* / ceres_hip_lm_compute_step*.  The phases are bracketed by HIP events
  * on the solver's stream, and an event record between two kernels idles the device for about 6 us (a barrier packet with a completion
@@ -586,6 +605,16 @@ int ceres_hip_debug_plan(const ceres_hip_block_structure* bs, int32_t num_elimin
  * block outside the ordering; *num_groups.  blocks: CERES_HIP_INNER_AUTOMATIC .. CERES_HIP_INNER_POINTS_CAMERAS. */
 int ceres_hip_debug_inner_iteration_ordering(int32_t num_cameras, int32_t num_points, int64_t num_observations, const int32_t* camera_index,
                                              const int32_t* point_index, int32_t blocks, int32_t* group_of_block, int32_t* num_groups);
+
+/* Debug: the subspace dogleg's boundary minimum (DoglegStrategy::FindMinimumOnTrustRegionBoundary and the first-order check of
+ * ComputeSubspaceDoglegStep, I/dogleg_strategy.cc:304-336, 473-515; pure host code).  B[4]: the 2x2 model matrix, row-major; g[2]; the
+ * radius.  x[2] = the minimiser x of 1/2 x'Bx + g'x over the real parts of all four roots of the quartic, UNSCALED (what the strategy
+ * keeps; x * radius / |x| lies on the boundary).  Returns 0, CERES_HIP_DOGLEG_NO_ROOT (no usable root: x = 0) or
+ * CERES_HIP_DOGLEG_COSINE (cos(x, -(Bx + g)) < 0.99; x is still the minimiser) — the two cases that fall back to the traditional step;
+ * CERES_HIP_E_INVALID for NULL pointers. */
+#define CERES_HIP_DOGLEG_NO_ROOT 1
+#define CERES_HIP_DOGLEG_COSINE 2
+int ceres_hip_debug_dogleg_subspace_minimum(const double* B, const double* g, double radius, double* x);
 
 /* DenseCholesky::FactorAndSolve on a caller-supplied matrix (I/dense_cholesky.cc: what DENSE_SCHUR runs on its reduced system,
  * I/schur_complement_solver.cc:163-222): A is n x n row-major with its UPPER triangle authoritative, x = A^-1 b.  The blocked
