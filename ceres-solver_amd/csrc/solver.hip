@@ -26,6 +26,7 @@
 #include <mutex>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "device.h"
@@ -276,12 +277,43 @@ int fail(ceres_hip_solver* s, int code, const char* fmt, ...) {
     if (_rc != 0) return _rc;  \
   } while (0)
 
+// CERES_HIP_DEBUG_POISON=nan|big (a debugging switch, read once per process, off by default): every new floating-point device buffer
+// is filled before first use, so that a kernel reading a value nothing wrote gives a wrong answer every time instead of only when the
+// allocator hands back an earlier handle's memory.  nan: bytes 0xFF (NaN as double and as float); big: bytes 0x43 (about 1.1e16 as a
+// double, finite), for reads whose value is later masked or selected away.  Integer, index, flag and peer-to-peer buffers are never
+// filled: a poisoned index would send a kernel out of bounds.
+int debug_poison_byte() {
+  static const int v = [] {
+    const char* e = getenv("CERES_HIP_DEBUG_POISON");
+    if (!e || !*e) return -1;
+    const int byte = !strcmp(e, "nan") ? 0xFF : !strcmp(e, "big") ? 0x43 : -1;
+    if (byte < 0) fprintf(stderr, "ceres_hip: CERES_HIP_DEBUG_POISON=%s ignored (nan or big)\n", e);
+    else fprintf(stderr, "ceres_hip: CERES_HIP_DEBUG_POISON=%s: new floating-point device buffers are filled\n", e);
+    return byte;
+  }();
+  return v;
+}
+template <typename T>
+constexpr bool kPoisonable = std::is_same<T, double>::value || std::is_same<T, float>::value || std::is_same<T, double2>::value ||
+                             std::is_same<T, float2>::value || std::is_same<T, float4>::value;
+// The fill goes on the handle's stream and is waited for: the buffer's first writer may be a copy on another stream.
+template <typename T>
+hipError_t debug_poison(ceres_hip_solver* s, T* p, size_t n) {
+  if (!kPoisonable<T> || debug_poison_byte() < 0 || !p || n == 0) return hipSuccess;
+  hipError_t e = hipMemsetAsync(p, debug_poison_byte(), n * sizeof(T), s->stream);
+  return e == hipSuccess ? hipStreamSynchronize(s->stream) : e;
+}
+
 template <typename T>
 int dev_alloc(ceres_hip_solver* s, T** p, size_t n) {
   *p = nullptr;
   if (n == 0) n = 1;
   void* q = nullptr;
   HIP_TRY(s, hipMalloc(&q, n * sizeof(T)));
+  if (debug_poison(s, static_cast<T*>(q), n) != hipSuccess) {
+    (void)hipFree(q);
+    return fail(s, CERES_HIP_E_HIP, "CERES_HIP_DEBUG_POISON: filling a new buffer failed");
+  }
   s->allocs.push_back(q);
   s->device_bytes += int64_t(n * sizeof(T));
   *p = static_cast<T*>(q);
@@ -486,7 +518,8 @@ int precond_to_caller_order(ceres_hip_solver* s) {
   const size_t n = size_t(9) * s->plan.n_points;
   double* tmp = nullptr;
   HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(double) * std::max<size_t>(1, n)));
-  hipError_t e = hipMemcpyAsync(tmp, s->precond, sizeof(double) * n, hipMemcpyDeviceToDevice, s->stream);
+  hipError_t e = debug_poison(s, tmp, n);
+  if (e == hipSuccess) e = hipMemcpyAsync(tmp, s->precond, sizeof(double) * n, hipMemcpyDeviceToDevice, s->stream);
   if (e == hipSuccess) e = LaunchScatterBlocks9(tmp, s->precond, s->d_pt_diag_off, s->plan.n_points, s->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
   (void)hipFree(tmp);
@@ -2814,6 +2847,7 @@ int ceres_hip_time_op(ceres_hip_solver* s, int32_t op, int32_t iters, double* av
     case CERES_HIP_TIMED_MODEL_COST:
       if (s->world > 1) return fail(s, CERES_HIP_E_UNSUPPORTED, "model-cost probe on one rank only");
       HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp.p), sizeof(double) * std::max<int64_t>(1, nc)));
+      HIP_TRY(s, debug_poison(s, tmp.p, size_t(nc)));
       HIP_TRY(s, LaunchSet(tmp.p, 1.0, nc, st));
       body = [&] {
         const double* parts = nullptr;
@@ -2825,6 +2859,7 @@ int ceres_hip_time_op(ceres_hip_solver* s, int32_t op, int32_t iters, double* av
       if (s->world > 1) return fail(s, CERES_HIP_E_UNSUPPORTED, "Gram probe on one rank only");
       TRY(require_caller_values(s, "the Gram probe"));
       HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp.p), sizeof(double) * (2 * nc + 5 * kDoglegGrid)));
+      HIP_TRY(s, debug_poison(s, tmp.p, size_t(2 * nc + 5 * kDoglegGrid)));
       HIP_TRY(s, LaunchSet(tmp.p, 1.0, nc, st));
       HIP_TRY(s, LaunchSet(tmp.p + nc, 0.5, nc, st));
       body = [&] {

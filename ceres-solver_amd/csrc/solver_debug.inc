@@ -73,6 +73,9 @@ int ceres_hip_op_dense_cholesky_solve(ceres_hip_solver* s, int32_t n, const doub
     HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&dA0), nn * sizeof(double)));
     HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&dA), nn * sizeof(double)));
     HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&dx), size_t(n) * sizeof(double)));
+    HIP_TRY(s, debug_poison(s, dA0, nn));
+    HIP_TRY(s, debug_poison(s, dA, nn));
+    HIP_TRY(s, debug_poison(s, dx, size_t(n)));
     HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&dflag), sizeof(int)));
     HIP_TRY(s, hipEventCreate(&e0)); HIP_TRY(s, hipEventCreate(&e1));
     HIP_TRY(s, hipMemcpyAsync(dA0, A, nn * sizeof(double), hipMemcpyHostToDevice, st));

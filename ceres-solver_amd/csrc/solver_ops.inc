@@ -68,7 +68,8 @@ int pmv_block_diagonal(ceres_hip_solver* s, int part, double* blocks, int64_t ca
   if (capacity < len) return fail(s, CERES_HIP_E_INVALID, "capacity %lld < %lld", (long long)capacity, (long long)len);
   double* tmp = nullptr;
   HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(double) * std::max<int64_t>(1, len)));
-  hipError_t e = LaunchGenBlockDiagonal(s->G, s->values, part, nullptr, tmp, len, s->stream);
+  hipError_t e = debug_poison(s, tmp, size_t(len));
+  if (e == hipSuccess) e = LaunchGenBlockDiagonal(s->G, s->values, part, nullptr, tmp, len, s->stream);
   int rc = e == hipSuccess ? down(s, blocks, tmp, size_t(len)) : fail(s, CERES_HIP_E_HIP, "block diagonal kernel failed");
   (void)hipFree(tmp);
   return rc;
@@ -117,7 +118,8 @@ int ceres_hip_op_jacobian_gram(ceres_hip_solver* s, const double* a, const doubl
   double* tmp = nullptr;
   HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(double) * (2 * nc + 5 * kDoglegGrid)));
   int np = 0;
-  hipError_t e = hipMemcpyAsync(tmp, a, sizeof(double) * nc, hipMemcpyHostToDevice, s->stream);
+  hipError_t e = debug_poison(s, tmp, 2 * nc + 5 * kDoglegGrid);
+  if (e == hipSuccess) e = hipMemcpyAsync(tmp, a, sizeof(double) * nc, hipMemcpyHostToDevice, s->stream);
   if (e == hipSuccess) e = hipMemcpyAsync(tmp + nc, b, sizeof(double) * nc, hipMemcpyHostToDevice, s->stream);
   if (e == hipSuccess) e = LaunchJacobianGram(s->G, s->values, tmp, tmp + nc, s->have_b ? s->b : nullptr, tmp + 2 * nc, &np, s->stream);
   std::vector<double> h(size_t(5) * kDoglegGrid);
@@ -156,7 +158,8 @@ int ceres_hip_get_ete_inverse(ceres_hip_solver* s, double* blocks, int64_t capac
   if (s->path == CERES_HIP_PATH_BAL) {
     double* tmp = nullptr;
     HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(double) * len));
-    hipError_t e = LaunchExpandSym(s->etei, s->ops->ne, s->ops->etei_pitch, tmp, s->d_pt_eoff, s->plan.n_points, s->stream);  // internal point order -> the caller's E blocks
+    hipError_t e = debug_poison(s, tmp, size_t(len));
+    if (e == hipSuccess) e = LaunchExpandSym(s->etei, s->ops->ne, s->ops->etei_pitch, tmp, s->d_pt_eoff, s->plan.n_points, s->stream);  // internal point order -> the caller's E blocks
     int rc = e == hipSuccess ? down(s, blocks, tmp, size_t(len)) : fail(s, CERES_HIP_E_HIP, "expand failed");
     (void)hipFree(tmp);
     return rc;
@@ -243,9 +246,9 @@ int ceres_hip_get_preconditioner_blocks(ceres_hip_solver* s, int32_t not_inverte
   // re-assemble without inverting, into a temporary
   double* tmp = nullptr;
   HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(double) * std::max<int64_t>(1, len)));
+  int rc = debug_poison(s, tmp, size_t(len)) == hipSuccess ? 0 : fail(s, CERES_HIP_E_HIP, "CERES_HIP_DEBUG_POISON: filling a new buffer failed");
   int type = s->opt.preconditioner_type == CERES_HIP_IDENTITY ? CERES_HIP_JACOBI : s->opt.preconditioner_type;
-  int rc = 0;
-  if (is_schur(s)) rc = op_schur_init(s, true);
+  if (!rc && is_schur(s)) rc = op_schur_init(s, true);
   if (!rc) rc = op_preconditioner(s, type, tmp, false);
   if (!rc) rc = down(s, blocks, tmp, size_t(len));
   (void)hipFree(tmp);
@@ -278,7 +281,8 @@ int ceres_hip_op_schur_eliminate_dense(ceres_hip_solver* s, double* lhs, double*
   const int64_t n = h.num_cols_f;
   double* d_lhs = nullptr;
   HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&d_lhs), sizeof(double) * std::max<int64_t>(1, n * n)));
-  hipError_t e = LaunchGenSchurDense(s->G, s->values, s->etei, s->D, d_lhs, s->stream);
+  hipError_t e = debug_poison(s, d_lhs, size_t(n * n));
+  if (e == hipSuccess) e = LaunchGenSchurDense(s->G, s->values, s->etei, s->D, d_lhs, s->stream);
   int rc = e == hipSuccess ? down(s, lhs, d_lhs, size_t(n * n)) : fail(s, CERES_HIP_E_HIP, "dense Schur kernel failed");
   (void)hipFree(d_lhs);
   if (rc) return rc;

@@ -22,14 +22,8 @@ def fuzz(hip):
 
 @pytest.mark.parametrize("first", [0, 20, 40])
 def test_random_structures_against_the_oracle(fuzz, first):
-    import warnings
+    # Every case must pass on its first run.  (A retry once hid case 17 here: errors of 2e-2, not rounding; tests/test_gpu_schur_state.py
+    # checks that case, on fresh handles after a dirty allocator and with poisoned allocations, against a numpy restatement.)
     for seed in range(first, first + 20):
         r = fuzz.run_case(seed)
-        if not r["ok"]:
-            # One full run of the suite in six (of the round's last) flagged a case here that 280 repeats of the same twenty seeds did not
-            # reproduce (tools/probes/repeat_fuzz_slice.py): the campaign's solves of dozens of iterations differ from one run of the
-            # PRODUCT to the next at the 1e-10 .. 1e-9 level (the order of the LDS additions; tools/fuzz_sequence.py measured it between
-            # two fresh handles), which is the tolerance.  A defect repeats; a tie does not: the case runs again and must pass then.
-            again = fuzz.run_case(seed)
-            assert again["ok"], (r, again)
-            warnings.warn(f"fuzz case {seed} passed only on its second run: {r.get('bad')}")
+        assert r["ok"], (seed, r["bad"], r)
