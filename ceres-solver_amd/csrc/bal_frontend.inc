@@ -14,7 +14,12 @@ struct ceres_hip_bal {
   ceres_hip_solver* s = nullptr;
   std::string err;
   int nc = 0, np = 0;
-  int64_t no = 0, n = 0;
+  int64_t no = 0;
+  // CERES_HIP_CAMERA_* (ceres_hip_bal_create_with_camera): state doubles (cs) and Jacobian columns (cw) per camera; the state is ambient
+  // (n_a = 3 n_p + cs n_c: d_x, d_cand, the caller's state), the step, scale, delta and gradient are tangent (n_t = 3 n_p + cw n_c)
+  int32_t camera_model = CERES_HIP_CAMERA_ANGLE_AXIS;
+  int cs = 9, cw = 9;
+  int64_t n_a = 0, n_t = 0;
   std::vector<int32_t> row_obs;  // residual row block -> observation
   int32_t *d_row_cam = nullptr, *d_row_pt = nullptr;
   double2* d_row_obs = nullptr;
@@ -69,7 +74,7 @@ int bal_evaluate_device(ceres_hip_bal* p, const double* d_state, bool jacobian, 
   A.state = d_state; A.cam_base = 3 * int64_t(p->np); A.scale = d_scale;
   A.residuals = d_residuals; A.values = jacobian ? p->d_vals : nullptr; A.partials = p->d_parts; A.loss = p->loss;
   int nparts = 0;
-  HIP_TRY(s, LaunchBalEvaluate(A, jacobian, &nparts, s->stream));
+  HIP_TRY(s, LaunchBalEvaluate(A, jacobian, &nparts, s->stream, p->camera_model));
   if (defer) { p->deferred_cost_parts = nparts; return 0; }
   HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nparts, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -83,6 +88,8 @@ int bal_evaluate_device(ceres_hip_bal* p, const double* d_state, bool jacobian, 
 // form — caller-layout values, re-laid-out by the gradient's pass — for A/B runs and as the cross-check of the tests)
 bool bal_writes_tiles(const ceres_hip_bal* p) {
   const ceres_hip_solver* s = p->s;
+  // (the tile evaluator computes the angle-axis Jacobian: quaternion cameras keep the two-pass form — the manifold's <2,3,9> included)
+  if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) return false;
   if (const char* e = getenv("CERES_HIP_EVAL_TILES")) if (atoi(e) == 0) return false;
   // (DENSE_SCHUR forms S from the caller-layout values, E cells included: it keeps the two-pass form)
   return s->path == CERES_HIP_PATH_BAL && s->ops && s->ops->ne == 3 && s->ops->nf == 9 && s->ops->ns == 0 && !s->d_Jf && s->d_J && s->world <= 1 &&
@@ -95,6 +102,7 @@ bool bal_writes_tiles(const ceres_hip_bal* p) {
 // The camera-major passes (preconditioner blocks, F^T F) evaluate their F cells from the records the tile-order evaluator leaves — no
 // caller-layout copy of the Jacobian exists then — or read them from p->d_vals (CERES_HIP_EVAL_TILES=2: always; 3: never).
 bool bal_camera_pass_evaluates(const ceres_hip_bal* p) {
+  if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) return false;   // (the evaluating pass is angle-axis)
   if (const char* e = getenv("CERES_HIP_EVAL_TILES")) {
     if (atoi(e) == 2) return false;
     if (atoi(e) == 3) return p->d_cm_obs != nullptr;   // (tests: the evaluating kernel whatever the item length)
@@ -143,12 +151,16 @@ int bal_evaluate_into_tiles(ceres_hip_bal* p, const double* d_state, const doubl
 
 constexpr int kBalSecondParts = 2048;   // d_parts / h_parts: an evaluation's cost partials in [0, 2048), a second kernel's from here on
 
-// max |g_i / scale_i|; deferred_cost != nullptr: also the cost of the evaluation enqueued before (bal_evaluate_*(…, defer = true))
-int bal_gradient_max(ceres_hip_bal* p, const double* d_scale, double* out, double* deferred_cost = nullptr) {
+// max |g_i / scale_i| — with quaternion-manifold cameras |x - Plus(x, -g)|_inf at the state d_x; deferred_cost != nullptr: also the cost of
+// the evaluation enqueued before (bal_evaluate_*(…, defer = true))
+int bal_gradient_max(ceres_hip_bal* p, const double* d_scale, const double* d_x, double* out, double* deferred_cost = nullptr) {
   ceres_hip_solver* s = p->s;
   int nparts = 0;
   static_assert(kMaxVecGrid <= kBalParts - kBalSecondParts, "room for the second kernel's partials");
-  HIP_TRY(s, LaunchBalGradientMax(p->d_grad, d_scale, p->n, p->d_parts + kBalSecondParts, &nparts, s->stream));
+  if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD)
+    HIP_TRY(s, LaunchBalGradientMaxQuat(p->d_grad, d_scale, d_x, p->np, p->nc, p->d_parts + kBalSecondParts, &nparts, s->stream));
+  else
+    HIP_TRY(s, LaunchBalGradientMax(p->d_grad, d_scale, p->n_t, p->d_parts + kBalSecondParts, &nparts, s->stream));
   const int nc = deferred_cost ? p->deferred_cost_parts : 0;
   if (nc > 0) HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nc, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipMemcpyAsync(p->h_parts + kBalSecondParts, p->d_parts + kBalSecondParts, sizeof(double) * nparts, hipMemcpyDeviceToHost, s->stream));
@@ -162,6 +174,16 @@ int bal_gradient_max(ceres_hip_bal* p, const double* d_scale, double* out, doubl
     *deferred_cost = c;
     p->deferred_cost_parts = 0;
   }
+  return 0;
+}
+
+// delta = step .* scale, cand = Plus(x, delta); |x|^2 partials at parts[0 ..), |delta|^2 at parts[*nparts ..)
+int bal_candidate(ceres_hip_bal* p, const double* x, const double* scale, double* cand, double* parts, int* nparts) {
+  ceres_hip_solver* s = p->s;
+  if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD)
+    HIP_TRY(s, LaunchBalCandidateQuat(x, p->d_step, scale, p->d_delta, cand, p->np, p->nc, parts, nparts, s->stream));
+  else   // (the angle-axis and the Euclidean quaternion camera: Plus is x + delta)
+    HIP_TRY(s, LaunchBalCandidate(x, p->d_step, scale, p->d_delta, cand, p->n_a, parts, nparts, s->stream));
   return 0;
 }
 
@@ -205,21 +227,37 @@ void ceres_hip_bal_destroy(ceres_hip_bal* p) {
   delete p;
 }
 
-ceres_hip_bal* ceres_hip_bal_create(const ceres_hip_options* options, int32_t num_cameras, int32_t num_points,
-                                    int64_t num_observations, const int32_t* camera_index, const int32_t* point_index,
-                                    const double* observations) try {   // (host vectors sized by the caller's counts: no C++ exception crosses the C boundary)
-  if (!options || num_cameras <= 0 || num_points <= 0 || num_observations <= 0 || !camera_index || !point_index ||
-      !observations) {
-    g_create_error = "ceres_hip_bal_create: bad arguments";
+}  // extern "C"
+
+namespace {
+
+// ceres_hip_bal_create and ceres_hip_bal_create_with_camera (`fn` names the entry point in the messages)
+ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras, int32_t num_points,
+                          int64_t num_observations, const int32_t* camera_index, const int32_t* point_index,
+                          const double* observations) try {   // (host vectors sized by the caller's counts: no C++ exception crosses the C boundary)
+  const std::string name(fn);
+  static_assert(kCamAngleAxis == CERES_HIP_CAMERA_ANGLE_AXIS && kCamQuaternion == CERES_HIP_CAMERA_QUATERNION &&
+                kCamQuaternionManifold == CERES_HIP_CAMERA_QUATERNION_MANIFOLD, "device camera models are the ABI's");
+  if (camera_model < CERES_HIP_CAMERA_ANGLE_AXIS || camera_model > CERES_HIP_CAMERA_QUATERNION_MANIFOLD) {
+    g_create_error = name + ": unknown camera_model " + std::to_string(camera_model);
     return nullptr;
   }
-  if (num_observations * 24 > int64_t(INT32_MAX)) {  // cell.position is an int in the reference too (I/block_structure.h:64)
-    g_create_error = "ceres_hip_bal_create: more than 89 M observations do not fit 32-bit value positions";
+  if (!options || num_cameras <= 0 || num_points <= 0 || num_observations <= 0 || !camera_index || !point_index ||
+      !observations) {
+    g_create_error = name + ": bad arguments";
+    return nullptr;
+  }
+  const int cs = camera_model == CERES_HIP_CAMERA_ANGLE_AXIS ? 9 : 10;       // state doubles per camera
+  const int cw = camera_model == CERES_HIP_CAMERA_QUATERNION ? 10 : 9;       // Jacobian columns per camera (tangent)
+  const int64_t per_obs = 6 + 2 * cw;                                        // Jacobian values per observation: 24, 26 or 24
+  if (num_observations * per_obs > int64_t(INT32_MAX)) {  // cell.position is an int in the reference too (I/block_structure.h:64)
+    g_create_error = name + ": more than " + std::to_string(int64_t(INT32_MAX) / per_obs / 1000000) +
+                     " M observations do not fit 32-bit value positions";
     return nullptr;
   }
   for (int64_t i = 0; i < num_observations; ++i) {
     if (camera_index[i] < 0 || camera_index[i] >= num_cameras || point_index[i] < 0 || point_index[i] >= num_points) {
-      g_create_error = "ceres_hip_bal_create: observation index out of range";
+      g_create_error = name + ": observation index out of range";
       return nullptr;
     }
   }
@@ -230,7 +268,9 @@ ceres_hip_bal* ceres_hip_bal_create(const ceres_hip_options* options, int32_t nu
   ceres_hip_bal* p = new ceres_hip_bal;
   p->s = s;
   p->nc = num_cameras; p->np = num_points; p->no = num_observations;
-  p->n = 3 * int64_t(num_points) + 9 * int64_t(num_cameras);
+  p->camera_model = camera_model; p->cs = cs; p->cw = cw;
+  p->n_a = 3 * int64_t(num_points) + cs * int64_t(num_cameras);
+  p->n_t = 3 * int64_t(num_points) + cw * int64_t(num_cameras);
   auto bail = [&](const char* what) -> ceres_hip_bal* {
     g_create_error = std::string(what) + ": " + s->err;
     ceres_hip_bal_destroy(p);
@@ -245,7 +285,7 @@ ceres_hip_bal* ceres_hip_bal_create(const ceres_hip_options* options, int32_t nu
   std::vector<int32_t> rsz(no, 2), rpos(no), csz(ncb), cpos(ncb), rptr(no + 1), ccol(2 * no), cval(2 * no), rcam(no), rpt(no);
   std::vector<double> robs(2 * no);
   for (int q = 0; q < num_points; ++q) { csz[q] = 3; cpos[q] = 3 * q; }
-  for (int c = 0; c < num_cameras; ++c) { csz[num_points + c] = 9; cpos[num_points + c] = 3 * num_points + 9 * c; }
+  for (int c = 0; c < num_cameras; ++c) { csz[num_points + c] = cw; cpos[num_points + c] = 3 * num_points + cw * c; }
   for (int64_t r = 0; r < no; ++r) {
     const int ob = p->row_obs[r];
     rpos[r] = int32_t(2 * r);
@@ -253,23 +293,24 @@ ceres_hip_bal* ceres_hip_bal_create(const ceres_hip_options* options, int32_t nu
     rcam[r] = camera_index[ob]; rpt[r] = point_index[ob];
     robs[2 * r] = observations[2 * int64_t(ob)]; robs[2 * r + 1] = observations[2 * int64_t(ob) + 1];
     ccol[2 * r] = rpt[r];                    cval[2 * r] = int32_t(6 * r);                 // E cell
-    ccol[2 * r + 1] = num_points + rcam[r];  cval[2 * r + 1] = int32_t(6 * no + 18 * r);  // F cell
+    ccol[2 * r + 1] = num_points + rcam[r];  cval[2 * r + 1] = int32_t(6 * no + 2 * cw * r);  // F cell
   }
   rptr[no] = int32_t(2 * no);
   ceres_hip_block_structure flat{int32_t(no), ncb, rsz.data(), rpos.data(), csz.data(), cpos.data(), rptr.data(), ccol.data(),
                                  cval.data()};
-  if (ceres_hip_set_structure(s, &flat) != CERES_HIP_OK) return bail("ceres_hip_bal_create: set_structure");
-  if (hipSetDevice(s->opt.device) != hipSuccess) return bail("ceres_hip_bal_create: hipSetDevice");
+  if (ceres_hip_set_structure(s, &flat) != CERES_HIP_OK) return bail((name + ": set_structure").c_str());
+  if (hipSetDevice(s->opt.device) != hipSuccess) return bail((name + ": hipSetDevice").c_str());
   bool ok = dev_upload(s, &p->d_row_cam, rcam) == 0 && dev_upload(s, &p->d_row_pt, rpt) == 0;
   double* obs_dev = nullptr;
   ok = ok && dev_upload(s, &obs_dev, robs) == 0;
   p->d_row_obs = reinterpret_cast<double2*>(obs_dev);
-  ok = ok && dev_alloc(s, &p->d_x, size_t(p->n)) == 0 && dev_alloc(s, &p->d_cand, size_t(p->n)) == 0 &&
-       dev_alloc(s, &p->d_step, size_t(p->n)) == 0 && dev_alloc(s, &p->d_delta, size_t(p->n)) == 0 &&
-       dev_alloc(s, &p->d_scale, size_t(p->n)) == 0 && dev_alloc(s, &p->d_grad, size_t(p->n)) == 0 &&
-       dev_alloc(s, &p->d_res, size_t(2 * no)) == 0 && dev_alloc(s, &p->d_vals, size_t(24 * no)) == 0 &&
+  ok = ok && dev_alloc(s, &p->d_x, size_t(p->n_a)) == 0 && dev_alloc(s, &p->d_cand, size_t(p->n_a)) == 0 &&
+       dev_alloc(s, &p->d_step, size_t(p->n_t)) == 0 && dev_alloc(s, &p->d_delta, size_t(p->n_t)) == 0 &&
+       dev_alloc(s, &p->d_scale, size_t(p->n_t)) == 0 && dev_alloc(s, &p->d_grad, size_t(p->n_t)) == 0 &&
+       dev_alloc(s, &p->d_res, size_t(2 * no)) == 0 && dev_alloc(s, &p->d_vals, size_t(per_obs * no)) == 0 &&
        dev_alloc(s, &p->d_parts, size_t(kBalParts)) == 0;
-  if (ok && s->path == CERES_HIP_PATH_BAL && !s->plan.slot_bpos.empty()) {   // the rows' camera / point / pixel in slot order
+  // the rows' camera / point / pixel in slot order: the tile evaluator's and the evaluating camera-major pass's records (angle-axis only)
+  if (ok && s->path == CERES_HIP_PATH_BAL && !s->plan.slot_bpos.empty() && camera_model == CERES_HIP_CAMERA_ANGLE_AXIS) {
     const size_t ns = s->plan.slot_bpos.size();
     std::vector<int32_t> scam(ns, 0), spt(ns, 0);
     std::vector<double> sobs(2 * ns, 0.0);
@@ -295,20 +336,44 @@ ceres_hip_bal* ceres_hip_bal_create(const ceres_hip_options* options, int32_t nu
       p->d_cm_obs = reinterpret_cast<double2*>(co);
     }
   }
-  if (!ok) return bail("ceres_hip_bal_create: device allocation");
+  if (!ok) return bail((name + ": device allocation").c_str());
   if (hipHostMalloc(reinterpret_cast<void**>(&p->h_parts), sizeof(double) * kBalParts) != hipSuccess)
-    return bail("ceres_hip_bal_create: pinned allocation");
+    return bail((name + ": pinned allocation").c_str());
   return p;
 } catch (const std::exception& ex) {
-  g_create_error = std::string("ceres_hip_bal_create: ") + ex.what();
+  g_create_error = std::string(fn) + ": " + ex.what();
   return nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+ceres_hip_bal* ceres_hip_bal_create(const ceres_hip_options* options, int32_t num_cameras, int32_t num_points,
+                                    int64_t num_observations, const int32_t* camera_index, const int32_t* point_index,
+                                    const double* observations) {
+  return bal_create("ceres_hip_bal_create", options, CERES_HIP_CAMERA_ANGLE_AXIS, num_cameras, num_points, num_observations, camera_index,
+                    point_index, observations);
+}
+
+ceres_hip_bal* ceres_hip_bal_create_with_camera(const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras,
+                                                int32_t num_points, int64_t num_observations, const int32_t* camera_index,
+                                                const int32_t* point_index, const double* observations) {
+  return bal_create("ceres_hip_bal_create_with_camera", options, camera_model, num_cameras, num_points, num_observations, camera_index,
+                    point_index, observations);
 }
 
 int ceres_hip_bal_sizes(const ceres_hip_bal* p, int64_t* num_parameters, int64_t* num_residuals, int64_t* num_jacobian_values) {
   if (!p) return CERES_HIP_E_INVALID;
-  if (num_parameters) *num_parameters = p->n;
+  if (num_parameters) *num_parameters = p->n_a;
   if (num_residuals) *num_residuals = 2 * p->no;
-  if (num_jacobian_values) *num_jacobian_values = 24 * p->no;
+  if (num_jacobian_values) *num_jacobian_values = (6 + 2 * p->cw) * p->no;
+  return 0;
+}
+
+int ceres_hip_bal_num_effective_parameters(const ceres_hip_bal* p, int64_t* num_effective_parameters) {
+  if (!p || !num_effective_parameters) return CERES_HIP_E_INVALID;
+  *num_effective_parameters = p->n_t;
   return 0;
 }
 
@@ -358,17 +423,17 @@ int ceres_hip_bal_evaluate(ceres_hip_bal* p, const double* state, double* cost, 
   if (!p || !state || !cost) return CERES_HIP_E_INVALID;
   ceres_hip_solver* s = p->s;
   HIP_TRY(s, hipSetDevice(s->opt.device));
-  BAL_TRY(p, up(s, p->d_x, state, size_t(p->n)));
+  BAL_TRY(p, up(s, p->d_x, state, size_t(p->n_a)));
   const bool jac = gradient != nullptr || jacobian_values != nullptr;
   BAL_TRY(p, bal_evaluate_device(p, p->d_x, jac, nullptr, p->d_res, cost));
   if (residuals) BAL_TRY(p, down(s, residuals, p->d_res, size_t(2 * p->no)));
   if (jac) {
     bal_set_camera_eval(p, false);
     BAL_TRY(p, load_device(s, p->d_vals, p->d_res, nullptr));
-    if (jacobian_values) BAL_TRY(p, down(s, jacobian_values, p->d_vals, size_t(24 * p->no)));
+    if (jacobian_values) BAL_TRY(p, down(s, jacobian_values, p->d_vals, size_t((6 + 2 * p->cw) * p->no)));
     if (gradient) {
       BAL_TRY(p, op_jtb(s, p->d_grad));
-      BAL_TRY(p, down(s, gradient, p->d_grad, size_t(p->n)));
+      BAL_TRY(p, down(s, gradient, p->d_grad, size_t(p->n_t)));
     }
   }
   return 0;
@@ -379,9 +444,13 @@ int ceres_hip_bal_evaluate(ceres_hip_bal* p, const double* state, double* cost, 
 int ceres_hip_debug_bal_evaluate_tiles_timing(ceres_hip_bal* p, const double* state, int32_t flags, int32_t iters, double* avg_us) {
   if (!p || !state || !avg_us || iters <= 0) return CERES_HIP_E_INVALID;
   ceres_hip_solver* s = p->s;
+  if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) {
+    p->err = "ceres_hip_debug_bal_evaluate_tiles_timing: the tile evaluator is angle-axis only";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
   HIP_TRY(s, hipSetDevice(s->opt.device));
   if (!bal_writes_tiles(p)) return fail(s, CERES_HIP_E_UNSUPPORTED, "the evaluator does not write this structure's tiles");
-  BAL_TRY(p, up(s, p->d_x, state, size_t(p->n)));
+  BAL_TRY(p, up(s, p->d_x, state, size_t(p->n_a)));
   double cost = 0;
   hipEvent_t e0, e1;
   HIP_TRY(s, hipEventCreate(&e0));
@@ -419,7 +488,11 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
   HIP_TRY(s, hipSetDevice(s->opt.device));
   const auto t_start = std::chrono::steady_clock::now();
   memset(S, 0, sizeof(*S));
-  const int64_t n = p->n;
+  if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS && s->world > 1) {
+    p->err = "ceres_hip_bal_minimize: quaternion cameras are not supported on sharded handles";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
+  const int64_t n = p->n_a;
   BAL_TRY(p, up(s, p->d_x, state, size_t(n)));
   double* x = p->d_x;
   double* cand = p->d_cand;
@@ -470,11 +543,11 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
     if (o->jacobi_scaling && iteration == 0) {  // scale = 1 / (1 + sqrt(SquaredColumnNorm(J))) of the first Jacobian
       TRY(eval_values(nullptr, true));
       TRY(op_squared_column_norm(s, p->d_grad));
-      HIP_TRY(s, LaunchBalJacobiScale(p->d_grad, p->d_scale, n, st));
+      HIP_TRY(s, LaunchBalJacobiScale(p->d_grad, p->d_scale, p->n_t, st));
     }
     TRY(eval_values(scale));
     TRY(op_jtb(s, p->d_grad));
-    TRY(bal_gradient_max(p, scale, &grad_max, &x_cost));
+    TRY(bal_gradient_max(p, scale, x, &grad_max, &x_cost));
     S->evaluation_seconds += seconds_since(t0);
     return 0;
   };
@@ -554,7 +627,7 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
     {
       const auto te = std::chrono::steady_clock::now();
       static_assert(2 * kMaxVecGrid <= kBalParts - kBalSecondParts, "room for |x|^2 and |delta|^2 partials");
-      HIP_TRY(s, LaunchBalCandidate(x, p->d_step, scale, p->d_delta, cand, n, p->d_parts + kBalSecondParts, &nparts, st));
+      BAL_TRY(p, bal_candidate(p, x, scale, cand, p->d_parts + kBalSecondParts, &nparts));
       if (inner_set) HIP_TRY(s, LaunchBalDiffNorm(x, cand, n, p->d_parts + kDiffParts, &ndiff, st));
       BAL_TRY(p, bal_evaluate_device(p, cand, false, nullptr, nullptr, &cand_cost, true));
       const int nc = p->deferred_cost_parts;
@@ -592,7 +665,7 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
         inner_enabled = 1.0 - inner_cost / cand_cost > p->inner_tolerance;
         cand_cost = inner_cost;
       } else {   // (the evaluation failed: Ceres keeps the candidate as it was — rebuilt here from x and the step)
-        HIP_TRY(s, LaunchBalCandidate(x, p->d_step, scale, p->d_delta, cand, n, p->d_parts + kBalSecondParts, &nparts, st));
+        BAL_TRY(p, bal_candidate(p, x, scale, cand, p->d_parts + kBalSecondParts, &nparts));
       }
       p->inner_seconds += seconds_since(ti);
     }

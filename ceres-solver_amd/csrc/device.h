@@ -556,7 +556,14 @@ struct BalEvalArgs {
   double* partials = nullptr;         // cost partial per workgroup (<= 2048)
   LossParams loss;                    // cost = sum rho / 2, corrected residuals and Jacobian (kLossNone: the squared loss)
 };
-hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, hipStream_t stream);
+// Camera models of the BAL front end (CERES_HIP_CAMERA_* of include/ceres_hip.h): state doubles / Jacobian columns per camera 9 / 9,
+// 10 / 10 and 10 / 9.  The quaternion cameras are [q_w q_x q_y q_z | t(3) | f k1 k2] (snavely.h, snavely_quat).
+enum : int { kCamAngleAxis = 0, kCamQuaternion = 1, kCamQuaternionManifold = 2 };
+// camera_model != kCamAngleAxis: 10 state doubles per camera, F cells of 2 x 10 (kCamQuaternion) or 2 x 9 (the manifold's tangent) at
+// 6 n_rows + 2 width r; A.scale then indexes the tangent vector
+hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, hipStream_t stream, int camera_model = kCamAngleAxis);
+// the quaternion cameras' instantiations of the same kernel on `grid` workgroups (kernels_quaternion.hip; LaunchBalEvaluate calls it)
+hipError_t LaunchBalEvaluateQuat(const BalEvalArgs& A, bool jacobian, int grid, hipStream_t stream, int camera_model);
 // The same in TILE order for the <2,3,9> fused path: the Jacobian lands in the solver's tiles (J_out, b_out: BalArgs' layout), the F
 // cells also at slot_fpos of e.values (nullptr: not), the residuals in e.residuals; e.values' E cells are NOT written.
 struct BalEvalTilesArgs {
@@ -578,6 +585,13 @@ hipError_t LaunchBalEvaluateTiles(const BalEvalTilesArgs& T, int64_t n_points, i
 // delta = step .* scale, cand = x + delta; partials[0..g) = |x|^2, [g..2g) = |delta|^2 partial sums
 hipError_t LaunchBalCandidate(const double* x, const double* step, const double* scale, double* delta, double* cand, int64_t n,
                               double* partials, int* nparts, hipStream_t stream);
+// kCamQuaternionManifold: delta = step .* scale (tangent, 3 n_p + 9 n_c), cand = Plus(x, delta) (ambient, 3 n_p + 10 n_c); the same
+// partials (|x|^2 ambient, |delta|^2 tangent)
+hipError_t LaunchBalCandidateQuat(const double* x, const double* step, const double* scale, double* delta, double* cand, int64_t n_points,
+                                  int64_t n_cameras, double* partials, int* nparts, hipStream_t stream);
+// kCamQuaternionManifold: partial maxima of |x - Plus(x, -g)| (ambient), g = gradient / scale (tangent)
+hipError_t LaunchBalGradientMaxQuat(const double* g, const double* scale, const double* x, int64_t n_points, int64_t n_cameras,
+                                    double* partials, int* nparts, hipStream_t stream);
 // partial maxima of |g_i / scale_i|
 hipError_t LaunchBalGradientMax(const double* g, const double* scale, int64_t n, double* partials, int* nparts, hipStream_t stream);
 hipError_t LaunchBalJacobiScale(const double* colnorm2, double* scale, int64_t n, hipStream_t stream);

@@ -246,7 +246,7 @@ int dogleg_step(ceres_hip_bal* p, DoglegState& st, const ceres_hip_minimizer_opt
     // the strategy's vectors and the pass over J; s->lm_diag holds the clamped column norms lm_step_loaded formed
     int n3 = 0, n5 = 0;
     double* parts = p->d_dl_parts;
-    HIP_TRY(s, LaunchDoglegPrep(s->lm_diag, p->d_grad, p->d_dl_b, p->d_dl_a, p->n, parts, &n3, stream));
+    HIP_TRY(s, LaunchDoglegPrep(s->lm_diag, p->d_grad, p->d_dl_b, p->d_dl_a, p->n_t, parts, &n3, stream));
     HIP_TRY(s, LaunchJacobianGram(s->G, s->values, p->d_dl_a, p->d_dl_b, s->b, parts + 3 * kDoglegGrid, &n5, stream));
     HIP_TRY(s, hipMemcpyAsync(p->h_parts, parts, sizeof(double) * 3 * n3, hipMemcpyDeviceToHost, stream));
     HIP_TRY(s, hipMemcpyAsync(p->h_parts + 3 * kDoglegGrid, parts + 3 * kDoglegGrid, sizeof(double) * 5 * n5, hipMemcpyDeviceToHost, stream));
@@ -267,7 +267,7 @@ int dogleg_step(ceres_hip_bal* p, DoglegState& st, const ceres_hip_minimizer_opt
   double u = 0, v = 0;
   if (st.type == CERES_HIP_SUBSPACE_DOGLEG) dl_subspace(st, &u, &v);
   else dl_traditional(st, &u, &v);
-  HIP_TRY(s, LaunchAxpby(u, p->d_dl_a, v, p->d_dl_b, d_step, p->n, stream));
+  HIP_TRY(s, LaunchAxpby(u, p->d_dl_a, v, p->d_dl_b, d_step, p->n_t, stream));
   lr->model_cost_change = -(u * st.jaf + v * st.jbf) - 0.5 * (u * u * st.jaa + 2.0 * u * v * st.jab + v * v * st.jbb);
   lr->step_is_finite = 1;
   return 0;
@@ -277,7 +277,7 @@ int dogleg_step(ceres_hip_bal* p, DoglegState& st, const ceres_hip_minimizer_opt
 int dogleg_alloc(ceres_hip_bal* p) {
   if (p->d_dl_a) return 0;
   ceres_hip_solver* s = p->s;
-  if (dev_alloc(s, &p->d_dl_a, size_t(p->n)) || dev_alloc(s, &p->d_dl_b, size_t(p->n)) || dev_alloc(s, &p->d_dl_parts, size_t(8) * kDoglegGrid)) {
+  if (dev_alloc(s, &p->d_dl_a, size_t(p->n_t)) || dev_alloc(s, &p->d_dl_b, size_t(p->n_t)) || dev_alloc(s, &p->d_dl_parts, size_t(8) * kDoglegGrid)) {
     p->d_dl_a = nullptr;
     return CERES_HIP_E_HIP;
   }

@@ -258,6 +258,10 @@ int ceres_hip_bal_set_inner_iterations(ceres_hip_bal* p, int32_t blocks, double 
   if (!p) return invalid("NULL problem handle");
   if (blocks < CERES_HIP_INNER_NONE || blocks > CERES_HIP_INNER_POINTS_CAMERAS) return invalid("unknown blocks " + std::to_string(blocks));
   if (!std::isfinite(tolerance) || tolerance < 0.0) return invalid("tolerance must be finite and >= 0");   // (solver.cc:423-424)
+  if (blocks != CERES_HIP_INNER_NONE && p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) {   // (kernels_inner.hip: angle-axis blocks)
+    p->err = "ceres_hip_bal_set_inner_iterations: inner iterations are not supported with quaternion cameras";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
   p->inner_blocks = blocks;
   p->inner_tolerance = tolerance;
   return 0;
@@ -271,14 +275,15 @@ int ceres_hip_bal_inner_iterate(ceres_hip_bal* p, double* state, double* cost_be
     return code;
   };
   if (!state || !cost_before || !cost_after) return refuse(CERES_HIP_E_INVALID, "NULL state or cost");
+  if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported with quaternion cameras");
   if (p->inner_blocks == CERES_HIP_INNER_NONE) return refuse(CERES_HIP_E_INVALID, "no inner iterations set (ceres_hip_bal_set_inner_iterations)");
   if (s->world > 1) return refuse(CERES_HIP_E_UNSUPPORTED, "not on sharded handles");
   HIP_TRY(s, hipSetDevice(s->opt.device));
-  BAL_TRY(p, up(s, p->d_cand, state, static_cast<size_t>(p->n)));
+  BAL_TRY(p, up(s, p->d_cand, state, static_cast<size_t>(p->n_a)));
   BAL_TRY(p, bal_evaluate_device(p, p->d_cand, false, nullptr, nullptr, cost_before));
   BAL_TRY(p, bal_inner_pass(p, p->d_cand));
   BAL_TRY(p, bal_evaluate_device(p, p->d_cand, false, nullptr, nullptr, cost_after));
-  BAL_TRY(p, down(s, state, p->d_cand, static_cast<size_t>(p->n)));
+  BAL_TRY(p, down(s, state, p->d_cand, static_cast<size_t>(p->n_a)));
   if (block_iterations) {
     const BalInner& I = *p->inner;
     const size_t nb = static_cast<size_t>(p->np) + p->nc;

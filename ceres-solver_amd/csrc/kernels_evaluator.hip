@@ -15,6 +15,7 @@
 
 #include "device.h"
 #include "robust_loss.h"
+#include "bal_evaluate.h"
 #include "snavely.h"
 
 namespace chip {
@@ -30,63 +31,6 @@ __device__ __forceinline__ double wave_max_e(double v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
   return v;
-}
-
-// ROBUST: A.loss applies (robust_loss.h) — cost rho / 2, the Jacobian corrected with the uncorrected residual, then the residual; the
-// Jacobi column scaling comes after the correction.  !ROBUST: the squared loss, as this kernel was before losses existed.
-template <bool JAC, bool ROBUST>
-__global__ __launch_bounds__(kVecBlock) void bal_evaluate_kernel(BalEvalArgs A) {
-  __shared__ double sh[4];
-  double cost = 0.0;
-  for (int64_t r = int64_t(blockIdx.x) * kVecBlock + threadIdx.x; r < A.n_rows; r += int64_t(gridDim.x) * kVecBlock) {
-    const int c = A.row_cam[r], p = A.row_pt[r];
-    const double2 o = A.row_obs[r];
-    double cam[9], X[3], res[2], jc[18], jp[6];
-    const double* cs = A.state + A.cam_base + 9 * int64_t(c);
-    const double* ps = A.state + 3 * int64_t(p);
-#pragma unroll
-    for (int i = 0; i < 9; ++i) cam[i] = cs[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) X[i] = ps[i];
-    snavely<JAC>(cam, X, o.x, o.y, res, jc, jp);
-    if constexpr (ROBUST) {
-      const double sq = res[0] * res[0] + res[1] * res[1];
-      double rho[3];
-      robust_rho(A.loss, sq, rho);
-      cost += 0.5 * rho[0];
-      if (JAC || A.residuals) {   // (cost only: no Corrector, I/residual_block.cc:175-178)
-        const RobustCorrector C = robust_corrector(sq, rho);
-        if constexpr (JAC) {
-          robust_correct_jacobian<9>(C, res[0], res[1], jc);
-          robust_correct_jacobian<3>(C, res[0], res[1], jp);
-        }
-        res[0] *= C.residual_scaling; res[1] *= C.residual_scaling;
-      }
-    } else {
-      cost += 0.5 * (res[0] * res[0] + res[1] * res[1]);
-    }
-    if (A.residuals) reinterpret_cast<double2*>(A.residuals)[r] = make_double2(res[0], res[1]);
-    if constexpr (JAC) {
-      if (A.scale) {
-        const double* sc = A.scale + A.cam_base + 9 * int64_t(c);
-        const double* sp = A.scale + 3 * int64_t(p);
-#pragma unroll
-        for (int j = 0; j < 9; ++j) { const double v = sc[j]; jc[j] *= v; jc[9 + j] *= v; }
-#pragma unroll
-        for (int j = 0; j < 3; ++j) { const double v = sp[j]; jp[j] *= v; jp[3 + j] *= v; }
-      }
-      double2* e = reinterpret_cast<double2*>(A.values + 6 * r);                // 48 B per row, 16-byte aligned
-      double2* fo = reinterpret_cast<double2*>(A.values + 6 * A.n_rows + 18 * r);  // 144 B per row
-#pragma unroll
-      for (int j = 0; j < 3; ++j) e[j] = make_double2(jp[2 * j], jp[2 * j + 1]);
-#pragma unroll
-      for (int j = 0; j < 9; ++j) fo[j] = make_double2(jc[2 * j], jc[2 * j + 1]);
-    }
-  }
-  cost = wave_sum_e(cost);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = cost;
-  __syncthreads();
-  if (threadIdx.x == 0) A.partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
 // The same evaluation in TILE order (round 4): one wavefront per tile of 64 observation slots, the Jacobian goes straight
@@ -298,11 +242,12 @@ int grid_for(int64_t n) {
 
 }  // namespace
 
-hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, hipStream_t stream) {
+hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, hipStream_t stream, int camera_model) {
   // one observation per thread and several per thread at scale: 2048 workgroups keep 256 CUs busy
   int64_t g = (A.n_rows + kVecBlock - 1) / kVecBlock;
   const int grid = int(g < 1 ? 1 : (g > 2048 ? 2048 : g));
   *nparts = grid;
+  if (camera_model != kCamAngleAxis) return LaunchBalEvaluateQuat(A, jacobian, grid, stream, camera_model);   // (kernels_quaternion.hip)
   if (A.loss.type == kLossNone) {
     if (jacobian) hipLaunchKernelGGL((bal_evaluate_kernel<true, false>), dim3(grid), dim3(kVecBlock), 0, stream, A);
     else hipLaunchKernelGGL((bal_evaluate_kernel<false, false>), dim3(grid), dim3(kVecBlock), 0, stream, A);

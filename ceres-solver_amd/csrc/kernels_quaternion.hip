@@ -1,0 +1,164 @@
+// The trust-region loop's vector kernels for quaternion-manifold cameras (ceres_hip_bal_create_with_camera,
+// CERES_HIP_CAMERA_QUATERNION_MANIFOLD): the state is ambient — [3 per point | q(4) t(3) f k1 k2 per camera] — and the step, the scale and
+// the gradient are tangent — 9 per camera — so that Plus and the gradient's max norm are no longer element-wise (bal_candidate_kernel and
+// bal_gradient_max_kernel of kernels_evaluator.hip serve the other two camera models).  A translation unit of its own: the sin / cos
+// of QuaternionPlus next to the evaluator's kernels changed the register allocation of its robust tile-order instantiations.
+#include <hip/hip_runtime.h>
+
+#include "bal_evaluate.h"
+#include "device.h"
+
+namespace chip {
+
+namespace {
+
+__device__ __forceinline__ double wave_sum_q(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+  return v;
+}
+__device__ __forceinline__ double wave_max_q(double v) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
+  return v;
+}
+
+// QuaternionPlusImpl (I/manifold.cc): [cos |d|, sin |d| / |d| d] (x) q, the product of include/ceres/rotation.h's QuaternionProduct;
+// q itself when |d| is exactly zero
+__device__ __forceinline__ void quaternion_plus(const double (&q)[4], double d0, double d1, double d2, double (&out)[4]) {
+  const double nd = norm3d(d0, d1, d2);
+  if (nd == 0.0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[k] = q[k];
+    return;
+  }
+  const double s = sin(nd) / nd;
+  const double z[4] = {cos(nd), s * d0, s * d1, s * d2};
+  out[0] = z[0] * q[0] - z[1] * q[1] - z[2] * q[2] - z[3] * q[3];
+  out[1] = z[0] * q[1] + z[1] * q[0] + z[2] * q[3] - z[3] * q[2];
+  out[2] = z[0] * q[2] - z[1] * q[3] + z[2] * q[0] + z[3] * q[1];
+  out[3] = z[0] * q[3] + z[1] * q[2] - z[2] * q[1] + z[3] * q[0];
+}
+
+// bal_candidate_kernel for quaternion-manifold cameras: delta = step .* scale (tangent: 9 per camera), candidate = Plus(x, delta)
+// (ambient: 10 per camera, QuaternionManifold on q, Euclidean on the rest).  One item per point coordinate, then one per camera: each
+// thread's sums run in a fixed order, so the partials — |x|^2 (ambient) at [b], |delta|^2 (tangent) at [grid + b] — are repeatable.
+__global__ __launch_bounds__(kVecBlock) void bal_candidate_quat_kernel(const double* x, const double* step, const double* scale,
+                                                                       double* delta, double* cand, int64_t n_points, int64_t n_cameras,
+                                                                       double* partials) {
+  __shared__ double sh[8];
+  double xn = 0, dn = 0;
+  const int64_t n_pt = 3 * n_points;
+  for (int64_t i = int64_t(blockIdx.x) * kVecBlock + threadIdx.x; i < n_pt + n_cameras; i += int64_t(gridDim.x) * kVecBlock) {
+    if (i < n_pt) {
+      const double d = scale ? step[i] * scale[i] : step[i];
+      const double xi = x[i];
+      delta[i] = d;
+      cand[i] = xi + d;
+      xn += xi * xi;
+      dn += d * d;
+      continue;
+    }
+    const int64_t t = n_pt + 9 * (i - n_pt), a = n_pt + 10 * (i - n_pt);
+    double d[9], q[4], qp[4];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) {
+      d[j] = scale ? step[t + j] * scale[t + j] : step[t + j];
+      delta[t + j] = d[j];
+      dn += d[j] * d[j];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { q[k] = x[a + k]; xn += q[k] * q[k]; }
+    quaternion_plus(q, d[0], d[1], d[2], qp);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cand[a + k] = qp[k];
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+      const double xi = x[a + 4 + j];
+      cand[a + 4 + j] = xi + d[3 + j];
+      xn += xi * xi;
+    }
+  }
+  xn = wave_sum_q(xn); dn = wave_sum_q(dn);
+  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = xn; sh[4 + (threadIdx.x >> 6)] = dn; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    partials[gridDim.x + blockIdx.x] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
+  }
+}
+
+// Ceres' gradient_max_norm with quaternion-manifold cameras: |x - Plus(x, -g)|_inf in ambient coordinates (I/trust_region_minimizer.cc:
+// 285-302), g = J^T f / scale the gradient of the unscaled problem (tangent).  |g_i| on points, translations and intrinsics; on a
+// camera's rotation the four components of q - Plus(q, -g_rot).
+__global__ __launch_bounds__(kVecBlock) void bal_gradient_max_quat_kernel(const double* g, const double* scale, const double* x,
+                                                                          int64_t n_points, int64_t n_cameras, double* partials) {
+  __shared__ double sh[4];
+  double m = 0;
+  const int64_t n_pt = 3 * n_points;
+  for (int64_t i = int64_t(blockIdx.x) * kVecBlock + threadIdx.x; i < n_pt + n_cameras; i += int64_t(gridDim.x) * kVecBlock) {
+    if (i < n_pt) {
+      m = fmax(m, fabs(scale ? g[i] / scale[i] : g[i]));
+      continue;
+    }
+    const int64_t t = n_pt + 9 * (i - n_pt), a = n_pt + 10 * (i - n_pt);
+    double gt[9];
+#pragma unroll
+    for (int j = 0; j < 9; ++j) gt[j] = scale ? g[t + j] / scale[t + j] : g[t + j];
+    double q[4], qp[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = x[a + k];
+    quaternion_plus(q, -gt[0], -gt[1], -gt[2], qp);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) m = fmax(m, fabs(q[k] - qp[k]));
+#pragma unroll
+    for (int j = 3; j < 9; ++j) m = fmax(m, fabs(gt[j]));
+  }
+  m = wave_max_q(m);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+}
+
+int grid_for(int64_t n) {
+  int64_t g = (n + kVecBlock - 1) / kVecBlock;
+  return int(g < 1 ? 1 : (g > kMaxVecGrid ? kMaxVecGrid : g));
+}
+
+}  // namespace
+
+hipError_t LaunchBalCandidateQuat(const double* x, const double* step, const double* scale, double* delta, double* cand, int64_t n_points,
+                                  int64_t n_cameras, double* partials, int* nparts, hipStream_t stream) {
+  const int grid = grid_for(3 * n_points + n_cameras);
+  *nparts = grid;
+  hipLaunchKernelGGL(bal_candidate_quat_kernel, dim3(grid), dim3(kVecBlock), 0, stream, x, step, scale, delta, cand, n_points, n_cameras,
+                     partials);
+  return hipGetLastError();
+}
+
+hipError_t LaunchBalGradientMaxQuat(const double* g, const double* scale, const double* x, int64_t n_points, int64_t n_cameras,
+                                    double* partials, int* nparts, hipStream_t stream) {
+  const int grid = grid_for(3 * n_points + n_cameras);
+  *nparts = grid;
+  hipLaunchKernelGGL(bal_gradient_max_quat_kernel, dim3(grid), dim3(kVecBlock), 0, stream, g, scale, x, n_points, n_cameras, partials);
+  return hipGetLastError();
+}
+
+hipError_t LaunchBalEvaluateQuat(const BalEvalArgs& A, bool jacobian, int grid, hipStream_t stream, int camera_model) {
+  const bool robust = A.loss.type != kLossNone;
+#define EVAL_QUAT_CASE(CM)                                                                                                        \
+  case CM:                                                                                                                        \
+    if (jacobian && robust) hipLaunchKernelGGL((bal_evaluate_kernel<true, true, CM>), dim3(grid), dim3(kVecBlock), 0, stream, A);    \
+    else if (jacobian) hipLaunchKernelGGL((bal_evaluate_kernel<true, false, CM>), dim3(grid), dim3(kVecBlock), 0, stream, A);       \
+    else if (robust) hipLaunchKernelGGL((bal_evaluate_kernel<false, true, CM>), dim3(grid), dim3(kVecBlock), 0, stream, A);         \
+    else hipLaunchKernelGGL((bal_evaluate_kernel<false, false, CM>), dim3(grid), dim3(kVecBlock), 0, stream, A);                    \
+    return hipGetLastError();
+  switch (camera_model) {
+    EVAL_QUAT_CASE(kCamQuaternion)
+    EVAL_QUAT_CASE(kCamQuaternionManifold)
+    default: return hipErrorInvalidValue;
+  }
+#undef EVAL_QUAT_CASE
+}
+
+}  // namespace chip

@@ -193,6 +193,9 @@ class CMinimizerSummary(ctypes.Structure):
 
 ABI += [
     ("ceres_hip_bal_create", c_void_p, [POINTER(COptions), c_int32, c_int32, c_int64, POINTER(c_int32), POINTER(c_int32), _DP]),
+    ("ceres_hip_bal_create_with_camera", c_void_p, [POINTER(COptions), c_int32, c_int32, c_int32, c_int64, POINTER(c_int32),
+                                                    POINTER(c_int32), _DP]),
+    ("ceres_hip_bal_num_effective_parameters", c_int32, [c_void_p, POINTER(c_int64)]),
     ("ceres_hip_bal_destroy", None, [c_void_p]),
     ("ceres_hip_bal_last_error", c_char_p, [c_void_p]),
     ("ceres_hip_bal_linear_solver", c_void_p, [c_void_p]),
@@ -862,6 +865,34 @@ DOGLEG_TYPES = {"traditional": TRADITIONAL_DOGLEG, "subspace": SUBSPACE_DOGLEG}
 DOGLEG_NO_ROOT, DOGLEG_COSINE = 1, 2
 
 
+# CERES_HIP_CAMERA_* (include/ceres_hip.h): the camera models of BalProblem, by name — bundle_adjuster's default, --use_quaternions, and
+# --use_quaternions --use_manifolds
+CAMERA_ANGLE_AXIS, CAMERA_QUATERNION, CAMERA_QUATERNION_MANIFOLD = 0, 1, 2
+CAMERA_MODELS = {"angle_axis": CAMERA_ANGLE_AXIS, "quaternion": CAMERA_QUATERNION, "quaternion_manifold": CAMERA_QUATERNION_MANIFOLD}
+
+
+def angle_axis_to_quaternion(a):
+    """AngleAxisToQuaternion (include/ceres/rotation.h), row-wise on an (n, 3) array: (n, 4) [w x y z]."""
+    a = np.asarray(a, dtype=np.float64).reshape(-1, 3)
+    theta = np.sqrt(np.sum(a * a, axis=1))
+    nz = theta != 0.0
+    th = np.where(nz, theta, 1.0)
+    k = np.where(nz, np.sin(0.5 * th) / th, 0.5)
+    return np.concatenate([np.where(nz, np.cos(0.5 * th), 1.0)[:, None], a * k[:, None]], axis=1)
+
+
+def quaternion_to_angle_axis(q):
+    """QuaternionToAngleAxis (include/ceres/rotation.h), row-wise on an (n, 4) [w x y z] array: (n, 3), angle in [-pi, pi]."""
+    q = np.asarray(q, dtype=np.float64).reshape(-1, 4)
+    v = q[:, 1:]
+    sin_theta = np.sqrt(np.sum(v * v, axis=1))
+    nz = sin_theta != 0.0
+    sign = np.copysign(1.0, q[:, 0])
+    st = np.where(nz, sin_theta, 1.0)
+    k = np.where(nz, 2.0 * np.arctan2(sign * sin_theta, sign * q[:, 0]) / st, 2.0)
+    return v * k[:, None]
+
+
 def dogleg_subspace_minimum(B, g, radius):
     """ceres_hip_debug_dogleg_subspace_minimum: (code, x) — the unscaled boundary minimiser x of 1/2 x'Bx + g'x for the 2x2 B, and 0,
     DOGLEG_NO_ROOT or DOGLEG_COSINE."""
@@ -897,11 +928,22 @@ class BalProblem:
     TrustRegionMinimizer::Minimize around the linear solver `options` selects.
 
     state = [3 doubles per point | 9 doubles per camera]; `state_from_bal` / `state_to_bal`
-    convert from the file order (cameras, then points)."""
+    convert from the file order (cameras, then points).
 
-    def __init__(self, options: LinearSolverOptions, num_cameras, num_points, camera_index, point_index, observations):
+    camera_model = "angle_axis" (the default), "quaternion" (bundle_adjuster --use_quaternions: cameras [q_w q_x q_y q_z | t | f k1 k2],
+    Euclidean Plus) or "quaternion_manifold" (--use_quaternions --use_manifolds: QuaternionManifold on q) — or a CAMERA_* number.  The
+    state is ambient (num_parameters: 10 per quaternion camera); gradients are tangent (num_effective_parameters: 9 per camera with
+    the manifold)."""
+
+    def __init__(self, options: LinearSolverOptions, num_cameras, num_points, camera_index, point_index, observations,
+                 camera_model="angle_axis"):
         self._lib = load_library()
         self.options = options
+        if isinstance(camera_model, str):
+            if camera_model not in CAMERA_MODELS:
+                raise ValueError(f"unknown camera model {camera_model!r}: one of {', '.join(CAMERA_MODELS)}")
+            camera_model = CAMERA_MODELS[camera_model]
+        self.camera_model = int(camera_model)
         self.num_cameras, self.num_points = int(num_cameras), int(num_points)
         cam = np.ascontiguousarray(camera_index, dtype=np.int32)
         pt = np.ascontiguousarray(point_index, dtype=np.int32)
@@ -914,21 +956,29 @@ class BalProblem:
                      int(options.force_generic_path), options.cg_check_interval, options.jacobian_storage,
                      options.max_num_spse_iterations, int(options.use_spse_initialization), options.spse_tolerance,
                      int(options.use_explicit_schur_complement))
-        self._h = self._lib.ceres_hip_bal_create(byref(c), self.num_cameras, self.num_points, self.num_observations,
-                                                 cam.ctypes.data_as(POINTER(c_int32)), pt.ctypes.data_as(POINTER(c_int32)),
-                                                 _p(obs))
+        if self.camera_model == CAMERA_ANGLE_AXIS:
+            self._h = self._lib.ceres_hip_bal_create(byref(c), self.num_cameras, self.num_points, self.num_observations,
+                                                     cam.ctypes.data_as(POINTER(c_int32)), pt.ctypes.data_as(POINTER(c_int32)),
+                                                     _p(obs))
+        else:
+            self._h = self._lib.ceres_hip_bal_create_with_camera(byref(c), self.camera_model, self.num_cameras, self.num_points,
+                                                                 self.num_observations, cam.ctypes.data_as(POINTER(c_int32)),
+                                                                 pt.ctypes.data_as(POINTER(c_int32)), _p(obs))
         if not self._h:
             raise HipError(self._lib.ceres_hip_bal_last_error(None).decode())
-        n, m, v = c_int64(), c_int64(), c_int64()
+        n, m, v, t = c_int64(), c_int64(), c_int64(), c_int64()
         self._check(self._lib.ceres_hip_bal_sizes(self._h, byref(n), byref(m), byref(v)))
+        self._check(self._lib.ceres_hip_bal_num_effective_parameters(self._h, byref(t)))
         self.num_parameters, self.num_residuals, self.num_jacobian_values = n.value, m.value, v.value
+        self.num_effective_parameters = t.value
+        self.camera_state_size = 9 if self.camera_model == CAMERA_ANGLE_AXIS else 10
 
     @classmethod
-    def from_file(cls, options: LinearSolverOptions, filename):
-        """BALProblem(filename) (examples/bal_problem.cc:75-135).  Returns (problem, initial state)."""
+    def from_file(cls, options: LinearSolverOptions, filename, camera_model="angle_axis"):
+        """BALProblem(filename, use_quaternions) (examples/bal_problem.cc:75-135).  Returns (problem, initial state)."""
         from . import problems
         nc, npts, cam, pt, obs, par = problems.read_bal(filename)
-        p = cls(options, nc, npts, cam, pt, obs)
+        p = cls(options, nc, npts, cam, pt, obs, camera_model=camera_model)
         return p, p.state_from_bal(par)
 
     def _check(self, rc):
@@ -954,7 +1004,9 @@ class BalProblem:
 
     def preconditioner_blocks(self, not_inverted=False):
         """The block-diagonal preconditioner of the LAST linear solve inside minimize (camera blocks; CGNR: point blocks first)."""
-        n = 81 * self.num_cameras + (9 * self.num_points if self.options.type == CGNR else 0)
+        w = self.num_effective_parameters - 3 * self.num_points
+        w //= max(1, self.num_cameras)
+        n = w * w * self.num_cameras + (9 * self.num_points if self.options.type == CGNR else 0)
         out = np.full(n, np.nan)
         inner = self._lib.ceres_hip_bal_linear_solver(self._h)
         rc = self._lib.ceres_hip_get_preconditioner_blocks(inner, int(not_inverted), _p(out), n)
@@ -975,13 +1027,23 @@ class BalProblem:
         return out
 
     def state_from_bal(self, parameters):
-        """BAL file order (9 per camera, then 3 per point) -> state."""
+        """BAL file order (9 per camera, then 3 per point) -> state; quaternion cameras through AngleAxisToQuaternion, as
+        BALProblem(filename, use_quaternions = true) converts them (examples/bal_problem.cc:110-131)."""
         a = _f64(parameters, 9 * self.num_cameras + 3 * self.num_points)
-        return np.concatenate([a[9 * self.num_cameras:9 * self.num_cameras + 3 * self.num_points], a[:9 * self.num_cameras]])
+        cams = a[:9 * self.num_cameras]
+        if self.camera_model != CAMERA_ANGLE_AXIS:
+            c9 = cams.reshape(-1, 9)
+            cams = np.concatenate([angle_axis_to_quaternion(c9[:, :3]), c9[:, 3:]], axis=1).reshape(-1)
+        return np.concatenate([a[9 * self.num_cameras:9 * self.num_cameras + 3 * self.num_points], cams])
 
     def state_to_bal(self, state):
+        """state -> BAL file order; quaternion cameras through QuaternionToAngleAxis (BALProblem::WriteToFile, examples/bal_problem.cc:157-160)."""
         a = _f64(state, self.num_parameters)
-        return np.concatenate([a[3 * self.num_points:], a[:3 * self.num_points]])
+        cams = a[3 * self.num_points:]
+        if self.camera_model != CAMERA_ANGLE_AXIS:
+            c10 = cams.reshape(-1, 10)
+            cams = np.concatenate([quaternion_to_angle_axis(c10[:, :4]), c10[:, 4:]], axis=1).reshape(-1)
+        return np.concatenate([cams, a[:3 * self.num_points]])
 
     def set_loss(self, kind, a=1.0, b=1.0, scale=1.0):
         """The robust loss of every observation, ScaledLoss(kind(a[, b]), scale) (include/ceres/loss_function.h): "trivial", "huber",
@@ -1033,11 +1095,12 @@ class BalProblem:
         return n.value, float(t[0]), g.value
 
     def evaluate(self, state, residuals=False, gradient=False, jacobian=False):
-        """Evaluator::Evaluate: returns (cost, residuals|None, gradient|None, jacobian values|None)."""
+        """Evaluator::Evaluate: returns (cost, residuals|None, gradient|None, jacobian values|None); the gradient and the Jacobian are
+        the local (tangent) ones."""
         x = _f64(state, self.num_parameters)
         cost = np.zeros(1)
         r = np.empty(self.num_residuals) if residuals else None
-        g = np.empty(self.num_parameters) if gradient else None
+        g = np.empty(self.num_effective_parameters) if gradient else None
         v = np.empty(self.num_jacobian_values) if jacobian else None
         self._check(self._lib.ceres_hip_bal_evaluate(self._h, _p(x), _p(cost), _p(r), _p(g), _p(v)))
         return float(cost[0]), r, g, v

@@ -4,6 +4,7 @@
 #ifndef CERES_HIP_HOST_BAL_PROBLEM_H_
 #define CERES_HIP_HOST_BAL_PROBLEM_H_
 
+#include <cmath>
 #include <cstdio>
 #include <stdexcept>
 #include <string>
@@ -13,6 +14,24 @@
 #include "hip_linear_solver.h"
 
 namespace ceres_hip {
+
+// AngleAxisToQuaternion / QuaternionToAngleAxis (include/ceres/rotation.h), quaternion [w x y z]
+inline void AngleAxisToQuaternion(const double* a, double* q) {
+  const double theta = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
+  double k = 0.5;
+  q[0] = 1.0;
+  if (theta != 0.0) { k = std::sin(0.5 * theta) / theta; q[0] = std::cos(0.5 * theta); }
+  for (int i = 0; i < 3; ++i) q[1 + i] = a[i] * k;
+}
+inline void QuaternionToAngleAxis(const double* q, double* a) {
+  const double sin_theta = std::sqrt(q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  double k = 2.0;
+  if (sin_theta != 0.0) {
+    const double sign = std::copysign(1.0, q[0]);   // (theta > pi / 2: the angle 2 theta - 2 pi, within [-pi, pi])
+    k = 2.0 * std::atan2(sign * sin_theta, sign * q[0]) / sin_theta;
+  }
+  for (int i = 0; i < 3; ++i) a[i] = q[1 + i] * k;
+}
 
 // examples/bal_problem.cc:75-135 — "cameras points observations", one "camera point x y" line per
 // observation, then 9 doubles per camera and 3 per point.
@@ -40,17 +59,44 @@ struct BalData {
     if (!ok) throw std::runtime_error(filename + " is not a BAL file");
     return d;
   }
-  // state of the reduced, Schur-ordered program: points first, then cameras
-  std::vector<double> State() const {
+  // state of the reduced, Schur-ordered program: points first, then cameras — 10 doubles per camera for the quaternion camera models
+  // (CERES_HIP_CAMERA_*), converted as BALProblem(filename, use_quaternions = true) does (examples/bal_problem.cc:110-131)
+  std::vector<double> State(int camera_model = CERES_HIP_CAMERA_ANGLE_AXIS) const {
     std::vector<double> x(parameters.begin() + 9 * size_t(num_cameras), parameters.end());
-    x.insert(x.end(), parameters.begin(), parameters.begin() + 9 * size_t(num_cameras));
+    if (camera_model == CERES_HIP_CAMERA_ANGLE_AXIS) {
+      x.insert(x.end(), parameters.begin(), parameters.begin() + 9 * size_t(num_cameras));
+      return x;
+    }
+    for (int c = 0; c < num_cameras; ++c) {
+      const double* cam = parameters.data() + 9 * size_t(c);
+      double q[4];
+      AngleAxisToQuaternion(cam, q);
+      x.insert(x.end(), q, q + 4);
+      x.insert(x.end(), cam + 3, cam + 9);
+    }
     return x;
+  }
+  // the cameras of a state back in BAL order (BALProblem::WriteToFile, examples/bal_problem.cc:157-160): 9 per camera, then 3 per point
+  std::vector<double> Parameters(const std::vector<double>& state, int camera_model = CERES_HIP_CAMERA_ANGLE_AXIS) const {
+    const size_t np3 = 3 * size_t(num_points), cs = camera_model == CERES_HIP_CAMERA_ANGLE_AXIS ? 9 : 10;
+    std::vector<double> p(9 * size_t(num_cameras) + np3);
+    for (int c = 0; c < num_cameras; ++c) {
+      const double* cam = state.data() + np3 + cs * c;
+      double* out = p.data() + 9 * size_t(c);
+      if (cs == 9) { for (int i = 0; i < 9; ++i) out[i] = cam[i]; continue; }
+      QuaternionToAngleAxis(cam, out);
+      for (int i = 0; i < 6; ++i) out[3 + i] = cam[4 + i];
+    }
+    for (size_t i = 0; i < np3; ++i) p[9 * size_t(num_cameras) + i] = state[i];
+    return p;
   }
 };
 
 class HipBalProblem {
  public:
-  HipBalProblem(const LinearSolver::Options& options, const BalData& d) {
+  // camera_model: CERES_HIP_CAMERA_* (bundle_adjuster --use_quaternions [--use_manifolds]: QUATERNION [_MANIFOLD]); BalData::State(camera_model)
+  // is the matching state
+  HipBalProblem(const LinearSolver::Options& options, const BalData& d, int camera_model = CERES_HIP_CAMERA_ANGLE_AXIS) {
     ceres_hip_options o{};
     o.solver_type = options.type;
     o.preconditioner_type = options.preconditioner_type;
@@ -58,10 +104,11 @@ class HipBalProblem {
     o.max_num_iterations = options.max_num_iterations;
     o.residual_reset_period = options.residual_reset_period;
     o.device = options.device;
-    handle_ = ceres_hip_bal_create(&o, d.num_cameras, d.num_points, int64_t(d.camera_index.size()), d.camera_index.data(),
-                                   d.point_index.data(), d.observations.data());
-    if (!handle_) throw std::runtime_error(std::string("ceres_hip_bal_create: ") + ceres_hip_bal_last_error(nullptr));
+    handle_ = ceres_hip_bal_create_with_camera(&o, camera_model, d.num_cameras, d.num_points, int64_t(d.camera_index.size()),
+                                               d.camera_index.data(), d.point_index.data(), d.observations.data());
+    if (!handle_) throw std::runtime_error(std::string("ceres_hip_bal_create_with_camera: ") + ceres_hip_bal_last_error(nullptr));
     ceres_hip_bal_sizes(handle_, &num_parameters_, &num_residuals_, &num_jacobian_values_);
+    ceres_hip_bal_num_effective_parameters(handle_, &num_effective_parameters_);
   }
   ~HipBalProblem() { ceres_hip_bal_destroy(handle_); }
   HipBalProblem(const HipBalProblem&) = delete;
@@ -69,6 +116,7 @@ class HipBalProblem {
 
   int NumParameters() const { return int(num_parameters_); }   // Evaluator::NumParameters, I/evaluator.h:151
   int NumResiduals() const { return int(num_residuals_); }     // Evaluator::NumResiduals, :158
+  int NumEffectiveParameters() const { return int(num_effective_parameters_); }   // Evaluator::NumEffectiveParameters: the gradient's length
   // The loss of every residual block, ScaledLoss(loss, scale): loss_type CERES_HIP_LOSS_*, a / b its constructor arguments
   // (bundle_adjuster --robustify: SetLoss(CERES_HIP_LOSS_HUBER, 1.0)).  Applies to the later Evaluate / Minimize calls.
   void SetLoss(int loss_type, double a, double b = 1.0, double scale = 1.0) {
@@ -110,7 +158,7 @@ class HipBalProblem {
 
  private:
   ceres_hip_bal* handle_ = nullptr;
-  int64_t num_parameters_ = 0, num_residuals_ = 0, num_jacobian_values_ = 0;
+  int64_t num_parameters_ = 0, num_residuals_ = 0, num_jacobian_values_ = 0, num_effective_parameters_ = 0;
 };
 
 }  // namespace ceres_hip

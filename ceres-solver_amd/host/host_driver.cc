@@ -261,16 +261,18 @@ int RunStreamedLmStep(const char* name, BlockSparseMatrix* A, const std::vector<
 
 }  // namespace
 
-// host_driver <problem.txt> [max_num_iterations [traditional_dogleg|subspace_dogleg]]: BALProblem + Evaluator + TrustRegionMinimizer
-// through the C++ mirror (with a dogleg type: DENSE_SCHUR and the DOGLEG strategy, bundle_adjuster --trust_region_strategy=dogleg --dogleg)
-int RunBalFile(const char* filename, int max_it, const char* dogleg) {
+// host_driver <problem.txt> [max_num_iterations [traditional_dogleg|subspace_dogleg] [quaternion|quaternion_manifold]]: BALProblem +
+// Evaluator + TrustRegionMinimizer through the C++ mirror (with a dogleg type: DENSE_SCHUR and the DOGLEG strategy, bundle_adjuster
+// --trust_region_strategy=dogleg --dogleg; with a camera model: --use_quaternions [--use_manifolds], the final state written back in
+// angle-axis form and evaluated again by an angle-axis problem)
+int RunBalFile(const char* filename, int max_it, const char* dogleg, int camera_model) {
   const BalData data = BalData::Read(filename);
   LinearSolver::Options o;
   o.type = dogleg ? DENSE_SCHUR : ITERATIVE_SCHUR;
   o.preconditioner_type = SCHUR_JACOBI;
   o.min_num_iterations = 0;
   o.max_num_iterations = 500;
-  HipBalProblem problem(o, data);
+  HipBalProblem problem(o, data, camera_model);
   if (dogleg) {
     const std::string kind(dogleg);
     if (kind != "traditional_dogleg" && kind != "subspace_dogleg") {
@@ -279,7 +281,7 @@ int RunBalFile(const char* filename, int max_it, const char* dogleg) {
     }
     problem.SetTrustRegionStrategy(CERES_HIP_DOGLEG, kind == "subspace_dogleg" ? CERES_HIP_SUBSPACE_DOGLEG : CERES_HIP_TRADITIONAL_DOGLEG);
   }
-  std::vector<double> x = data.State();
+  std::vector<double> x = data.State(camera_model);
   double cost0 = 0;
   if (!problem.Evaluate(x.data(), &cost0, nullptr, nullptr, nullptr)) return 1;
   ceres_hip_minimizer_options mo;
@@ -288,6 +290,16 @@ int RunBalFile(const char* filename, int max_it, const char* dogleg) {
   const ceres_hip_minimizer_summary s = problem.Minimize(mo, x.data());
   double cost1 = 0;
   if (!problem.Evaluate(x.data(), &cost1, nullptr, nullptr, nullptr)) return 1;
+  if (camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) {   // the final state in angle-axis form: the same cost
+    BalData aa = data;
+    aa.parameters = data.Parameters(x, camera_model);
+    HipBalProblem angle_axis(o, aa);
+    const std::vector<double> xa = aa.State();
+    double cost_aa = 0;
+    if (!angle_axis.Evaluate(xa.data(), &cost_aa, nullptr, nullptr, nullptr)) return 1;
+    std::printf("quaternion camera_model=%d effective_parameters=%d angle_axis_final=%.17g\n", camera_model, problem.NumEffectiveParameters(),
+                cost_aa);
+  }
   std::printf("bal parameters=%d residuals=%d initial_cost=%.17g evaluated_initial=%.17g final_cost=%.17g evaluated_final=%.17g "
               "successful=%d unsuccessful=%d termination=%d linear_solves=%d message=%s\n",
               problem.NumParameters(), problem.NumResiduals(), s.initial_cost, cost0, s.final_cost, cost1, s.num_successful_steps,
@@ -300,7 +312,17 @@ int main(int argc, char** argv) {
     std::printf("FAIL no gfx950 device visible (the library has no CPU path)\n");
     return 2;
   }
-  if (argc >= 2) return RunBalFile(argv[1], argc >= 3 ? std::atoi(argv[2]) : 10, argc >= 4 ? argv[3] : nullptr);
+  if (argc >= 2) {
+    const char* dogleg = nullptr;
+    int camera_model = CERES_HIP_CAMERA_ANGLE_AXIS;
+    for (int i = 3; i < argc; ++i) {
+      const std::string a(argv[i]);
+      if (a == "quaternion") camera_model = CERES_HIP_CAMERA_QUATERNION;
+      else if (a == "quaternion_manifold") camera_model = CERES_HIP_CAMERA_QUATERNION_MANIFOLD;
+      else dogleg = argv[i];
+    }
+    return RunBalFile(argv[1], argc >= 3 ? std::atoi(argv[2]) : 10, dogleg, camera_model);
+  }
   int bad = 0, nelim = 0;
   std::vector<double> b, D;
   auto p2 = Problem2(&b, &D, &nelim);

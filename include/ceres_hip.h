@@ -444,12 +444,35 @@ typedef struct ceres_hip_bal ceres_hip_bal;
 ceres_hip_bal* ceres_hip_bal_create(const ceres_hip_options* options, int32_t num_cameras, int32_t num_points,
                                     int64_t num_observations, const int32_t* camera_index,
                                     const int32_t* point_index, const double* observations);
+/* Camera models (bundle_adjuster --use_quaternions, --use_manifolds: examples/bundle_adjuster.cc:111-113, 323-347).  The quaternion
+ * cameras are [q_w q_x q_y q_z | t(3) | f k1 k2] (Ceres' quaternion order; SnavelyReprojectionErrorWithQuaternions, rotation by
+ * QuaternionRotatePoint: q need not have unit norm).                                 state / Jacobian columns per camera */
+#define CERES_HIP_CAMERA_ANGLE_AXIS 0           /* [angle-axis(3) t(3) f k1 k2] (ceres_hip_bal_create)        9 / 9  */
+#define CERES_HIP_CAMERA_QUATERNION 1           /* Euclidean Plus on all ten (--use_quaternions)              10 / 10 */
+#define CERES_HIP_CAMERA_QUATERNION_MANIFOLD 2  /* ProductManifold<QuaternionManifold, EuclideanManifold<6>>
+                                                   (--use_quaternions --use_manifolds)                         10 / 9  */
+/* ceres_hip_bal_create with a camera model (ceres_hip_bal_create is camera_model CERES_HIP_CAMERA_ANGLE_AXIS).  The state stays
+ * [3 per point | cameras] and is AMBIENT (Evaluator::NumParameters, ceres_hip_bal_sizes); the Jacobian, the gradient and
+ * minimize's step and scaling are in the TANGENT space (Evaluator::NumEffectiveParameters, ceres_hip_bal_num_effective_parameters):
+ * the local Jacobian ambient J x PlusJacobian, then the Corrector, as ResidualBlock::Evaluate forms it.  F cells are 2 x 10 or 2 x 9
+ * (E cells at 6 r, F cells at 6 n_rows + 2 width r).  NULL (message in ceres_hip_bal_last_error(NULL)) for an unknown camera_model —
+ * checked before any device call — and for what ceres_hip_bal_create refuses.  With a quaternion camera: inner iterations
+ * (ceres_hip_bal_set_inner_iterations with anything but CERES_HIP_INNER_NONE, ceres_hip_bal_inner_iterate) and the tile timing probe
+ * return CERES_HIP_E_UNSUPPORTED, so does ceres_hip_bal_minimize on a sharded handle; the loop evaluates in the caller layout (the
+ * tile-order evaluator is angle-axis only). */
+ceres_hip_bal* ceres_hip_bal_create_with_camera(const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras,
+                                                int32_t num_points, int64_t num_observations, const int32_t* camera_index,
+                                                const int32_t* point_index, const double* observations);
 void ceres_hip_bal_destroy(ceres_hip_bal* p);
 const char* ceres_hip_bal_last_error(const ceres_hip_bal* p);
 /* The linear solver this problem drives (borrowed; operators, timing, info). */
 ceres_hip_solver* ceres_hip_bal_linear_solver(ceres_hip_bal* p);
-/* Evaluator::NumParameters / NumResiduals, and the number of Jacobian values (24 per observation). */
+/* Evaluator::NumParameters (the ambient state) / NumResiduals, and the number of Jacobian values (6 + 2 x camera Jacobian columns per
+ * observation: 24, or 26 for CERES_HIP_CAMERA_QUATERNION). */
 int ceres_hip_bal_sizes(const ceres_hip_bal* p, int64_t* num_parameters, int64_t* num_residuals, int64_t* num_jacobian_values);
+/* Evaluator::NumEffectiveParameters: the tangent length — of the gradient, and the Jacobian's columns (= num_parameters for the
+ * angle-axis and the Euclidean quaternion camera). */
+int ceres_hip_bal_num_effective_parameters(const ceres_hip_bal* p, int64_t* num_effective_parameters);
 /* row_observation[r] = index of the observation residual row block r belongs to. */
 int ceres_hip_bal_get_row_order(const ceres_hip_bal* p, int32_t* row_observation);
 /* Robust losses (include/ceres/loss_function.h:131-330, internal/ceres/loss_function.cc:46-175).  Ceres has no enumeration of
