@@ -2,7 +2,13 @@
 """Randomised campaign on the BAL front end (GPU box): scenes of random size from the oracle's generator — the device
 evaluator (cost, residuals, analytic Jacobian, gradient) against the oracle's dual numbers, and ceres_hip_bal_minimize against the
 oracle's trust-region loop (same accept / reject sequence, CG counts within one, costs to 1e-6), both solvers.
-usage: fuzz_frontend.py [first_seed] [count]"""
+--variants: the front end's other options (tests/test_gpu_frontend_matrix.py's factors: camera model, loss, trust-region strategy, linear
+solver, inner iterations, Jacobi scaling, evaluator form) drawn at random among the allowed tuples, with that module's checks against the
+composed restatement (tests/frontend_reference.py): the evaluation, one inner pass and the loop on a random edge scene
+(test_gpu_frontend_matrix.edge_scene; the loop's costs, radii and state compared only where the restatement's own sensitivity to the
+Jacobian's rounding, measured per case, allows: see EDGE_ILL_CONDITIONED), and the loop on a random clean scene (clean_scene).  One
+JSON line per case, then the worst deviation of every check.
+usage: fuzz_frontend.py [first_seed] [count] [--variants]"""
 import json
 import os
 import sys
@@ -90,18 +96,57 @@ def run_case(seed):
                 seconds=round(time.time() - t0, 2))
 
 
+def run_variant(seed):
+    import test_gpu_frontend_matrix as M
+    rng = np.random.default_rng(700001 * seed + 3)
+    while True:
+        case = tuple(levels[int(rng.integers(len(levels)))] for _, levels in M.FACTORS)
+        if M.allowed(case):
+            break
+    shape = dict(npts=int(rng.choice([90, 120, 160, 200])), track=int(rng.integers(5, 11)))
+    t0 = time.time()
+    sc = None
+    for k in range(5):   # (a draw that leaves a camera without observations: the next scene seed)
+        try:
+            sc = M.edge_scene(oracle, seed=seed * 10 + k + 1, **shape)
+            break
+        except AssertionError:
+            continue
+    if sc is None:
+        return dict(seed=seed, case=M.case_id(case), **shape, ok=False, error="no edge scene in five draws")
+    loop_sc = M.clean_scene(oracle, seed=seed + 1)
+    c = dict(zip(M.NAMES, case))
+    for name, v in (("CERES_HIP_EVAL_TILES", c["tiles"]), ("CERES_HIP_INNER_FORM", c["inner_form"])):
+        if v is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = v
+    dev = M.compare(hip, oracle, sc, loop_sc, case, conditioning=True)
+    lim = M.limits(case, conditioning=dev["edge_conditioning"])
+    bad = M.exceeded(dev, lim)
+    return dict(seed=seed, case=M.case_id(case), nobs=int(sc[2].shape[0]), **shape, ok=not bad, bad=bad,
+                dev={k: (float(v) if isinstance(v, (int, float, np.floating)) else v) for k, v in dev.items()},
+                seconds=round(time.time() - t0, 2))
+
+
 def main():
-    first = int(sys.argv[1]) if len(sys.argv) > 1 else 0
-    count = int(sys.argv[2]) if len(sys.argv) > 2 else 40
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    first = int(args[0]) if args else 0
+    count = int(args[1]) if len(args) > 1 else 40
+    variants = "--variants" in sys.argv
     failed = 0
+    worst = {}
     for seed in range(first, first + count):
         try:
-            r = run_case(seed)
+            r = run_variant(seed) if variants else run_case(seed)
+            for k, v in r.get("dev", {}).items():
+                if isinstance(v, float) and not (worst.get(k, (-1.0,))[0] >= v):
+                    worst[k] = (v, r["case"])
         except Exception as ex:
             r = dict(seed=seed, ok=False, error=repr(ex)[:600], trace=traceback.format_exc()[-1000:])
         failed += 0 if r["ok"] else 1
         print(json.dumps(r), flush=True)
-    print(json.dumps({"cases": count, "failed": failed}), flush=True)
+    print(json.dumps({"cases": count, "failed": failed, **({"worst": worst} if variants else {})}), flush=True)
     return 1 if failed else 0
 
 
