@@ -18,9 +18,16 @@ Workload (config.workload): synthetic BAL-shaped Jacobian with Venice-1778's blo
 the configuration BASELINE.json's targets are quoted on.  Default solver: ITERATIVE_SCHUR +
 SCHUR_JACOBI (BASELINE.json configs[0] and [2]; dominant kernel: the fused implicit Schur product
 S·x); `--solver cgnr` switches to CGNR + JACOBI (dominant kernel: the fused JtJx SpMV).  With
-`--both-solvers 1` (default, N = 1) the other solver is measured in the same run: `extra` carries its
+`--full` and `--both-solvers 1` (default, N = 1) the other solver is measured in the same run: `extra` carries its
 step rate and the line carries BOTH rooflines (`roofline` for the timed solver's operator,
 `roofline_jtjx` / `roofline_sx` for the other).
+
+A plain run measures the headline figure alone: it sets up, warms up, times the `--steps` steps, writes
+`--dump-outputs` if asked, and prints the line with `value`, `ms_per_step`, `config` and `step_roofline`
+(the other figures are null).  Everything else the benchmark measures or checks — the operator rooflines
+and their live counter passes, the other solver, the host boundary, the trust-region loop and the scene
+steps, the other configurations, sizes and precisions, the shard ceiling, the full-size oracle check and
+the CPU baseline — runs only with `--full`, each leg as its own option below says.
 
 N > 1 (strong scaling): the SAME problem sharded by point across the ranks
 (ceres-solver_amd/partition.py); camera-space sums and the CGNR inner products go through
@@ -115,7 +122,11 @@ def parse():
                          "10 M points x 3 observations, 50 k cameras (camera accumulators do not fit in LDS); synthetic1M = the same regime at a tenth")
     ap.add_argument("--storage", default="fp64", choices=["fp64", "fp32"],
                     help="fp32: Jacobian tiles rounded to fp32, fp64 arithmetic (configs[4] 'fp32 and fp64'; an accuracy mode, not parity)")
-    ap.add_argument("--host-boundary-steps", type=int, default=5,
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement and check beyond the headline figure (the options of the group below; a plain run "
+                         "times the steps alone)")
+    fa = ap.add_argument_group("measurements beyond the headline figure (only with --full)")
+    fa.add_argument("--host-boundary-steps", type=int, default=5,
                     help="also time this many steps through the host-pointer boundary (ceres_hip_lm_compute_step: H2D of values/residuals from "
                          "pinned memory + the step + D2H of the step), reported as host_boundary (N=1; 0: skip)")
     ap.add_argument("--solver", default="iterative_schur", choices=["cgnr", "iterative_schur"])
@@ -126,37 +137,37 @@ def parse():
     ap.add_argument("--values", default="normal", choices=["normal", "scene"],
                     help="normal: N(0,1) Jacobian values (SURVEY.md §8d); scene: the first LM linear system of a synthetic "
                          "bundle-adjustment scene (Snavely camera model, Jacobi-scaled like TrustRegionMinimizer)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0)
-    ap.add_argument("--kernel-iters", type=int, default=50)
-    ap.add_argument("--minimizer-iterations", type=int, default=8,
+    fa.add_argument("--no-cpu-baseline", action="store_true")
+    fa.add_argument("--cpu-seconds", type=float, default=20.0)
+    fa.add_argument("--kernel-iters", type=int, default=50)
+    fa.add_argument("--minimizer-iterations", type=int, default=8,
                     help="also run the device-resident trust-region loop (f4) for this many iterations and report it in `extra` (0: skip)")
-    ap.add_argument("--both-solvers", type=int, default=1, help="also report the other solver in `extra` (N=1 only)")
+    fa.add_argument("--both-solvers", type=int, default=1, help="also report the other solver in `extra` (N=1 only)")
     ap.add_argument("--eta", type=float, default=0.1, help="q_tolerance of the timed steps (Solver::Options::eta; bundle_adjuster runs 0.01)")
-    ap.add_argument("--scene-step-steps", type=int, default=10,
+    fa.add_argument("--scene-step-steps", type=int, default=10,
                     help="also time this many LM steps at eta = 0.1 and 0.01 on the Jacobi-scaled Jacobian of the synthetic SCENE the device "
                          "evaluator produces (scene_step; N=1, needs --minimizer-iterations > 0; 0: skip)")
-    ap.add_argument("--conditioned-steps", type=int, default=5,
+    fa.add_argument("--conditioned-steps", type=int, default=5,
                     help="also time this many LM steps at eta = 1e-2 / 1e-3 / 1e-4 on a SEQUENCE-like scene (banded camera graph: tens of CG "
                          "iterations per step; conditioned_step; N=1, needs --minimizer-iterations > 0; 0: skip)")
-    ap.add_argument("--extra-synthetic10m", type=int, default=1,
-                    help="default venice1778 run at N=1: also run `--workload synthetic10M` (BASELINE.json configs[4]) in a child process and put a "
+    fa.add_argument("--extra-synthetic10m", type=int, default=1,
+                    help="venice1778 run at N=1: also run `--workload synthetic10M` (BASELINE.json configs[4]) in a child process and put a "
                          "condensed result under extra.synthetic10M (0: skip)")
-    ap.add_argument("--extra-real-graph", type=int, default=1, help="default line: S.x / JtJx on the replicated libmv visibility graph (extra.real_graph)")
-    ap.add_argument("--extra-other-shapes", type=int, default=1, help="default line: camera widths other than 9, the libmv structure and the generic kernels on the Ladybug shape (extra.other_shapes)")
-    ap.add_argument("--extra-dense-cholesky", type=int, default=1, help="default line: DENSE_SCHUR's factorisation at n = 8190 (extra.dense_schur_cholesky)")
-    ap.add_argument("--also-fp32", type=int, default=-1, help="also time the fp32-tile storage mode (extra.fp32_tiles; BASELINE.json configs[4] asks for a sweep over both "
-                                                               "precisions): -1 = on the default Venice line, 1 = on, 0 = off")
-    ap.add_argument("--extra-banded", type=int, default=1, help="default line: S.x / JtJx on a 50 000-camera sequence-like (banded) graph (extra.banded50k)")
-    ap.add_argument("--extra-configs", type=int, default=1, help="default line: BASELINE.json configs[1] (Dubrovnik-16, CGNR + JACOBI) and configs[2] "
+    fa.add_argument("--extra-real-graph", type=int, default=1, help="venice1778 line: S.x / JtJx on the replicated libmv visibility graph (extra.real_graph)")
+    fa.add_argument("--extra-other-shapes", type=int, default=1, help="venice1778 line: camera widths other than 9, the libmv structure and the generic kernels on the Ladybug shape (extra.other_shapes)")
+    fa.add_argument("--extra-dense-cholesky", type=int, default=1, help="venice1778 line: DENSE_SCHUR's factorisation at n = 8190 (extra.dense_schur_cholesky)")
+    fa.add_argument("--also-fp32", type=int, default=-1, help="also time the fp32-tile storage mode (extra.fp32_tiles; BASELINE.json configs[4] asks for a sweep over both "
+                                                               "precisions): -1 = on the venice1778 line, 1 = on, 0 = off")
+    fa.add_argument("--extra-banded", type=int, default=1, help="venice1778 line: S.x / JtJx on a 50 000-camera sequence-like (banded) graph (extra.banded50k)")
+    fa.add_argument("--extra-configs", type=int, default=1, help="venice1778 line: BASELINE.json configs[1] (Dubrovnik-16, CGNR + JACOBI) and configs[2] "
                                                                  "(Ladybug-1723, ITERATIVE_SCHUR + SCHUR_JACOBI): steps/s, operator roofline, oracle check, CPU port (extra.configs)")
-    ap.add_argument("--pmc-live", type=int, default=1, help="N = 1: measure roofline.traffic now with two rocprofv3 --pmc passes in child processes "
+    fa.add_argument("--pmc-live", type=int, default=1, help="N = 1: measure roofline.traffic now with two rocprofv3 --pmc passes in child processes "
                                                             "(tools/pmc_live.py; 0: the committed constant of profiles/pmc_traffic.json)")
-    ap.add_argument("--pmc-live-timeout", type=float, default=120.0, help="seconds per counter pass")
-    ap.add_argument("--shard-ceiling", type=int, default=1,
+    fa.add_argument("--pmc-live-timeout", type=float, default=120.0, help="seconds per counter pass")
+    fa.add_argument("--shard-ceiling", type=int, default=1,
                     help="N = 1: also run rank 0's shard of the workload for N = 2, 4, 8 alone on the device with the sharded code path on "
                          "(ghost peers) and report T_1 / (N T_shard) as extra.shard_ceiling (0: skip)")
-    ap.add_argument("--oracle-check", type=int, default=-1,
+    fa.add_argument("--oracle-check", type=int, default=-1,
                     help="(-1 = on where one oracle step takes about a second: the workloads whose camera sums fit in LDS) compare the step of the LAST timed solve with ONE oracle step on the same FULL-SIZE inputs (16 threads; N > 1: the ranks' "
                          "shards of the step are gathered and assembled first) and report it as oracle_check.  Independent of --no-cpu-baseline: "
                          "the synthetic10M child and the one-GPU N = 8 validation run use it")
@@ -525,11 +536,62 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     step_ok = bool(torch.isfinite(tx).all().item())
+    scalar_bytes = 4 if storage else 8
+
+    def finish(extra, roofline=None, roofline_other=None, cpu=None, oracle_check=None, host_boundary=None, scene_tr=None, scene_step=None):
+        """Rank 0 prints the one JSON line (the figures a plain run does not measure are null); every rank closes its solver."""
+        if rank == 0:
+            value = args.steps / elapsed
+            line = {
+                "metric": "LM trust-region steps/sec (linear-solve hot path) + JtJx SpMV HBM GB/s on BAL",
+                "value": round(value, 4), "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+                "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
+                "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic", "full": bool(args.full),
+                "config": {"workload": f"{args.workload}-shaped synthetic BAL Jacobian <2,3,9>: {n_cams} cameras, {n_points} points, "
+                                       f"{n_obs} observations, " + ("N(0,1) values" if args.values == "normal" else "values = Jacobi-scaled Snavely Jacobian "
+                                       "of a synthetic scene (first LM step)") + f", seed 38401, camera popularity skew {args.skew}"
+                                       + (", values generated in HBM (torch.randn), one generator per rank" if many_cameras else ""),
+                           "solver": "CGNR + JACOBI" if args.solver == "cgnr" else "ITERATIVE_SCHUR + SCHUR_JACOBI",
+                           "step": ("LevenbergMarquardtStrategy::ComputeStep (diag(J'J), D = sqrt(diag/1e4), Solve, finite check, negate) + "
+                                    "model cost change, all on the device" if args.step == "lm_step" else "LinearSolver::Solve"),
+                           "eta": args.eta, "max_num_iterations": 500, "cg_iterations_per_step": iters[-1],
+                           "termination": hs.TERMINATION_NAMES[last.termination_type],
+                           "parallelism": (f"points sharded over {world} rank(s), camera-space sums by " +
+                                           ("the one-shot peer-to-peer all-reduce (hipIpc / xGMI)" if solver.p2p_ok else "RCCL all-reduce") +
+                                           (" — ONE-GPU VALIDATION MODE, timings meaningless" if one_gpu else ""))
+                                          if world > 1 else "1 GPU",
+                           "collectives_per_step": collectives_last_step if world > 1 and args.step == "lm_step" else 0,
+                           "inputs_resident_in_hbm": True, "step_finite": step_ok,
+                           "jacobian_storage": "fp32 tiles, fp64 arithmetic (accuracy mode, not parity)" if storage else "fp64",
+                           "kernel_path": "fused<2,3,9>" if info.kernel_path == hs.PATH_BAL else "generic",
+                           "camera_accumulators_in_lds": bool(info.camera_accum_in_lds)},
+                "roofline": roofline, "cpu_baseline": cpu, "oracle_check": oracle_check, "host_boundary": host_boundary, "scene_trust_region": scene_tr, "scene_step": scene_step,
+                "extra": extra,
+            }
+            if args.step == "lm_step":  # the whole step against ITS roofline: minimum bytes of all its passes / measured time / peak
+                tot_obs, tot_pts = (n_obs, n_points)
+                mb = step_min_bytes(args.solver, tot_obs, tot_pts, n_cams, int(iters[-1]), scalar_bytes)
+                line["step_roofline"] = {"bound": "hbm", "min_bytes_per_step": int(mb), "achieved": round(mb / (elapsed / args.steps) / 1e9, 1),
+                                         "peak": HBM_PEAK_GBS * world, "unit": "GB/s", "frac": round(mb / (elapsed / args.steps) / 1e9 / (HBM_PEAK_GBS * world), 4),
+                                         "what": "minimum HBM bytes of every pass of the step (J in the layout each pass wants; re-layout not counted) / ms_per_step"}
+            if roofline_other is not None:
+                line["roofline_jtjx" if args.solver == "iterative_schur" else "roofline_sx"] = roofline_other
+            # what a Ceres process with a CPU evaluator gets through the drop-in boundary (PCIe H2D of J and f every accepted step): next to
+            # `value`, which is the device-resident rate
+            line["value_host_boundary"] = None if host_boundary is None else host_boundary["steps_per_s"]
+            print(json.dumps(line), flush=True)
+        solver.close()
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+
+    if not args.full:   # a plain run: the headline figure alone; what setting up measured on the way comes along
+        finish({"set_structure_s": round(getattr(solver, "set_structure_seconds", float("nan")), 3), "device_bytes": int(info.device_bytes)})
+        return
     timing = phase_timing(solver, (tv, tb, tD, tx), args.step, args.eta)   # (one more step of the same kind, untimed, with the phase events on)
 
     # ---- dominant kernel against the HBM roofline (HIP events on the solver's stream) ----
     kind = "jtjx" if args.solver == "cgnr" else "sx"
-    scalar_bytes = 4 if storage else 8
     my_obs = int(info.num_observations)
     my_points = int(info.num_e_blocks)
 
@@ -882,7 +944,7 @@ def main():
         if free_b < 60e9:
             extra["synthetic10M"] = {"skipped": f"{free_b / 1e9:.0f} GB of HBM free, the child wants 60"}
         else:
-            cmd = [sys.executable, os.path.abspath(__file__), "--workload", "synthetic10M", "--steps", "5", "--warmup", "1", "--kernel-iters", "20",
+            cmd = [sys.executable, os.path.abspath(__file__), "--workload", "synthetic10M", "--full", "--steps", "5", "--warmup", "1", "--kernel-iters", "20",
                    "--no-cpu-baseline", "--oracle-check", "1", "--host-boundary-steps", "0", "--minimizer-iterations", "0", "--extra-synthetic10m", "0", "--pmc-live", "0", "--also-fp32", "1",
                    "--solver", args.solver, "--eta", str(args.eta)]
             try:
@@ -1151,50 +1213,7 @@ def main():
                "cg_iterations": cpu_iters, "step_rel_diff_vs_gpu": parity}
         oracle.set_num_threads(1)
 
-    if rank == 0:
-        value = args.steps / elapsed
-        line = {
-            "metric": "LM trust-region steps/sec (linear-solve hot path) + JtJx SpMV HBM GB/s on BAL",
-            "value": round(value, 4), "unit": "steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(1e3 * elapsed / args.steps, 4), "higher_is_better": True,
-            "scaling": "strong", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "config": {"workload": f"{args.workload}-shaped synthetic BAL Jacobian <2,3,9>: {n_cams} cameras, {n_points} points, "
-                                   f"{n_obs} observations, " + ("N(0,1) values" if args.values == "normal" else "values = Jacobi-scaled Snavely Jacobian "
-                                   "of a synthetic scene (first LM step)") + f", seed 38401, camera popularity skew {args.skew}"
-                                   + (", values generated in HBM (torch.randn), one generator per rank" if many_cameras else ""),
-                       "solver": "CGNR + JACOBI" if args.solver == "cgnr" else "ITERATIVE_SCHUR + SCHUR_JACOBI",
-                       "step": ("LevenbergMarquardtStrategy::ComputeStep (diag(J'J), D = sqrt(diag/1e4), Solve, finite check, negate) + "
-                                "model cost change, all on the device" if args.step == "lm_step" else "LinearSolver::Solve"),
-                       "eta": args.eta, "max_num_iterations": 500, "cg_iterations_per_step": iters[-1],
-                       "termination": hs.TERMINATION_NAMES[last.termination_type],
-                       "parallelism": (f"points sharded over {world} rank(s), camera-space sums by " +
-                                       ("the one-shot peer-to-peer all-reduce (hipIpc / xGMI)" if solver.p2p_ok else "RCCL all-reduce") +
-                                       (" — ONE-GPU VALIDATION MODE, timings meaningless" if one_gpu else ""))
-                       if world > 1 else "1 GPU",
-                       "collectives_per_step": collectives_last_step if world > 1 and args.step == "lm_step" else 0,
-                       "inputs_resident_in_hbm": True, "step_finite": step_ok,
-                       "jacobian_storage": "fp32 tiles, fp64 arithmetic (accuracy mode, not parity)" if storage else "fp64",
-                       "kernel_path": "fused<2,3,9>" if info.kernel_path == hs.PATH_BAL else "generic",
-                       "camera_accumulators_in_lds": bool(info.camera_accum_in_lds)},
-            "roofline": roofline, "cpu_baseline": cpu, "oracle_check": oracle_check, "host_boundary": host_boundary, "scene_trust_region": scene_tr, "scene_step": scene_step,
-            "extra": extra,
-        }
-        if args.step == "lm_step":  # the whole step against ITS roofline: minimum bytes of all its passes / measured time / peak
-            tot_obs, tot_pts = (n_obs, n_points)
-            mb = step_min_bytes(args.solver, tot_obs, tot_pts, n_cams, int(iters[-1]), scalar_bytes)
-            line["step_roofline"] = {"bound": "hbm", "min_bytes_per_step": int(mb), "achieved": round(mb / (elapsed / args.steps) / 1e9, 1),
-                                     "peak": HBM_PEAK_GBS * world, "unit": "GB/s", "frac": round(mb / (elapsed / args.steps) / 1e9 / (HBM_PEAK_GBS * world), 4),
-                                     "what": "minimum HBM bytes of every pass of the step (J in the layout each pass wants; re-layout not counted) / ms_per_step"}
-        if roofline_other is not None:
-            line["roofline_jtjx" if args.solver == "iterative_schur" else "roofline_sx"] = roofline_other
-        # what a Ceres process with a CPU evaluator gets through the drop-in boundary (PCIe H2D of J and f every accepted step): next to
-        # `value`, which is the device-resident rate
-        line["value_host_boundary"] = None if host_boundary is None else host_boundary["steps_per_s"]
-        print(json.dumps(line), flush=True)
-    solver.close()
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
+    finish(extra, roofline, roofline_other, cpu, oracle_check, host_boundary, scene_tr, scene_step)
 
 
 if __name__ == "__main__":

@@ -9,7 +9,7 @@ for M in ${MODES:-auto 1 0}; do for C in ${CHUNKS:-64}; do
   echo "== CERES_HIP_CAM_ITEMS_MFMA=$M CERES_HIP_CAM_CHUNK_MIN=$C"
   for WL in ${WLS:-dubrovnik16 ladybug1723 venice1778}; do
     echo -n "$WL "
-    CERES_HIP_CAM_CHUNK_MIN=$C timeout 300 python bench.py --workload $WL --steps 100 --warmup 10 --no-cpu-baseline --minimizer-iterations 0 --host-boundary-steps 0 --scene-step-steps 0 --both-solvers 1 2>/dev/null \
+    CERES_HIP_CAM_CHUNK_MIN=$C timeout 300 python bench.py --full --workload $WL --steps 100 --warmup 10 --no-cpu-baseline --minimizer-iterations 0 --host-boundary-steps 0 --scene-step-steps 0 --both-solvers 1 2>/dev/null \
     | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps({'ms_per_step': d['ms_per_step'], 'cgnr': d['extra'].get('cgnr',{}).get('ms_per_step'), 'phases': d['extra']['solve_phases_ms']}))"
   done
   [ -n "$GRAPHS" ] && CERES_HIP_CAM_CHUNK_MIN=$C timeout 300 python tools/real_graph_times.py $GRAPHS 2>/dev/null | python -c "

@@ -7,6 +7,6 @@ timeout 900 python -m pytest tests -m gpu -q --timeout 300 2>&1 | grep -v "^RCCL
 for W in venice1778 ${EXTRA_WORKLOADS}; do timeout 600 python tools/kernel_times.py $W 2>/dev/null | tee -a $OUT/ktimes_$TAG.jsonl; echo; done
 STORAGE=1 timeout 600 python tools/kernel_times.py venice1778 2>/dev/null | tee -a $OUT/ktimes_$TAG.jsonl; echo
 for S in cgnr iterative_schur; do
-timeout 600 python bench.py --no-cpu-baseline --both-solvers 0 --solver $S 2>/dev/null | tee $OUT/bench_${S}_$TAG.json | python -c "
+timeout 600 python bench.py --full --no-cpu-baseline --both-solvers 0 --solver $S 2>/dev/null | tee $OUT/bench_${S}_$TAG.json | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print(d['config']['solver'], 'steps/s', d['value'], 'ms', d['ms_per_step'], 'its', d['config']['cg_iterations_per_step'], d['roofline']['frac'], d['extra']['solve_phases_ms'])"
 done

@@ -14,17 +14,17 @@ for STAGE in "$@"; do
     pytest) timeout 2400 python -m pytest tests -m gpu -q --timeout 900 -x 2>&1 | tail -60 | tee $OUT/pytest_gpu_$TAG.log | tail -15 ;;
     pytest_all) timeout 2400 python -m pytest tests -m gpu -q --timeout 900 2>&1 | tail -80 | tee $OUT/pytest_gpu_$TAG.log | tail -25 ;;
     smoke) timeout 300 python -c "import __graft_entry__ as e; e.smoke()" 2>&1 | tail -5 | tee $OUT/smoke_$TAG.log ;;
-    bench) timeout 900 python bench.py --gpus 1 2> $OUT/bench_$TAG.err | tee $OUT/bench_$TAG.json | cut -c1-1800; tail -3 $OUT/bench_$TAG.err ;;
-    bench_cgnr) timeout 900 python bench.py --gpus 1 --solver cgnr --both-solvers 0 --minimizer-iterations 0 --host-boundary-steps 0 2> $OUT/bench_cgnr_$TAG.err | tee $OUT/bench_cgnr_$TAG.json | cut -c1-1200; tail -3 $OUT/bench_cgnr_$TAG.err ;;
-    bench10m) timeout 1500 python bench.py --gpus 1 --workload synthetic10M --steps 10 --cpu-seconds 30 2> $OUT/bench_synthetic10M_fp64_$TAG.err | tee $OUT/bench_synthetic10M_fp64_$TAG.json | cut -c1-1800; tail -3 $OUT/bench_synthetic10M_fp64_$TAG.err ;;
-    bench10m_fp32) timeout 1500 python bench.py --gpus 1 --workload synthetic10M --storage fp32 --steps 10 --no-cpu-baseline 2> $OUT/bench_synthetic10M_fp32_$TAG.err | tee $OUT/bench_synthetic10M_fp32_$TAG.json | cut -c1-1500; tail -3 $OUT/bench_synthetic10M_fp32_$TAG.err ;;
-    bench1m) timeout 900 python bench.py --gpus 1 --workload synthetic1M --steps 20 --no-cpu-baseline 2> $OUT/bench_synthetic1M_$TAG.err | tee $OUT/bench_synthetic1M_$TAG.json | cut -c1-1500; tail -3 $OUT/bench_synthetic1M_$TAG.err ;;
+    bench) timeout 900 python bench.py --full --gpus 1 2> $OUT/bench_$TAG.err | tee $OUT/bench_$TAG.json | cut -c1-1800; tail -3 $OUT/bench_$TAG.err ;;
+    bench_cgnr) timeout 900 python bench.py --full --gpus 1 --solver cgnr --both-solvers 0 --minimizer-iterations 0 --host-boundary-steps 0 2> $OUT/bench_cgnr_$TAG.err | tee $OUT/bench_cgnr_$TAG.json | cut -c1-1200; tail -3 $OUT/bench_cgnr_$TAG.err ;;
+    bench10m) timeout 1500 python bench.py --full --gpus 1 --workload synthetic10M --steps 10 --cpu-seconds 30 2> $OUT/bench_synthetic10M_fp64_$TAG.err | tee $OUT/bench_synthetic10M_fp64_$TAG.json | cut -c1-1800; tail -3 $OUT/bench_synthetic10M_fp64_$TAG.err ;;
+    bench10m_fp32) timeout 1500 python bench.py --full --gpus 1 --workload synthetic10M --storage fp32 --steps 10 --no-cpu-baseline 2> $OUT/bench_synthetic10M_fp32_$TAG.err | tee $OUT/bench_synthetic10M_fp32_$TAG.json | cut -c1-1500; tail -3 $OUT/bench_synthetic10M_fp32_$TAG.err ;;
+    bench1m) timeout 900 python bench.py --full --gpus 1 --workload synthetic1M --steps 20 --no-cpu-baseline 2> $OUT/bench_synthetic1M_$TAG.err | tee $OUT/bench_synthetic1M_$TAG.json | cut -c1-1500; tail -3 $OUT/bench_synthetic1M_$TAG.err ;;
     longcg)
       for F in 0 1; do CERES_HIP_CG_FUSED=$F timeout 600 python tools/gpu_long_cg.py 30 2>&1 | tail -1 | tee -a $OUT/longcg_$TAG.jsonl; done ;;
     small)
       for WL in dubrovnik16 ladybug1723; do for F in 0 1; do
         echo -n "$WL fused=$F " | tee -a $OUT/small_$TAG.txt
-        CERES_HIP_CG_FUSED=$F timeout 600 python bench.py --workload $WL --steps 200 --warmup 20 --no-cpu-baseline --minimizer-iterations 0 --host-boundary-steps 0 2>/dev/null \
+        CERES_HIP_CG_FUSED=$F timeout 600 python bench.py --full --workload $WL --steps 200 --warmup 20 --no-cpu-baseline --minimizer-iterations 0 --host-boundary-steps 0 2>/dev/null \
           | python -c "import sys,json; d=json.loads(sys.stdin.read()); print(json.dumps({k: d[k] for k in ('ms_per_step','value')} | {'cg_its': d['config']['cg_iterations_per_step'], 'cgnr': d['extra'].get('cgnr',{}).get('ms_per_step'), 'sx_ms': d['roofline']['avg_launch_ms'], 'phases': d['extra']['solve_phases_ms']}))" | tee -a $OUT/small_$TAG.txt
       done; done ;;
     ab_mo)   # M_o written camera-major by kInit vs gathered through cam_slot (Venice shape)
@@ -83,13 +83,13 @@ PY
     bench_n2)  # the N > 1 code path of bench.py and of the library with two ranks on ONE GPU (validation only: timings meaningless)
       for WL in ${WLS:-ladybug1723 synthetic1M}; do for SV in iterative_schur cgnr; do
         echo "--- $WL $SV"
-        CERES_HIP_BENCH_ONE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --workload $WL --solver $SV --steps 5 --warmup 2 --no-cpu-baseline 2> $OUT/bench_n2_${WL}_${SV}_$TAG.err | tee $OUT/bench_n2_${WL}_${SV}_$TAG.json | cut -c1-900; tail -2 $OUT/bench_n2_${WL}_${SV}_$TAG.err
+        CERES_HIP_BENCH_ONE_GPU=1 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 2 --workload $WL --solver $SV --steps 5 --warmup 2 --no-cpu-baseline 2> $OUT/bench_n2_${WL}_${SV}_$TAG.err | tee $OUT/bench_n2_${WL}_${SV}_$TAG.json | cut -c1-900; tail -2 $OUT/bench_n2_${WL}_${SV}_$TAG.err
       done; done ;;
     rocprof1m)
       cd /tmp && export TMPDIR=/tmp
       for MIB in ${CHUNKS:-64}; do
         rm -rf /tmp/prof_1m
-        CERES_HIP_Z_CHUNK_MIB=$MIB timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_1m -o s1m -- python $REPO/bench.py --workload synthetic1M --steps 10 --warmup 2 --no-cpu-baseline --both-solvers 0 > $OUT/rocprof_bench_synthetic1M_${MIB}_$TAG.json 2> $OUT/rocprof_synthetic1M_$TAG.err
+        CERES_HIP_Z_CHUNK_MIB=$MIB timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_1m -o s1m -- python $REPO/bench.py --full --workload synthetic1M --steps 10 --warmup 2 --no-cpu-baseline --both-solvers 0 > $OUT/rocprof_bench_synthetic1M_${MIB}_$TAG.json 2> $OUT/rocprof_synthetic1M_$TAG.err
         F=$(find /tmp/prof_1m -name "*kernel_stats.csv" | head -1)
         echo "--- chunk MiB $MIB"; python -c "import json;d=json.loads(open('$OUT/rocprof_bench_synthetic1M_${MIB}_$TAG.json').read());print('sx_ms',d['roofline']['avg_launch_ms'],'step',d['ms_per_step'])"
         [ -n "$F" ] && cp $F $OUT/kernel_stats_synthetic1M_${MIB}_$TAG.csv && head -8 $F | cut -c1-160
@@ -99,7 +99,7 @@ PY
       cd /tmp && export TMPDIR=/tmp
       for WL in ladybug1723 dubrovnik16; do
         rm -rf /tmp/prof_$WL
-        timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$WL -o $WL -- python $REPO/bench.py --workload $WL --steps 200 --warmup 10 --no-cpu-baseline --both-solvers 0 --minimizer-iterations 0 --host-boundary-steps 0 > $OUT/rocprof_bench_${WL}_$TAG.json 2> $OUT/rocprof_${WL}_$TAG.err
+        timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$WL -o $WL -- python $REPO/bench.py --full --workload $WL --steps 200 --warmup 10 --no-cpu-baseline --both-solvers 0 --minimizer-iterations 0 --host-boundary-steps 0 > $OUT/rocprof_bench_${WL}_$TAG.json 2> $OUT/rocprof_${WL}_$TAG.err
         F=$(find /tmp/prof_$WL -name "*kernel_stats.csv" | head -1)
         [ -n "$F" ] && cp $F $OUT/kernel_stats_${WL}_$TAG.csv && head -22 $F | cut -c1-200
       done
@@ -108,7 +108,7 @@ PY
       cd /tmp && export TMPDIR=/tmp
       for SOLVER in iterative_schur cgnr; do
         rm -rf /tmp/prof_$SOLVER
-        timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$SOLVER -o $SOLVER -- python $REPO/bench.py --steps 20 --warmup 3 --no-cpu-baseline --both-solvers 0 --minimizer-iterations 0 --host-boundary-steps 0 --solver $SOLVER > $OUT/rocprof_bench_${SOLVER}_$TAG.json 2> $OUT/rocprof_${SOLVER}_$TAG.err
+        timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$SOLVER -o $SOLVER -- python $REPO/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --both-solvers 0 --minimizer-iterations 0 --host-boundary-steps 0 --solver $SOLVER > $OUT/rocprof_bench_${SOLVER}_$TAG.json 2> $OUT/rocprof_${SOLVER}_$TAG.err
         F=$(find /tmp/prof_$SOLVER -name "*kernel_stats.csv" | head -1)
         [ -n "$F" ] && cp $F $OUT/kernel_stats_${SOLVER}_venice_$TAG.csv && head -14 $F | cut -c1-220
       done
@@ -116,7 +116,7 @@ PY
     rocprof10m)
       cd /tmp && export TMPDIR=/tmp
       rm -rf /tmp/prof_10m
-      timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_10m -o s10m -- python $REPO/bench.py --workload synthetic10M --steps 5 --warmup 2 --no-cpu-baseline --both-solvers 1 > $OUT/rocprof_bench_synthetic10M_$TAG.json 2> $OUT/rocprof_synthetic10M_$TAG.err
+      timeout 1500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_10m -o s10m -- python $REPO/bench.py --full --workload synthetic10M --steps 5 --warmup 2 --no-cpu-baseline --both-solvers 1 > $OUT/rocprof_bench_synthetic10M_$TAG.json 2> $OUT/rocprof_synthetic10M_$TAG.err
       F=$(find /tmp/prof_10m -name "*kernel_stats.csv" | head -1)
       [ -n "$F" ] && cp $F $OUT/kernel_stats_synthetic10M_$TAG.csv && head -14 $F | cut -c1-220
       cd $REPO ;;

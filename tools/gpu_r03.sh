@@ -15,7 +15,7 @@ for STAGE in "$@"; do
       N=${STAGE#bench_n}
       for WL in ${WLS:-ladybug1723}; do for SV in iterative_schur cgnr; do
         echo "--- $WL $SV world $N"
-        CERES_HIP_BENCH_ONE_GPU=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus $N --workload $WL --solver $SV --steps 5 --warmup 2 --no-cpu-baseline 2> $OUT/bench_n${N}_${WL}_${SV}_$TAG.err | tee $OUT/bench_n${N}_${WL}_${SV}_$TAG.json | cut -c1-700; tail -2 $OUT/bench_n${N}_${WL}_${SV}_$TAG.err
+        CERES_HIP_BENCH_ONE_GPU=1 timeout 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus $N --workload $WL --solver $SV --steps 5 --warmup 2 --no-cpu-baseline 2> $OUT/bench_n${N}_${WL}_${SV}_$TAG.err | tee $OUT/bench_n${N}_${WL}_${SV}_$TAG.json | cut -c1-700; tail -2 $OUT/bench_n${N}_${WL}_${SV}_$TAG.err
       done; done ;;
     ab)   # interleaved processes, one library per process: base = the product
       echo "===== $STAGE ($(date +%T))"

@@ -15,7 +15,7 @@ for STAGE in "$@"; do
       N=${STAGE#bench_self}
       for WL in ${WLS:-ladybug1723}; do for SV in ${SVS:-iterative_schur cgnr}; do
         echo "--- $WL $SV --gpus $N (self-launched)"
-        timeout 1200 python bench.py --gpus $N --workload $WL --solver $SV --steps 3 --warmup 1 --no-cpu-baseline --oracle-check 1 2> $OUT/bench_self${N}_${WL}_${SV}_$TAG.err | tee $OUT/bench_self${N}_${WL}_${SV}_$TAG.json | python -c "
+        timeout 1200 python bench.py --full --gpus $N --workload $WL --solver $SV --steps 3 --warmup 1 --no-cpu-baseline --oracle-check 1 2> $OUT/bench_self${N}_${WL}_${SV}_$TAG.err | tee $OUT/bench_self${N}_${WL}_${SV}_$TAG.json | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1]); print({'n_gpus': d['n_gpus'], 'value': d['value'], 'parallelism': d['config']['parallelism'][:90], 'oracle_check': d.get('oracle_check')})"
         tail -2 $OUT/bench_self${N}_${WL}_${SV}_$TAG.err

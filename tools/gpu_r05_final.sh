@@ -10,7 +10,7 @@ timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG
 echo "== new tests ($(date +%T))"
 timeout 600 python -m pytest tests/test_gpu_operators.py -m gpu -q -x --timeout 300 -k "fp32" 2>&1 | grep -v "^RCCL\|^HIP ver\|^ROCm\|^Hostname\|^Librccl" | tail -6 | tee $OUT/pytest_fp32_$TAG.log
 echo "== bench ($(date +%T))"
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default_$TAG.json 2> $OUT/bench_default_$TAG.err
+timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default_$TAG.json 2> $OUT/bench_default_$TAG.err
 timeout 30 python - <<PY
 import json
 try:
@@ -24,7 +24,7 @@ cd /tmp && export TMPDIR=/tmp
 for SOLVER in iterative_schur cgnr; do
   echo "== rocprof $SOLVER ($(date +%T))"
   rm -rf /tmp/prof_$SOLVER
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$SOLVER -o $SOLVER -- python $REPO/bench.py --steps 20 --warmup 3 --no-cpu-baseline --both-solvers 0 --minimizer-iterations 0 --host-boundary-steps 0 --extra-synthetic10m 0 --extra-other-shapes 0 --extra-dense-cholesky 0 --solver $SOLVER > $OUT/bench_under_rocprof_${SOLVER}_$TAG.json 2> $OUT/rocprof_${SOLVER}_$TAG.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$SOLVER -o $SOLVER -- python $REPO/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --both-solvers 0 --minimizer-iterations 0 --host-boundary-steps 0 --extra-synthetic10m 0 --extra-other-shapes 0 --extra-dense-cholesky 0 --solver $SOLVER > $OUT/bench_under_rocprof_${SOLVER}_$TAG.json 2> $OUT/rocprof_${SOLVER}_$TAG.err
   F=$(timeout 20 find /tmp/prof_$SOLVER -name "*kernel_stats.csv" | head -1)
   if [ -n "$F" ]; then cp "$F" $OUT/kernel_stats_${SOLVER}_venice_$TAG.csv; head -8 "$F" | cut -c1-170; else echo "no kernel_stats.csv"; tail -3 $OUT/rocprof_${SOLVER}_$TAG.err; fi
 done

@@ -11,7 +11,7 @@ timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke_$TAG
 echo "== gpu tests ($(date +%T))"
 timeout 2400 python -m pytest tests -m gpu -q -x --timeout 900 2>&1 | grep -v "^RCCL\|^HIP ver\|^ROCm\|^Hostname\|^Librccl" | tail -8 | tee $OUT/pytest_gpu_$TAG.log
 echo "== bench ($(date +%T))"
-timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default_iterative_schur_$TAG.json 2> $OUT/bench_default_$TAG.err
+timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_default_iterative_schur_$TAG.json 2> $OUT/bench_default_$TAG.err
 timeout 30 python - <<PY
 import json
 try:
@@ -25,7 +25,7 @@ cd /tmp && export TMPDIR=/tmp
 for SOLVER in iterative_schur cgnr; do
   echo "== rocprof $SOLVER ($(date +%T))"
   rm -rf /tmp/prof_$SOLVER
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$SOLVER -o $SOLVER -- python $REPO/bench.py --steps 20 --warmup 3 --no-cpu-baseline --both-solvers 0 --minimizer-iterations 0 --host-boundary-steps 0 --extra-synthetic10m 0 --extra-other-shapes 0 --extra-dense-cholesky 0 --extra-real-graph 0 --extra-banded 0 --extra-configs 0 --shard-ceiling 0 --solver $SOLVER > $OUT/bench_under_rocprof_${SOLVER}_$TAG.json 2> $OUT/rocprof_${SOLVER}_$TAG.err
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$SOLVER -o $SOLVER -- python $REPO/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --both-solvers 0 --minimizer-iterations 0 --host-boundary-steps 0 --extra-synthetic10m 0 --extra-other-shapes 0 --extra-dense-cholesky 0 --extra-real-graph 0 --extra-banded 0 --extra-configs 0 --shard-ceiling 0 --solver $SOLVER > $OUT/bench_under_rocprof_${SOLVER}_$TAG.json 2> $OUT/rocprof_${SOLVER}_$TAG.err
   F=$(timeout 20 find /tmp/prof_$SOLVER -name "*kernel_stats.csv" | head -1)
   if [ -n "$F" ]; then cp "$F" $OUT/kernel_stats_${SOLVER}_venice_$TAG.csv; head -8 "$F" | cut -c1-170; else echo "no kernel_stats.csv"; tail -3 $OUT/rocprof_${SOLVER}_$TAG.err; fi
 done

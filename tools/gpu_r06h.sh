@@ -8,7 +8,7 @@ timeout 300 ceres-solver_amd/host/host_driver 2>&1 | tail -6 | cut -c1-250
 echo "== streamed upload tests ($(date +%T))"
 timeout 900 python -m pytest tests/test_gpu_streamed_upload.py -m gpu -q -x --timeout 600 2>&1 | grep -v "^RCCL\|^HIP ver\|^ROCm\|^Hostname\|^Librccl" | tail -15 | tee $OUT/pytest_$TAG.log
 echo "== bench ($(date +%T))"
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --minimizer-iterations 0 --extra-synthetic10m 0 --extra-other-shapes 0 --extra-dense-cholesky 0 --extra-real-graph 0 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; tail -3 $OUT/bench_$TAG.err
+timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline --minimizer-iterations 0 --extra-synthetic10m 0 --extra-other-shapes 0 --extra-dense-cholesky 0 --extra-real-graph 0 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; tail -3 $OUT/bench_$TAG.err
 python - <<PY
 import json
 try:

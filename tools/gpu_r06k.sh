@@ -4,7 +4,7 @@ REPO=$(cd $(dirname $0)/.. && pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT; cd $REP
 export CERES_HIP_PROBLEM_CACHE=/tmp/ceres_problem_cache
 exec < /dev/null
 echo "== bench banded ($(date +%T))"
-timeout 900 python bench.py --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --minimizer-iterations 0 --extra-synthetic10m 0 --extra-other-shapes 0 --extra-dense-cholesky 0 --extra-real-graph 0 --host-boundary-steps 0 --shard-ceiling 0 --extra-configs 0 --both-solvers 0 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; tail -2 $OUT/bench_$TAG.err
+timeout 900 python bench.py --full --gpus 1 --steps 10 --warmup 3 --no-cpu-baseline --minimizer-iterations 0 --extra-synthetic10m 0 --extra-other-shapes 0 --extra-dense-cholesky 0 --extra-real-graph 0 --host-boundary-steps 0 --shard-ceiling 0 --extra-configs 0 --both-solvers 0 > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err; tail -2 $OUT/bench_$TAG.err
 python - <<PY
 import json
 d = json.loads([l for l in open("$OUT/bench_$TAG.json").read().splitlines() if l.startswith("{")][-1])

@@ -4,7 +4,7 @@ TAG=${1:-r06o}
 REPO=$(cd $(dirname $0)/.. && pwd); OUT=$REPO/gpurun_out; mkdir -p $OUT; cd $REPO
 exec < /dev/null
 echo "== bench default ($(date +%T))"
-T0=$(date +%s); timeout 1500 python bench.py > $OUT/bench_default_$TAG.json 2> $OUT/bench_default_$TAG.err; echo "bench wall seconds: $(( $(date +%s) - T0 ))"; tail -2 $OUT/bench_default_$TAG.err
+T0=$(date +%s); timeout 1500 python bench.py --full > $OUT/bench_default_$TAG.json 2> $OUT/bench_default_$TAG.err; echo "bench wall seconds: $(( $(date +%s) - T0 ))"; tail -2 $OUT/bench_default_$TAG.err
 python - <<PY
 import json
 d = json.loads([l for l in open("$OUT/bench_default_$TAG.json").read().splitlines() if l.startswith("{")][-1])

@@ -6,7 +6,7 @@ exec < /dev/null
 for CASE in "4 synthetic1M iterative_schur" "4 synthetic1M cgnr" "8 ladybug1723 cgnr" "3 ladybug1723 iterative_schur"; do
   set -- $CASE
   echo "== --gpus $1 $2 $3 ($(date +%T))"
-  timeout 900 python bench.py --gpus $1 --workload $2 --solver $3 --steps 3 --warmup 1 --oracle-check 1 > $OUT/bench_n$1_$2_$3_r06q.json 2> $OUT/bench_n$1_$2_$3_r06q.err
+  timeout 900 python bench.py --full --gpus $1 --workload $2 --solver $3 --steps 3 --warmup 1 --oracle-check 1 > $OUT/bench_n$1_$2_$3_r06q.json 2> $OUT/bench_n$1_$2_$3_r06q.err
   python - <<PY
 import json
 try:

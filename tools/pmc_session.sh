@@ -26,7 +26,7 @@ PY
 done
 for SOLVER in cgnr iterative_schur; do
   rm -rf /tmp/prof_$SOLVER
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$SOLVER -o $SOLVER -- python $REPO/bench.py --steps 10 --warmup 2 --no-cpu-baseline --both-solvers 0 --solver $SOLVER > $OUT/rocprof_bench_$SOLVER\_$TAG.json 2> $OUT/rocprof_$SOLVER\_$TAG.err
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$SOLVER -o $SOLVER -- python $REPO/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --both-solvers 0 --solver $SOLVER > $OUT/rocprof_bench_$SOLVER\_$TAG.json 2> $OUT/rocprof_$SOLVER\_$TAG.err
   F=$(find /tmp/prof_$SOLVER -name "*kernel_stats.csv" | head -1)
   [ -n "$F" ] && cp $F $OUT/kernel_stats_${SOLVER}_$TAG.csv
 done
