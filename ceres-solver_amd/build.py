@@ -17,10 +17,12 @@ BAL_SHAPES = [(2, 0), (3, 0), (4, 0), (5, 0), (6, 0), (7, 0), (8, 0), (9, 0), (1
 BAL_SHAPES_E = [(2, 2), (2, 3), (2, 4), (2, 6), (2, 9), (4, 2), (4, 3), (4, 4), (4, 5), (4, 6), (4, 7), (4, 8), (4, 9), (4, 10)]
 # row blocks other than 2 high (round 5): (nr, ne, nf), no strip — the reference's (3,3,3), (4,4,2), (4,4,3), (4,4,4)
 BAL_SHAPES_R = [(3, 3, 3), (4, 4, 2), (4, 4, 3), (4, 4, 4)]
-SOURCES = (["plan.cc", "kernels_generic.hip", "kernels_cg.hip", "kernels_bal_common.hip"] + [f"kernels_bal_shape_f{nf}_s{ns}.hip" for nf, ns in BAL_SHAPES] +
+SOURCES = (["plan.cc", "visibility.cc", "kernels_generic.hip", "kernels_cg.hip", "kernels_bal_common.hip"] + [f"kernels_bal_shape_f{nf}_s{ns}.hip" for nf, ns in BAL_SHAPES] +
            [f"kernels_bal_shape_e{ne}_f{nf}_s0.hip" for ne, nf in BAL_SHAPES_E] +
            [f"kernels_bal_shape_r{nr}_e{ne}_f{nf}_s0.hip" for nr, ne, nf in BAL_SHAPES_R] +
-           ["kernels_schur.hip", "kernels_evaluator.hip", "kernels_quaternion.hip", "kernels_inner.hip", "kernels_dogleg.hip", "solver.hip"])
+           ["kernels_schur.hip", "kernels_cluster.hip", "kernels_evaluator.hip", "kernels_quaternion.hip", "kernels_inner.hip", "kernels_dogleg.hip", "solver.hip"])
+# visibility.cc: the clustering is compared bit-for-bit with a restatement in the tests — no contraction of a * b + c into one rounding
+EXTRA_FLAGS = {"visibility.cc": ["-ffp-contract=off"]}
 HEADERS = ["common.h", "device.h", "p2p.h", "snavely.h", "bal_evaluate.h", "robust_loss.h", "bal_frontend.inc", "inner_iterations.inc", "dogleg.inc", "solver_comm.inc", "solver_stream.inc", "solver_ops.inc", "solver_debug.inc", "kernels_bal.inc", os.path.join("..", "..", "include", "ceres_hip.h")]
 HOST_DRIVER_SRC = os.path.join(HERE, "host", "host_driver.cc")
 HOST_DRIVER = os.path.join(HERE, "host", "host_driver")
@@ -45,8 +47,8 @@ def build_library(force=False, verbose=False):
         obj = os.path.splitext(src)[0] + ".o"
         objs.append(obj)
         if force or _stale(obj, [src] + [os.path.join(CSRC, h) for h in HEADERS]):
-            cmds.append([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics",
-                         "-x", "hip", "-c", src, "-o", obj])
+            cmds.append([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics"] + EXTRA_FLAGS.get(os.path.basename(src), []) +
+                        ["-x", "hip", "-c", src, "-o", obj])
     if cmds:  # one hipcc per translation unit, a few at a time (the per-shape units take ~25 s each)
         from concurrent.futures import ThreadPoolExecutor
 

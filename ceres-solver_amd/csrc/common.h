@@ -197,7 +197,39 @@ struct SchurStorage {
   int64_t num_values() const { return pair_off.empty() ? 0 : pair_off.back(); }
   int64_t scratch_values() const { return item_off.empty() ? 0 : item_off.back(); }
 };
-void BuildSchurStorage(const HostStructure& hs, SchurStorage* out);
+// cluster_of (optional): the cluster of every F block — only pairs inside one cluster are stored (the CLUSTER_JACOBI preconditioner's
+// block pairs: VisibilityBasedPreconditioner::ComputeBlockPairsInPreconditioner, I/visibility_based_preconditioner.cc:224-303)
+void BuildSchurStorage(const HostStructure& hs, SchurStorage* out, const int32_t* cluster_of = nullptr);
+
+// ---------------------------------------------------------------------------
+// Visibility-based clustering of the F blocks (visibility.cc; no HIP; ceres_hip_debug_cluster_cameras).
+// Restates ComputeVisibility / CreateSchurComplementGraph (I/visibility.cc), ComputeCanonicalViewsClustering
+// (I/canonical_views_clustering.cc), ComputeSingleLinkageClustering (I/single_linkage_clustering.cc) and
+// VisibilityBasedPreconditioner::ClusterCameras / FlattenMembershipMap for any structure with an elimination order: every F block is
+// a "camera", its visibility the E blocks of the rows it has a cell in.  The reference walks hash sets; what that leaves open is
+// pinned here: candidates are scanned and a candidate's neighbours summed in ascending F-block index, only a strictly greater score
+// replaces the best, and the clusters are numbered by ascending first member.
+// ---------------------------------------------------------------------------
+struct VisibilityGraph {   // symmetric, self edges of weight 1 included; neighbours ascending
+  std::vector<int64_t> ptr;      // n + 1
+  std::vector<int32_t> nbr;
+  std::vector<double> weight;
+};
+void BuildVisibilityGraph(const HostStructure& hs, VisibilityGraph* g);
+struct CanonicalViewsOptions { double size_penalty_weight = 3.0, similarity_penalty_weight = 0.0, view_score_weight = 0.0; int min_views = 3; };
+// centers in the order chosen; view_center[v] = index into centers of the centre that claimed v, -1: none.  vertex_weight may be null (1.0).
+void CanonicalViews(const VisibilityGraph& g, const CanonicalViewsOptions& o, const double* vertex_weight, std::vector<int32_t>* centers,
+                    std::vector<int32_t>* view_center);
+// membership[f] in [0, *num_clusters); clustering_type: CERES_HIP_CANONICAL_VIEWS / CERES_HIP_SINGLE_LINKAGE.  Returns "" or an error.
+std::string ClusterCameras(const HostStructure& hs, int clustering_type, std::vector<int32_t>* membership, int* num_clusters);
+// The scalar layout of the cluster factors: cluster k owns scalars [cl_off[k], cl_off[k + 1]) of the permuted F space, its F blocks in
+// ascending order; perm[q] = the F-space scalar at permuted position q; block_loc[f] = first scalar of block f inside its cluster.
+struct ClusterLayoutHost {
+  int num_clusters = 0, largest = 0;
+  std::vector<int32_t> block_cluster, block_loc, perm, cl_off;
+  std::vector<int64_t> mat_off;   // num_clusters + 1: cluster k's dim x dim row-major matrix
+};
+void BuildClusterLayout(const HostStructure& hs, const std::vector<int32_t>& membership, int num_clusters, ClusterLayoutHost* out);
 
 // Fills hs from the ABI structure; returns "" or an error message.
 std::string AnalyzeStructure(const ceres_hip_block_structure& bs, int nelim, HostStructure* hs);

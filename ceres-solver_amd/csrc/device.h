@@ -391,6 +391,29 @@ hipError_t LaunchSchurSparseDiag(const GenStructure& G, const SchurPairs& P, con
 hipError_t LaunchDenseCholesky(double* A, int n, int* fail_flag, hipStream_t stream);
 hipError_t LaunchDenseCholeskySolve(const double* A, int n, double* x, hipStream_t stream);
 
+// ---- CLUSTER_JACOBI (kernels_cluster.hip): one dense factor per cluster of F blocks ------------------
+// Clusters of at most kClusterLdsDim scalars are factored and applied one workgroup per cluster with the matrix in LDS
+// (128 x 129 doubles = 129 KiB of the CU's 160); larger ones go through LaunchDenseCholesky / LaunchDenseCholeskySolve.
+constexpr int kClusterLdsDim = 128;
+struct ClusterLayout {   // device image of ClusterLayoutHost (common.h)
+  int num_clusters = 0, n = 0;   // n = num_cols_f
+  const int32_t *perm = nullptr, *cl_off = nullptr, *block_cluster = nullptr, *block_loc = nullptr;
+  const int64_t* mat_off = nullptr;
+  const int32_t* small_list = nullptr;   // the clusters of at most kClusterLdsDim scalars
+  int n_small = 0, small_max_dim = 0;
+};
+// mats (zeroed by the caller) <- the stored blocks of the cluster pairs, both triangles of every cluster's matrix
+hipError_t LaunchClusterAssemble(const GenStructure& G, const SchurPairs& P, const ClusterLayout& C, const double* S, int64_t total,
+                                 double* mats, hipStream_t stream);
+// in-place Cholesky of the small clusters (L in the lower triangle); a pivot that is not positive raises *fail_flag
+hipError_t LaunchClusterFactorSmall(const ClusterLayout& C, double* mats, int* fail_flag, hipStream_t stream);
+// y[perm] = (L L^T)^-1 x[perm] over the small clusters; status: CG status word (no-op once it is non-zero), may be nullptr
+hipError_t LaunchClusterSolveSmall(const ClusterLayout& C, const double* mats, const double* x, double* y, const int* status,
+                                   hipStream_t stream);
+// xc[q] = x[perm[q]] / y[perm[q]] = xc[q] for q in [q0, q0 + len)
+hipError_t LaunchClusterGather(const int32_t* perm, int q0, int len, const double* x, double* xc, hipStream_t stream);
+hipError_t LaunchClusterScatter(const int32_t* perm, int q0, int len, const double* xc, double* y, hipStream_t stream);
+
 // ---- vector kernels + device-resident CG (kernels_cg.hip) ------------------
 hipError_t LaunchSet(double* x, double v, int64_t n, hipStream_t stream);
 hipError_t LaunchAxpby(double a, const double* x, double b, const double* y, double* z, int64_t n, hipStream_t stream);

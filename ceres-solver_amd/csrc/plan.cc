@@ -887,7 +887,7 @@ void BuildBalPlan(const HostStructure& h, int reorder_mode, const HybridRequest&
   P.eligible = true;
 }
 
-void BuildSchurStorage(const HostStructure& h, SchurStorage* out) {
+void BuildSchurStorage(const HostStructure& h, SchurStorage* out, const int32_t* cluster_of) {
   SchurStorage& S = *out;
   S = SchurStorage();
   S.nf = h.ncb - h.nelim;
@@ -900,6 +900,7 @@ void BuildSchurStorage(const HostStructure& h, SchurStorage* out) {
   auto add = [&](int e, int k1, int k2) {
     const int b1 = h.ccol[k1] - h.nelim, b2 = h.ccol[k2] - h.nelim;
     if (b1 > b2) return;  // upper block triangle only (I/schur_eliminator_impl.h:548-565); equal blocks keep both orders
+    if (cluster_of && cluster_of[b1] != cluster_of[b2]) return;   // CLUSTER_JACOBI: the pair is not in the preconditioner
     trips.push_back({int64_t(b1) * nf + b2, e, k1, k2});
   };
   std::vector<int32_t> cells;

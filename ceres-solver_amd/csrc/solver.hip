@@ -173,6 +173,18 @@ struct ceres_hip_solver {
   SchurStorage schur_storage;
   SchurPairs schur_pairs;
   bool precond_valid = false;
+  // CLUSTER_JACOBI (ITERATIVE_SCHUR only, one rank): the F blocks clustered by visibility (visibility.cc), the block pairs inside a
+  // cluster in the explicit solver's block-sparse storage (the same gather elimination), one dense matrix per cluster (d_Cmat:
+  // factored in place, L in the lower triangle) and the cluster permutation.  Clusters above kClusterLdsDim scalars are listed in
+  // cluster_large and go through the dense Cholesky kernels one by one.
+  ClusterLayoutHost cluster_host;
+  ClusterLayout cluster;
+  SchurStorage cluster_storage;
+  SchurPairs cluster_pairs;
+  std::vector<int32_t> cluster_large;
+  double *d_Cblk = nullptr, *d_Cmat = nullptr, *d_Cvec = nullptr;
+  bool cluster_valid = false;
+  double cluster_setup_seconds = 0.0;
   // SCHUR_POWER_SERIES_EXPANSION: blockdiag(F^T F + D_f^2)^-1 and two F-space temporaries
   double *ftf_inv = nullptr, *spse_a = nullptr, *spse_b = nullptr;
   bool ftf_inv_valid = false;
@@ -393,6 +405,8 @@ int require_caller_values(ceres_hip_solver* s, const char* what) {
 bool is_dense_schur(const ceres_hip_solver* s) { return s->opt.solver_type == CERES_HIP_DENSE_SCHUR; }
 // solvers built on the E | F partition (ImplicitSchurComplement / SchurEliminator state, camera-space CG vectors)
 bool is_schur(const ceres_hip_solver* s) { return s->opt.solver_type == CERES_HIP_ITERATIVE_SCHUR || is_dense_schur(s); }
+// (DENSE_SCHUR ignores the preconditioner field)
+bool is_cluster_jacobi(const ceres_hip_solver* s) { return s->opt.solver_type == CERES_HIP_ITERATIVE_SCHUR && s->opt.preconditioner_type == CERES_HIP_CLUSTER_JACOBI; }
 
 // ---------------------------------------------------------------------------
 // Operators.  All take device pointers and enqueue on s->stream.
@@ -1467,6 +1481,83 @@ int check_factorization(ceres_hip_solver* s, bool* failed) {
   return 0;
 }
 
+// ---- CLUSTER_JACOBI --------------------------------------------------------------------------------------------------------------
+// VisibilityBasedPreconditioner::UpdateImpl (I/visibility_based_preconditioner.cc:322-380) after op_schur_init: SchurEliminator::Eliminate
+// into the cluster pairs (the gather of the explicit solver: caller-layout values, dense point inverses), the blocks scattered into one
+// dense matrix per cluster, one Cholesky per cluster.  *failed: a pivot was not positive (read back: one synchronisation).
+int cluster_jacobi_eliminate(ceres_hip_solver* s) {
+  hipStream_t st = s->stream;
+  TRY(require_caller_values(s, "CLUSTER_JACOBI"));
+  const double* ei = s->etei;
+  if (s->path == CERES_HIP_PATH_BAL) {  // packed point inverses (internal point order) -> the dense E-block store the eliminator reads
+    HIP_TRY(s, LaunchExpandSym(s->etei, s->ops->ne, s->ops->etei_pitch, s->etei_dense, s->d_pt_eoff, s->plan.n_points, st));
+    ei = s->etei_dense;
+  }
+  HIP_TRY(s, LaunchSchurSparseEliminate(s->G, s->cluster_pairs, s->values, ei, s->D, s->d_Cblk, st));
+  return 0;
+}
+int cluster_jacobi_assemble_and_factor(ceres_hip_solver* s) {
+  hipStream_t st = s->stream;
+  const int64_t mat_values = s->cluster_host.mat_off.back();
+  HIP_TRY(s, hipMemsetAsync(s->d_Cmat, 0, sizeof(double) * size_t(mat_values), st));
+  HIP_TRY(s, LaunchClusterAssemble(s->G, s->cluster_pairs, s->cluster, s->d_Cblk, s->cluster_storage.num_values(), s->d_Cmat, st));
+  if (!s->fail_flag_clean) HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
+  s->fail_flag_clean = false;
+  HIP_TRY(s, LaunchClusterFactorSmall(s->cluster, s->d_Cmat, s->d_fail_flag, st));
+  for (int k : s->cluster_large)
+    HIP_TRY(s, LaunchDenseCholesky(s->d_Cmat + s->cluster_host.mat_off[k], s->cluster_host.cl_off[k + 1] - s->cluster_host.cl_off[k], s->d_fail_flag, st));
+  return 0;
+}
+int op_cluster_jacobi_update(ceres_hip_solver* s, bool* failed) {
+  *failed = false;
+  s->cluster_valid = false;
+  TRY(cluster_jacobi_eliminate(s));
+  TRY(cluster_jacobi_assemble_and_factor(s));
+  TRY(check_factorization(s, failed));
+  s->cluster_valid = !*failed;
+  return 0;
+}
+// out = M^-1 in (both F-space device vectors, distinct): two triangular solves per cluster
+int op_cluster_jacobi_apply(ceres_hip_solver* s, const double* in, double* out, const int* status) {
+  hipStream_t st = s->stream;
+  const ClusterLayoutHost& L = s->cluster_host;
+  HIP_TRY(s, LaunchClusterSolveSmall(s->cluster, s->d_Cmat, in, out, status, st));
+  for (int k : s->cluster_large) {
+    const int q0 = L.cl_off[k], dim = L.cl_off[k + 1] - q0;
+    HIP_TRY(s, LaunchClusterGather(s->cluster.perm, q0, dim, in, s->d_Cvec, st));
+    HIP_TRY(s, LaunchDenseCholeskySolve(s->d_Cmat + L.mat_off[k], dim, s->d_Cvec + q0, st));
+    HIP_TRY(s, LaunchClusterScatter(s->cluster.perm, q0, dim, s->d_Cvec, out, st));
+  }
+  return 0;
+}
+
+// device image of a SchurStorage (+ the scratch of its work items)
+int upload_schur_pairs(ceres_hip_solver* s, const SchurStorage& Q, SchurPairs* out) {
+  SchurPairs& P = *out;
+  P.npairs = int(Q.pair_i.size());
+  int32_t* q32 = nullptr; int64_t* q64 = nullptr;
+  TRY(dev_upload(s, &q32, Q.pair_i)); P.pair_i = q32;
+  TRY(dev_upload(s, &q32, Q.pair_j)); P.pair_j = q32;
+  TRY(dev_upload(s, &q32, Q.row_ptr)); P.row_ptr = q32;
+  TRY(dev_upload(s, &q32, Q.col_ptr)); P.col_ptr = q32;
+  TRY(dev_upload(s, &q32, Q.col_pair)); P.col_pair = q32;
+  TRY(dev_upload(s, &q64, Q.pair_off)); P.pair_off = q64;
+  TRY(dev_upload(s, &q64, Q.trip_ptr)); P.trip_ptr = q64;
+  TRY(dev_upload(s, &q32, Q.trip_e)); P.trip_e = q32;
+  TRY(dev_upload(s, &q32, Q.trip_k1)); P.trip_k1 = q32;
+  TRY(dev_upload(s, &q32, Q.trip_k2)); P.trip_k2 = q32;
+  TRY(dev_upload(s, &q32, Q.cell_row)); P.cell_row = q32;
+  P.n_items = int(Q.item_pair.size());
+  P.total_values = Q.num_values();
+  TRY(dev_upload(s, &q32, Q.item_pair)); P.item_pair = q32;
+  TRY(dev_upload(s, &q32, Q.pair_item_ptr)); P.pair_item_ptr = q32;
+  TRY(dev_upload(s, &q64, Q.item_t0)); P.item_t0 = q64;
+  TRY(dev_upload(s, &q64, Q.item_t1)); P.item_t1 = q64;
+  TRY(dev_upload(s, &q64, Q.item_off)); P.item_off = q64;
+  { double* sc = nullptr; TRY(dev_alloc(s, &sc, std::max<size_t>(1, size_t(Q.scratch_values())))); P.scratch = sc; }
+  return 0;
+}
+
 int require_loaded(ceres_hip_solver* s) {
   if (!s) return CERES_HIP_E_INVALID;
   if (!s->have_structure) return fail(s, CERES_HIP_E_INVALID, "ceres_hip_set_structure has not been called");
@@ -1482,6 +1573,7 @@ int load_device(ceres_hip_solver* s, const double* dv, const double* db, const d
   s->have_b = db != nullptr;
   s->have_D = dD != nullptr;
   s->precond_valid = false;
+  s->cluster_valid = false;
   s->ftf_inv_valid = false;
   s->packed = false;  // the tiles are (re)built by the first kernel that walks J, or by ensure_packed()
   s->tiles_only = false;
@@ -1497,6 +1589,7 @@ int load_device(ceres_hip_solver* s, const double* dv, const double* db, const d
 // The packed tiles, the remainder rows' blocks and the loaded pointers stay.
 void keep_loaded_values(ceres_hip_solver* s) {
   s->precond_valid = false;
+  s->cluster_valid = false;   // (the factor contains D_f^2: a retry with another radius refactors)
   s->ftf_inv_valid = false;
   s->D_int_valid = false;
 }
@@ -1560,6 +1653,7 @@ int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x
   // ImplicitSchurComplement::Init / Preconditioner::Update do on every Solve.
   s->ftf_inv_valid = false;
   s->precond_valid = false;
+  s->cluster_valid = false;
   // finite-step flag + factorization flag, adjacent.  Fused path: the solve's first pass clears them itself (BalArgs::clear_flags:
   // op_schur_init / op_cgnr_setup_bal, which every fused solve starts with) — no fill command in front of it
   s->clear_flags_pending = s->path == CERES_HIP_PATH_BAL && s->ops != nullptr;
@@ -1739,7 +1833,15 @@ int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x
     // On the fused path the factorization flag of the preconditioner blocks is not read back here
     // (a host round trip in front of CG): the CG init kernel looks at it and starts in kCgSetupFailed.
     const bool defer_check = s->path == CERES_HIP_PATH_BAL;
-    if (pre != CERES_HIP_IDENTITY && !spse_pre) {
+    const bool cluster_pre = pre == CERES_HIP_CLUSTER_JACOBI;
+    if (cluster_pre) {
+      TRY(op_cluster_jacobi_update(s, &bad));
+      if (bad) {  // Preconditioner::Update returned false, :113-121
+        summary->termination_type = CERES_HIP_FAILURE;
+        snprintf(summary->message, sizeof(summary->message), "Preconditioner update failed.");
+        return 0;
+      }
+    } else if (pre != CERES_HIP_IDENTITY && !spse_pre) {
       TRY(op_preconditioner(s, pre, s->precond, true));
       if (!defer_check) {
         TRY(check_factorization(s, &bad));
@@ -1771,7 +1873,7 @@ int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x
     spec.nblocks = h.ncb - h.nelim;
     spec.col_begin = h.num_cols_e;
     spec.diag_off = s->G.diag_off_f;
-    spec.blocks = (pre == CERES_HIP_IDENTITY || spse_pre) ? nullptr : s->precond;
+    spec.blocks = (pre == CERES_HIP_IDENTITY || spse_pre || cluster_pre) ? nullptr : s->precond;
     if (cg_tail_possible(s) && spec.blocks) {
       // a camera space this small: the S.x pass finishes the CG iteration itself (one launch instead of four)
       spec.iteration = [s, status](int it) -> int {
@@ -1794,6 +1896,8 @@ int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x
     if (defer_check && spec.blocks) spec.setup_fail = s->d_fail_flag;
     if (spse_pre)  // tolerance 0: the preconditioner must stay fixed during CG (:178-186)
       spec.precondition = [s, spse_iters, status](const double* in, double* out) { return op_spse_apply(s, in, out, spse_iters, 0.0, status); };
+    if (cluster_pre)   // not block diagonal over the F blocks: CG takes it as an operator (the five-kernel iteration, no one-launch tail)
+      spec.precondition = [s, status](const double* in, double* out) { return op_cluster_jacobi_apply(s, in, out, status); };
     if (s->opt.use_spse_initialization) {  // :97-111
       TRY(op_spse_apply(s, s->rhs_f, s->cg.x, spse_iters, s->opt.spse_tolerance, nullptr));
       spec.x0_nonzero = true;
@@ -1949,7 +2053,7 @@ ceres_hip_solver* ceres_hip_create(const ceres_hip_options* o) {
   const bool pre_ok = o->solver_type == CERES_HIP_DENSE_SCHUR ? true  // a direct solver: the field is ignored
                       : o->solver_type == CERES_HIP_CGNR ? (pre == CERES_HIP_IDENTITY || pre == CERES_HIP_JACOBI)
                                                        : (pre == CERES_HIP_IDENTITY || pre == CERES_HIP_JACOBI || pre == CERES_HIP_SCHUR_JACOBI ||
-                                                          pre == CERES_HIP_SCHUR_POWER_SERIES_EXPANSION);
+                                                          pre == CERES_HIP_SCHUR_POWER_SERIES_EXPANSION || pre == CERES_HIP_CLUSTER_JACOBI);
   if (!pre_ok) {  // CgnrSolver's ctor LOG(FATAL)s on the same condition, I/cgnr_solver.cc:119-128
     fail(nullptr, CERES_HIP_E_UNSUPPORTED, "preconditioner_type %d is not available for solver_type %d", pre, o->solver_type);
     return nullptr;
@@ -1963,6 +2067,11 @@ ceres_hip_solver* ceres_hip_create(const ceres_hip_options* o) {
       fail(nullptr, CERES_HIP_E_UNSUPPORTED, "Only SCHUR_JACOBI is supported with use_explicit_schur_complement");
       return nullptr;
     }
+  }
+  if (o->solver_type == CERES_HIP_ITERATIVE_SCHUR && pre == CERES_HIP_CLUSTER_JACOBI &&
+      o->visibility_clustering_type != CERES_HIP_CANONICAL_VIEWS && o->visibility_clustering_type != CERES_HIP_SINGLE_LINKAGE) {
+    fail(nullptr, CERES_HIP_E_INVALID, "visibility_clustering_type %d is not CANONICAL_VIEWS (0) or SINGLE_LINKAGE (1)", o->visibility_clustering_type);
+    return nullptr;
   }
   if (o->jacobian_storage != 0 && o->jacobian_storage != 1) {
     fail(nullptr, CERES_HIP_E_INVALID, "jacobian_storage must be 0 (fp64) or 1 (fp32 tiles)");
@@ -2054,6 +2163,8 @@ int ceres_hip_set_structure(ceres_hip_solver* s, const ceres_hip_block_structure
 static int set_structure_impl(ceres_hip_solver* s, const ceres_hip_block_structure* bs) {
   HIP_TRY(s, hipSetDevice(s->opt.device));
   if (s->have_structure) return fail(s, CERES_HIP_E_INVALID, "structure already set: one instance sees one sparsity (I/linear_solver.h:137-142)");
+  if (is_cluster_jacobi(s) && s->world > 1)   // (before any collective: every rank holds the same options)
+    return fail(s, CERES_HIP_E_UNSUPPORTED, "the CLUSTER_JACOBI preconditioner is not available on a sharded instance (world_size %d)", s->world);
   const int nelim = s->opt.num_eliminate_blocks;
   std::string e = AnalyzeStructure(*bs, nelim, &s->hs);
   if (!e.empty()) return fail(s, CERES_HIP_E_INVALID, "invalid block structure: %s", e.c_str());
@@ -2213,30 +2324,44 @@ static int set_structure_impl(ceres_hip_solver* s, const ceres_hip_block_structu
   if (s->sparse_S || s->dense_from_blocks) {
     SchurStorage& Q = s->schur_storage;
     BuildSchurStorage(h, &Q);
-    SchurPairs& P = s->schur_pairs;
-    P.npairs = int(Q.pair_i.size());
-    int32_t* q32 = nullptr; int64_t* q64 = nullptr;
-    TRY(dev_upload(s, &q32, Q.pair_i)); P.pair_i = q32;
-    TRY(dev_upload(s, &q32, Q.pair_j)); P.pair_j = q32;
-    TRY(dev_upload(s, &q32, Q.row_ptr)); P.row_ptr = q32;
-    TRY(dev_upload(s, &q32, Q.col_ptr)); P.col_ptr = q32;
-    TRY(dev_upload(s, &q32, Q.col_pair)); P.col_pair = q32;
-    TRY(dev_upload(s, &q64, Q.pair_off)); P.pair_off = q64;
-    TRY(dev_upload(s, &q64, Q.trip_ptr)); P.trip_ptr = q64;
-    TRY(dev_upload(s, &q32, Q.trip_e)); P.trip_e = q32;
-    TRY(dev_upload(s, &q32, Q.trip_k1)); P.trip_k1 = q32;
-    TRY(dev_upload(s, &q32, Q.trip_k2)); P.trip_k2 = q32;
-    TRY(dev_upload(s, &q32, Q.cell_row)); P.cell_row = q32;
-    P.n_items = int(Q.item_pair.size());
-    P.total_values = Q.num_values();
-    TRY(dev_upload(s, &q32, Q.item_pair)); P.item_pair = q32;
-    TRY(dev_upload(s, &q32, Q.pair_item_ptr)); P.pair_item_ptr = q32;
-    TRY(dev_upload(s, &q64, Q.item_t0)); P.item_t0 = q64;
-    TRY(dev_upload(s, &q64, Q.item_t1)); P.item_t1 = q64;
-    TRY(dev_upload(s, &q64, Q.item_off)); P.item_off = q64;
-    { double* sc = nullptr; TRY(dev_alloc(s, &sc, std::max<size_t>(1, size_t(Q.scratch_values())))); P.scratch = sc; }
+    TRY(upload_schur_pairs(s, Q, &s->schur_pairs));
     TRY(dev_alloc(s, s->sparse_S ? &s->d_S : &s->d_Sblk, std::max<size_t>(1, size_t(Q.num_values()))));
     if (s->dense_from_blocks && s->path == CERES_HIP_PATH_BAL) TRY(dev_alloc(s, &s->etei_dense, size_t(h.diag_off_e.back())));
+  }
+  if (is_cluster_jacobi(s) && h.ncb - h.nelim > 0) {
+    // host analysis: clustering, the block pairs inside a cluster, the permutation that makes a cluster's scalars contiguous
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<int32_t> membership;
+    int num_clusters = 0;
+    const std::string err = ClusterCameras(h, s->opt.visibility_clustering_type, &membership, &num_clusters);
+    if (!err.empty()) return fail(s, CERES_HIP_E_INVALID, "%s", err.c_str());
+    BuildClusterLayout(h, membership, num_clusters, &s->cluster_host);
+    BuildSchurStorage(h, &s->cluster_storage, membership.data());
+    s->cluster_setup_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    const ClusterLayoutHost& L = s->cluster_host;
+    TRY(upload_schur_pairs(s, s->cluster_storage, &s->cluster_pairs));
+    ClusterLayout& C = s->cluster;
+    C = ClusterLayout();
+    C.num_clusters = num_clusters; C.n = h.num_cols_f;
+    int32_t* q32 = nullptr; int64_t* q64 = nullptr;
+    TRY(dev_upload(s, &q32, L.perm)); C.perm = q32;
+    TRY(dev_upload(s, &q32, L.cl_off)); C.cl_off = q32;
+    TRY(dev_upload(s, &q32, L.block_cluster)); C.block_cluster = q32;
+    TRY(dev_upload(s, &q32, L.block_loc)); C.block_loc = q32;
+    TRY(dev_upload(s, &q64, L.mat_off)); C.mat_off = q64;
+    std::vector<int32_t> small;
+    s->cluster_large.clear();
+    for (int k = 0; k < num_clusters; ++k) {
+      const int dim = L.cl_off[k + 1] - L.cl_off[k];
+      if (dim <= kClusterLdsDim) { small.push_back(k); C.small_max_dim = std::max(C.small_max_dim, dim); }
+      else s->cluster_large.push_back(k);
+    }
+    C.n_small = int(small.size());
+    TRY(dev_upload(s, &q32, small)); C.small_list = q32;
+    TRY(dev_alloc(s, &s->d_Cblk, std::max<size_t>(1, size_t(s->cluster_storage.num_values()))));
+    TRY(dev_alloc(s, &s->d_Cmat, std::max<size_t>(1, size_t(L.mat_off.back()))));
+    TRY(dev_alloc(s, &s->d_Cvec, std::max<size_t>(1, size_t(h.num_cols_f))));
+    if (s->path == CERES_HIP_PATH_BAL) TRY(dev_alloc(s, &s->etei_dense, size_t(h.diag_off_e.back())));
   }
   const int64_t cg_n = is_schur(s) ? h.num_cols_f : h.num_cols;
   TRY(dev_alloc(s, &s->cg.x, size_t(cg_n)));
@@ -2496,7 +2621,7 @@ int ceres_hip_get_info(const ceres_hip_solver* s, ceres_hip_info* info) {
     info->points_renumbered = s->plan.renumbered ? 1 : 0;
     // (the same condition solve_loaded applies: a block-diagonal preconditioner — not IDENTITY, not the power-series operator)
     info->cg_iteration_in_operator = (cg_tail_possible(s) && s->opt.preconditioner_type != CERES_HIP_IDENTITY &&
-                                      s->opt.preconditioner_type != CERES_HIP_SCHUR_POWER_SERIES_EXPANSION) ? 1 : 0;
+                                      s->opt.preconditioner_type != CERES_HIP_SCHUR_POWER_SERIES_EXPANSION && !is_cluster_jacobi(s)) ? 1 : 0;
   }
   return 0;
 }
@@ -2620,7 +2745,8 @@ int lm_step_loaded(ceres_hip_solver* s, const ceres_hip_lm_options* o, double* d
   const bool fresh = !o->reuse_diagonal || !s->have_lm_diag;
   // (DENSE_SCHUR forms no preconditioner blocks: nobody would form the camera part of a fused diagonal)
   // (a shared strip's column norms are not formed by the set-up kernels: such shapes take the separate column-norm pass)
-  s->lm_fuse_active = fresh && s->path == CERES_HIP_PATH_BAL && s->opt.preconditioner_type != CERES_HIP_IDENTITY && !is_dense_schur(s) && s->plan.ns == 0;
+  s->lm_fuse_active = fresh && s->path == CERES_HIP_PATH_BAL && s->opt.preconditioner_type != CERES_HIP_IDENTITY && !is_dense_schur(s) && s->plan.ns == 0 &&
+                      !is_cluster_jacobi(s);   // (the cluster factor is formed by the gather elimination, which reads a finished D)
   s->lm_opts = *o;
   if (fresh && !s->lm_fuse_active) TRY(op_squared_column_norm(s, s->lm_diag));
   if (!s->lm_fuse_active)
@@ -2636,7 +2762,7 @@ int lm_step_loaded(ceres_hip_solver* s, const ceres_hip_lm_options* o, double* d
   s->lm_cgnr_copy_pending = false;
   // (rows outside the tiles add ungated generic launches to the ITERATIVE_SCHUR tail: no speculation then)
   // (sharded: ITERATIVE_SCHUR where every rank can — the tail then holds one exchange per poll, which all ranks must issue alike)
-  s->lm_speculate = s->speculate && s->lm_negate_in_solve &&
+  s->lm_speculate = s->speculate && s->lm_negate_in_solve && !is_cluster_jacobi(s) &&
                     (s->world <= 1 ? (!is_schur(s) || (s->lm_want_model_cost && !has_remainder(s))) : (is_schur(s) && s->spec_agreed && s->p2p && s->lm_want_model_cost));
   s->spec_tail_done = false;
   const int rc = solve_loaded(s, o->eta, -1.0, dx, &res->linear_solver);
@@ -2917,6 +3043,19 @@ int ceres_hip_time_op(ceres_hip_solver* s, int32_t op, int32_t iters, double* av
       if (s->path != CERES_HIP_PATH_BAL) return fail(s, CERES_HIP_E_INVALID, "read-stream probe uses the packed tiles of the <2,3,9> path");
       body = [&] { HIP_TRY(s, s->ops->stream_probe(s->d_J, s->plan.n_tiles, std::min(s->num_cus, s->plan.nf * s->plan.n_cameras), s->d_global_acc, st)); return 0; };
       break;
+    case CERES_HIP_TIMED_CLUSTER_ELIMINATE:
+    case CERES_HIP_TIMED_CLUSTER_FACTOR:
+    case CERES_HIP_TIMED_CLUSTER_APPLY: {
+      if (!is_cluster_jacobi(s) || h.ncb - h.nelim <= 0) return fail(s, CERES_HIP_E_INVALID, "needs an ITERATIVE_SCHUR instance with CLUSTER_JACOBI");
+      TRY(op_schur_init(s, false));
+      bool failed = false;
+      TRY(op_cluster_jacobi_update(s, &failed));
+      if (failed) return fail(s, CERES_HIP_E_INVALID, "Preconditioner update failed.");
+      if (op == CERES_HIP_TIMED_CLUSTER_ELIMINATE) body = [&] { return cluster_jacobi_eliminate(s); };
+      else if (op == CERES_HIP_TIMED_CLUSTER_FACTOR) body = [&] { return cluster_jacobi_assemble_and_factor(s); };   // (re-assembled from the blocks every time)
+      else body = [&] { return op_cluster_jacobi_apply(s, s->cg.p, s->cg.z, nullptr); };
+      break;
+    }
     default:
       return fail(s, CERES_HIP_E_INVALID, "unknown timed op %d", op);
   }

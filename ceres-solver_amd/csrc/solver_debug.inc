@@ -27,6 +27,23 @@ int ceres_hip_debug_staged_x_plan(const ceres_hip_block_structure* bs, int32_t n
   } catch (...) { return CERES_HIP_E_INVALID; }   // (host allocations sized by the caller's structure: no C++ exception crosses the C boundary)
 }
 
+// the clustering set_structure computes for CLUSTER_JACOBI (visibility.cc)
+int ceres_hip_debug_cluster_cameras(const ceres_hip_block_structure* bs, int32_t num_eliminate_blocks, int32_t visibility_clustering_type,
+                                    int32_t* membership, int32_t* num_clusters) {
+  try {
+  if (!bs || !membership || !num_clusters) return CERES_HIP_E_INVALID;
+  HostStructure h;
+  if (!AnalyzeStructure(*bs, num_eliminate_blocks, &h).empty()) return CERES_HIP_E_INVALID;
+  if (num_eliminate_blocks <= 0 || !h.chunks_contiguous) return CERES_HIP_E_INVALID;
+  std::vector<int32_t> m;
+  int n = 0;
+  if (!ClusterCameras(h, visibility_clustering_type, &m, &n).empty()) return CERES_HIP_E_INVALID;
+  for (size_t f = 0; f < m.size(); ++f) membership[f] = m[f];
+  *num_clusters = n;
+  return 0;
+  } catch (...) { return CERES_HIP_E_INVALID; }
+}
+
 int ceres_hip_debug_plan(const ceres_hip_block_structure* bs, int32_t num_eliminate_blocks, int32_t* eligible,
                          int64_t* n_tiles, int32_t* slot_row_out, int32_t* slot_cam_out, int32_t* slot_pt_out,
                          uint32_t* slot_seg_out, int32_t* tile_kind_out, int32_t* tile_aux_out, int64_t slot_capacity,

@@ -232,9 +232,34 @@ int ceres_hip_op_schur_jacobi_update(ceres_hip_solver* s) {
   return 0;
 }
 
+int ceres_hip_op_cluster_jacobi_update(ceres_hip_solver* s) {
+  TRY(require_loaded(s));
+  HIP_TRY(s, hipSetDevice(s->opt.device));
+  if (!is_cluster_jacobi(s)) return fail(s, CERES_HIP_E_INVALID, "the handle was not created with the CLUSTER_JACOBI preconditioner");
+  if (s->hs.ncb - s->hs.nelim <= 0) return fail(s, CERES_HIP_E_INVALID, "the structure has no F block");
+  TRY(op_schur_init(s, false));
+  bool failed = false;
+  TRY(op_cluster_jacobi_update(s, &failed));
+  if (failed) return fail(s, CERES_HIP_E_INVALID, "Preconditioner update failed.");
+  return 0;
+}
+
+int ceres_hip_cluster_jacobi_stats(const ceres_hip_solver* s, int32_t* num_clusters, int32_t* largest_cluster_dimension, int64_t* factor_bytes,
+                                   double* setup_seconds) {
+  if (!s) return CERES_HIP_E_INVALID;
+  if (!s->have_structure || !is_cluster_jacobi(s)) return CERES_HIP_E_INVALID;
+  const ClusterLayoutHost& L = s->cluster_host;
+  if (num_clusters) *num_clusters = L.num_clusters;
+  if (largest_cluster_dimension) *largest_cluster_dimension = L.largest;
+  if (factor_bytes) *factor_bytes = L.mat_off.empty() ? 0 : int64_t(sizeof(double)) * L.mat_off.back();
+  if (setup_seconds) *setup_seconds = s->cluster_setup_seconds;
+  return 0;
+}
+
 int ceres_hip_get_preconditioner_blocks(ceres_hip_solver* s, int32_t not_inverted, double* blocks, int64_t capacity) {
   TRY(require_loaded(s));
   HIP_TRY(s, hipSetDevice(s->opt.device));
+  if (is_cluster_jacobi(s)) return fail(s, CERES_HIP_E_INVALID, "CLUSTER_JACOBI keeps one dense factor per cluster, not blocks per F block");
   const HostStructure& h = s->hs;
   const int64_t len = is_schur(s) ? h.diag_off_f.back() : h.diag_off_all.back();
   if (capacity < len) return fail(s, CERES_HIP_E_INVALID, "capacity %lld < %lld", (long long)capacity, (long long)len);
@@ -258,6 +283,16 @@ int ceres_hip_get_preconditioner_blocks(ceres_hip_solver* s, int32_t not_inverte
 int ceres_hip_op_precond_apply(ceres_hip_solver* s, const double* x, double* y) {
   TRY(require_loaded(s));
   HIP_TRY(s, hipSetDevice(s->opt.device));
+  if (is_cluster_jacobi(s)) {   // y += M^-1 x, M^-1 x by two triangular solves per cluster
+    if (!x || !y) return fail(s, CERES_HIP_E_INVALID, "x or y == NULL");
+    if (!s->cluster_valid) return fail(s, CERES_HIP_E_INVALID, "no preconditioner has been computed");
+    const int nf = s->hs.num_cols_f;
+    TRY(up(s, s->cg.p, x, nf));
+    TRY(up(s, s->cg.r, y, nf));
+    TRY(op_cluster_jacobi_apply(s, s->cg.p, s->cg.z, nullptr));
+    HIP_TRY(s, LaunchAxpby(1.0, s->cg.r, 1.0, s->cg.z, s->cg.z, nf, s->stream));
+    return down(s, y, s->cg.z, nf);
+  }
   if (!s->precond_valid) return fail(s, CERES_HIP_E_INVALID, "no preconditioner has been computed");
   TRY(precond_to_caller_order(s));  // a CGNR solve left its point blocks in CG's order
   const HostStructure& h = s->hs;

@@ -26,7 +26,8 @@ from .block_structure import BlockStructure, CBlockStructure
 
 # enum values equal the reference's (include/ceres/types.h:57-141, internal/ceres/linear_solver.h:57-74)
 DENSE_SCHUR, ITERATIVE_SCHUR, CGNR = 3, 5, 6
-IDENTITY, JACOBI, SCHUR_JACOBI, SCHUR_POWER_SERIES_EXPANSION = 0, 1, 2, 3
+IDENTITY, JACOBI, SCHUR_JACOBI, SCHUR_POWER_SERIES_EXPANSION, CLUSTER_JACOBI = 0, 1, 2, 3, 4
+CANONICAL_VIEWS, SINGLE_LINKAGE = 0, 1   # ceres::VisibilityClusteringType (read with CLUSTER_JACOBI)
 SUCCESS, NO_CONVERGENCE, FAILURE, FATAL_ERROR = 0, 1, 2, 3
 PATH_GENERIC, PATH_BAL = 0, 1
 E_INVALID, E_UNSUPPORTED, E_HIP, E_COMM, E_NODEVICE = -1, -2, -3, -4, -5   # CERES_HIP_E_* (include/ceres_hip.h)
@@ -35,7 +36,8 @@ UNIQUE_ID_BYTES = 128
 IPC_HANDLE_BYTES = 64
 
 (TIMED_JTJX, TIMED_SX, TIMED_SCHUR_INIT, TIMED_SCHUR_JACOBI, TIMED_BACK_SUBSTITUTE, TIMED_PACK, TIMED_BLOCK_JACOBI, TIMED_COPY,
- TIMED_READ_STREAM, TIMED_CGNR_SETUP, TIMED_MODEL_COST, TIMED_JACOBIAN_GRAM) = range(1, 13)
+ TIMED_READ_STREAM, TIMED_CGNR_SETUP, TIMED_MODEL_COST, TIMED_JACOBIAN_GRAM, TIMED_CLUSTER_ELIMINATE, TIMED_CLUSTER_FACTOR,
+ TIMED_CLUSTER_APPLY) = range(1, 16)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -50,7 +52,7 @@ class COptions(ctypes.Structure):
                 ("max_num_iterations", c_int32), ("residual_reset_period", c_int32), ("num_eliminate_blocks", c_int32),
                 ("device", c_int32), ("force_generic_path", c_int32), ("cg_check_interval", c_int32),
                 ("jacobian_storage", c_int32), ("max_num_spse_iterations", c_int32), ("use_spse_initialization", c_int32),
-                ("spse_tolerance", c_double), ("use_explicit_schur_complement", c_int32), ("reserved", c_int32)]
+                ("spse_tolerance", c_double), ("use_explicit_schur_complement", c_int32), ("visibility_clustering_type", c_int32)]
 
 
 class CSummary(ctypes.Structure):
@@ -130,6 +132,9 @@ ABI = [
     ("ceres_hip_op_spse_apply", c_int32, [c_void_p, _DP, _DP, c_int32, c_double]),
     ("ceres_hip_op_block_jacobi_update", c_int32, [c_void_p]),
     ("ceres_hip_op_schur_jacobi_update", c_int32, [c_void_p]),
+    ("ceres_hip_op_cluster_jacobi_update", c_int32, [c_void_p]),
+    ("ceres_hip_cluster_jacobi_stats", c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int64), _DP]),
+    ("ceres_hip_debug_cluster_cameras", c_int32, [POINTER(CBlockStructure), c_int32, c_int32, POINTER(c_int32), POINTER(c_int32)]),
     ("ceres_hip_get_preconditioner_blocks", c_int32, [c_void_p, c_int32, _DP, c_int64]),
     ("ceres_hip_op_precond_apply", c_int32, [c_void_p, _DP, _DP]),
     ("ceres_hip_op_schur_eliminate_dense", c_int32, [c_void_p, _DP, _DP]),
@@ -271,6 +276,7 @@ class LinearSolverOptions:
     use_spse_initialization: bool = False
     spse_tolerance: float = 0.1
     use_explicit_schur_complement: bool = False   # ITERATIVE_SCHUR on an explicitly formed (dense) S; SCHUR_JACOBI only
+    visibility_clustering_type: int = CANONICAL_VIEWS   # CLUSTER_JACOBI: CANONICAL_VIEWS or SINGLE_LINKAGE (Preconditioner::Options)
 
 
 @dataclass
@@ -325,7 +331,7 @@ class HipLinearSolver:
                      options.max_num_iterations, options.residual_reset_period, nelim, options.device,
                      int(options.force_generic_path), options.cg_check_interval, options.jacobian_storage,
                      options.max_num_spse_iterations, int(options.use_spse_initialization), options.spse_tolerance,
-                     int(options.use_explicit_schur_complement))
+                     int(options.use_explicit_schur_complement), int(options.visibility_clustering_type))
         self._h = self._lib.ceres_hip_create(byref(c))
         if not self._h:
             raise HipError(self._lib.ceres_hip_last_error(None).decode())
@@ -654,6 +660,16 @@ class HipLinearSolver:
     def schur_jacobi_update(self):
         self._check(self._lib.ceres_hip_op_schur_jacobi_update(self._h))
 
+    def cluster_jacobi_update(self):
+        """Forms and factors the CLUSTER_JACOBI preconditioner of the loaded point; precond_apply then applies it."""
+        self._check(self._lib.ceres_hip_op_cluster_jacobi_update(self._h))
+
+    def cluster_jacobi_stats(self):
+        """(number of clusters, largest cluster's scalar dimension, bytes of the factors, seconds of the host analysis)."""
+        n, d, b, t = c_int32(0), c_int32(0), c_int64(0), c_double(0.0)
+        self._check(self._lib.ceres_hip_cluster_jacobi_stats(self._h, byref(n), byref(d), byref(b), byref(t)))
+        return n.value, d.value, b.value, t.value
+
     def preconditioner_blocks(self, not_inverted=False):
         i = self._info
         sizes = self.bs.col_block_size.astype(np.int64)
@@ -770,6 +786,20 @@ def debug_plan(bs: BlockStructure, num_eliminate_blocks: int):
     return {"eligible": True, "n_tiles": nt, "slot_row": row, "slot_cam": cam, "slot_pt": pt, "seg_first": seg & 0xff,
             "seg_last": (seg >> 8) & 0xff, "valid": (seg >> 16) & 1, "tail_a": (seg >> 17) & 63, "has_a": (seg >> 23) & 1,
             "tail_b": (seg >> 24) & 63, "has_b": (seg >> 30) & 1, "tile_kind": kind, "tile_aux": aux}
+
+
+def debug_cluster_cameras(bs: BlockStructure, num_eliminate_blocks: int, visibility_clustering_type: int = CANONICAL_VIEWS):
+    """ceres_hip_debug_cluster_cameras: (cluster of every F block, number of clusters) — the host analysis of CLUSTER_JACOBI, no device."""
+    lib = load_library()
+    c = bs.as_ctypes()
+    nf = int(bs.num_col_blocks) - int(num_eliminate_blocks)
+    membership = np.full(max(nf, 1), -1, dtype=np.int32)
+    n = c_int32(0)
+    rc = lib.ceres_hip_debug_cluster_cameras(byref(c), int(num_eliminate_blocks), int(visibility_clustering_type),
+                                             membership.ctypes.data_as(POINTER(c_int32)), byref(n))
+    if rc != 0:
+        raise HipError(f"ceres_hip_debug_cluster_cameras: error {rc}")
+    return membership[:max(nf, 0)], n.value
 
 
 def debug_staged_x_plan(bs: BlockStructure, num_eliminate_blocks: int):
@@ -955,7 +985,7 @@ class BalProblem:
                      options.max_num_iterations, options.residual_reset_period, self.num_points, options.device,
                      int(options.force_generic_path), options.cg_check_interval, options.jacobian_storage,
                      options.max_num_spse_iterations, int(options.use_spse_initialization), options.spse_tolerance,
-                     int(options.use_explicit_schur_complement))
+                     int(options.use_explicit_schur_complement), int(options.visibility_clustering_type))
         if self.camera_model == CAMERA_ANGLE_AXIS:
             self._h = self._lib.ceres_hip_bal_create(byref(c), self.num_cameras, self.num_points, self.num_observations,
                                                      cam.ctypes.data_as(POINTER(c_int32)), pt.ctypes.data_as(POINTER(c_int32)),

@@ -76,7 +76,8 @@ class BlockSparseMatrix {
 // Values equal ceres::LinearSolverType / PreconditionerType / LinearSolverTerminationType.
 enum LinearSolverType { DENSE_SCHUR = CERES_HIP_DENSE_SCHUR, ITERATIVE_SCHUR = CERES_HIP_ITERATIVE_SCHUR, CGNR = CERES_HIP_CGNR };
 enum PreconditionerType { IDENTITY = CERES_HIP_IDENTITY, JACOBI = CERES_HIP_JACOBI, SCHUR_JACOBI = CERES_HIP_SCHUR_JACOBI,
-                          SCHUR_POWER_SERIES_EXPANSION = CERES_HIP_SCHUR_POWER_SERIES_EXPANSION };
+                          SCHUR_POWER_SERIES_EXPANSION = CERES_HIP_SCHUR_POWER_SERIES_EXPANSION, CLUSTER_JACOBI = CERES_HIP_CLUSTER_JACOBI };
+enum VisibilityClusteringType { CANONICAL_VIEWS = CERES_HIP_CANONICAL_VIEWS, SINGLE_LINKAGE = CERES_HIP_SINGLE_LINKAGE };
 enum class LinearSolverTerminationType { SUCCESS = 0, NO_CONVERGENCE = 1, FAILURE = 2, FATAL_ERROR = 3 };
 
 class LinearSolver {
@@ -92,6 +93,7 @@ class LinearSolver {
     int max_num_spse_iterations = 5;
     bool use_spse_initialization = false;
     double spse_tolerance = 0.1;
+    VisibilityClusteringType visibility_clustering_type = CANONICAL_VIEWS;  // CLUSTER_JACOBI (Preconditioner::Options, internal/ceres/preconditioner.h)
     int device = 0;  // not in the reference: HIP device ordinal
   };
   struct PerSolveOptions {
@@ -129,6 +131,7 @@ class HipLinearSolver final : public LinearSolver {
     o.max_num_spse_iterations = options.max_num_spse_iterations;
     o.use_spse_initialization = options.use_spse_initialization ? 1 : 0;
     o.spse_tolerance = options.spse_tolerance;
+    o.visibility_clustering_type = options.visibility_clustering_type;
     handle_ = ceres_hip_create(&o);
     if (!handle_) throw std::runtime_error(std::string("ceres_hip_create: ") + ceres_hip_last_error(nullptr));
   }

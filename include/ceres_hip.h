@@ -75,6 +75,11 @@ extern "C" {
 #define CERES_HIP_JACOBI 1
 #define CERES_HIP_SCHUR_JACOBI 2
 #define CERES_HIP_SCHUR_POWER_SERIES_EXPANSION 3 /* ITERATIVE_SCHUR only */
+#define CERES_HIP_CLUSTER_JACOBI 4 /* ITERATIVE_SCHUR only: VisibilityBasedPreconditioner, I/visibility_based_preconditioner.cc (design/14_cluster_jacobi.md) */
+
+/* visibility_clustering_type ceres::VisibilityClusteringType       include/ceres/types.h (read with CLUSTER_JACOBI only) */
+#define CERES_HIP_CANONICAL_VIEWS 0
+#define CERES_HIP_SINGLE_LINKAGE 1
 
 #define CERES_HIP_SUCCESS 0
 #define CERES_HIP_NO_CONVERGENCE 1
@@ -113,7 +118,7 @@ typedef struct ceres_hip_block_structure {
  * I/linear_solver.h:148-230; defaults as there (max_num_iterations = 1!).   */
 typedef struct ceres_hip_options {
   int32_t solver_type;           /* CERES_HIP_CGNR | CERES_HIP_ITERATIVE_SCHUR             */
-  int32_t preconditioner_type;   /* IDENTITY | JACOBI | SCHUR_JACOBI                       */
+  int32_t preconditioner_type;   /* IDENTITY | JACOBI | SCHUR_JACOBI | SPSE | CLUSTER_JACOBI */
   int32_t min_num_iterations;    /* LinearSolver::Options::min_num_iterations              */
   int32_t max_num_iterations;    /* LinearSolver::Options::max_num_iterations              */
   int32_t residual_reset_period; /* LinearSolver::Options::residual_reset_period (10)      */
@@ -137,7 +142,13 @@ typedef struct ceres_hip_options {
    * HBM); a sharded run stores it DENSE (num_cols_f <= CERES_HIP_MAX_EXPLICIT_SCHUR_COLS) and all-reduces it.
    * preconditioner_type must be SCHUR_JACOBI (the reference CHECKs the same).                */
   int32_t use_explicit_schur_complement;
-  int32_t reserved;
+  /* CLUSTER_JACOBI: how the F blocks ("cameras") are clustered by the E blocks they see — CERES_HIP_CANONICAL_VIEWS (0, Ceres' default)
+   * or CERES_HIP_SINGLE_LINKAGE; any other value fails ceres_hip_create with CERES_HIP_E_INVALID.  Ignored by the other
+   * preconditioners.  (The field was `reserved`, which every caller passed as 0.)
+   * Where the reference leaves the result to the iteration order of its hash sets, this library pins it: candidates are scanned and a
+   * candidate's neighbours summed in ascending F-block index, only a strictly greater score replaces the best (the lowest index wins a
+   * tie), and the clusters are numbered by ascending first member.  Every such result is one the reference can produce. */
+  int32_t visibility_clustering_type;
 } ceres_hip_options;
 #define CERES_HIP_MAX_EXPLICIT_SCHUR_COLS 8192
 
@@ -327,6 +338,17 @@ int ceres_hip_op_block_jacobi_update(ceres_hip_solver* s);
 /* SchurJacobiPreconditioner::UpdateImpl = SchurEliminator::Eliminate into a
  * block-diagonal lhs + Invert     I/schur_jacobi_preconditioner.cc:87-97, I/schur_eliminator_impl.h:184-311 */
 int ceres_hip_op_schur_jacobi_update(ceres_hip_solver* s);
+/* VisibilityBasedPreconditioner::UpdateImpl for CLUSTER_JACOBI (I/visibility_based_preconditioner.cc:322-380): SchurEliminator::Eliminate
+ * into the block pairs (i <= j) of F blocks that share a chunk (or an E-free row) AND a cluster, D_f^2 on the diagonal, then one dense
+ * Cholesky factorisation per cluster.  ceres_hip_op_precond_apply then applies y += M^-1 x by two triangular solves per cluster.
+ * CERES_HIP_E_INVALID on a handle that was not created with CERES_HIP_CLUSTER_JACOBI; a pivot that is not positive is reported as
+ * CERES_HIP_E_INVALID "Preconditioner update failed." (inside a solve: termination FAILURE with that message). */
+int ceres_hip_op_cluster_jacobi_update(ceres_hip_solver* s);
+/* What set_structure derived for CLUSTER_JACOBI: the number of clusters, the largest cluster's scalar dimension, the bytes of the dense
+ * factors, and the seconds the host analysis took (clustering + pair lists).  Any pointer may be NULL.  CERES_HIP_E_INVALID on a NULL
+ * handle, before set_structure, or on a handle without CLUSTER_JACOBI. */
+int ceres_hip_cluster_jacobi_stats(const ceres_hip_solver* s, int32_t* num_clusters, int32_t* largest_cluster_dimension,
+                                   int64_t* factor_bytes, double* setup_seconds);
 /* The preconditioner's inverted diagonal blocks, dense row-major, block order.
  * If not_inverted != 0 the blocks as they were BEFORE Invert() are returned
  * (i.e. the diagonal blocks of J^T J + D^2, or of S).                        */
@@ -600,6 +622,11 @@ int ceres_hip_debug_bal_evaluate_tiles_timing(ceres_hip_bal* p, const double* st
 #define CERES_HIP_TIMED_READ_STREAM 9 /* read-only pass over the packed tiles, same loads as the fused kernels */
 #define CERES_HIP_TIMED_MODEL_COST 11 /* -(J x)'(f + J x / 2) as the LM step forms it where nothing else does (fused path: the kJx pass) */
 #define CERES_HIP_TIMED_JACOBIAN_GRAM 12 /* the dogleg strategy's pass over J: what ceres_hip_op_jacobian_gram launches, on device vectors */
+/* CLUSTER_JACOBI handles: the gather elimination into the cluster pairs / scatter into the dense cluster matrices + their Cholesky
+ * factorisations (re-assembled every time) / one application z = M^-1 r */
+#define CERES_HIP_TIMED_CLUSTER_ELIMINATE 13
+#define CERES_HIP_TIMED_CLUSTER_FACTOR 14
+#define CERES_HIP_TIMED_CLUSTER_APPLY 15
 int ceres_hip_time_op(ceres_hip_solver* s, int32_t op, int32_t iters, double* avg_ms);
 /* Per-phase event timings (ms) of the most recent ceres_hip_solve* / ceres_hip_lm_compute_step*.  The phases are bracketed by HIP events
  * on the solver's stream, and an event record between two kernels idles the device for about 6 us (a barrier packet with a completion
@@ -628,6 +655,13 @@ int ceres_hip_debug_plan(const ceres_hip_block_structure* bs, int32_t num_elimin
  * block outside the ordering; *num_groups.  blocks: CERES_HIP_INNER_AUTOMATIC .. CERES_HIP_INNER_POINTS_CAMERAS. */
 int ceres_hip_debug_inner_iteration_ordering(int32_t num_cameras, int32_t num_points, int64_t num_observations, const int32_t* camera_index,
                                              const int32_t* point_index, int32_t blocks, int32_t* group_of_block, int32_t* num_groups);
+
+/* Debug: the camera clustering of CLUSTER_JACOBI (csrc/visibility.cc; pure host code): membership[num_col_blocks - num_eliminate_blocks]
+ * = the cluster of every F block, *num_clusters = their number (clusters numbered by ascending first member; the tie-break rule is
+ * stated at ceres_hip_options.visibility_clustering_type).  CERES_HIP_E_INVALID for NULL pointers, a structure AnalyzeStructure
+ * rejects, no F block, or an unknown clustering type. */
+int ceres_hip_debug_cluster_cameras(const ceres_hip_block_structure* bs, int32_t num_eliminate_blocks, int32_t visibility_clustering_type,
+                                    int32_t* membership, int32_t* num_clusters);
 
 /* Debug: the subspace dogleg's boundary minimum (DoglegStrategy::FindMinimumOnTrustRegionBoundary and the first-order check of
  * ComputeSubspaceDoglegStep, I/dogleg_strategy.cc:304-336, 473-515; pure host code).  B[4]: the 2x2 model matrix, row-major; g[2]; the

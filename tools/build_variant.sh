@@ -13,7 +13,8 @@ SRCS=$(python3 -c "import sys; sys.path.insert(0, '$REPO/ceres-solver_amd'); imp
 OBJS=""
 for S in $SRCS; do
   O=$TMP/$(basename $S).o
-  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics "$@" -x hip -c $CSRC/$S -o $O &
+  EXTRA=$(python3 -c "import sys; sys.path.insert(0, '$REPO/ceres-solver_amd'); import build; print(' '.join(getattr(build, 'EXTRA_FLAGS', {}).get('$S', [])))")   # per-file flags of build.py
+  hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -munsafe-fp-atomics $EXTRA "$@" -x hip -c $CSRC/$S -o $O &
   OBJS="$OBJS $O"
 done
 wait
