@@ -5,6 +5,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "device.h"
 #include "robust_loss.h"
 #include "snavely.h"
@@ -23,8 +25,10 @@ __device__ __forceinline__ double bal_eval_wave_sum(double v) {
 // Jacobi column scaling comes after the correction.  !ROBUST: the squared loss, as this kernel was before losses existed.
 // CM: the camera model (kCam*, device.h) — state doubles per camera SW, Jacobian columns per camera CW (the scale vector and the F cells
 // are in the tangent space: 9 for the angle-axis and the quaternion-manifold camera, 10 for the Euclidean quaternion).
-template <bool JAC, bool ROBUST, int CM = kCamAngleAxis>
-__global__ __launch_bounds__(kVecBlock) void bal_evaluate_kernel(BalEvalArgs A) {
+// CONST: a reduced program (BalEvalConstArgs: row_fpos / row_scam / row_spt): a cell of a constant block is neither scaled nor stored,
+// the Corrector still uses the whole residual.  A template flag: the !CONST instantiations are the kernel as it was, arguments included.
+template <bool JAC, bool ROBUST, int CM = kCamAngleAxis, bool CONST = false>
+__global__ __launch_bounds__(kVecBlock) void bal_evaluate_kernel(typename std::conditional<CONST, BalEvalConstArgs, BalEvalArgs>::type A) {
   constexpr int SW = CM == kCamAngleAxis ? 9 : 10;
   constexpr int CW = CM == kCamQuaternion ? 10 : 9;
   __shared__ double sh[4];
@@ -58,7 +62,29 @@ __global__ __launch_bounds__(kVecBlock) void bal_evaluate_kernel(BalEvalArgs A) 
       cost += 0.5 * (res[0] * res[0] + res[1] * res[1]);
     }
     if (A.residuals) reinterpret_cast<double2*>(A.residuals)[r] = make_double2(res[0], res[1]);
-    if constexpr (JAC) {
+    if constexpr (JAC && CONST) {
+      const int fpos = A.row_fpos[r], scam = A.row_scam[r], spt = A.row_spt[r];
+      if (spt >= 0) {
+        if (A.scale) {
+          const double* sp = A.scale + spt;
+#pragma unroll
+          for (int j = 0; j < 3; ++j) { const double v = sp[j]; jp[j] *= v; jp[3 + j] *= v; }
+        }
+        double2* e = reinterpret_cast<double2*>(A.values + 6 * r);   // (rows with an E cell come first: its place is the row's)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) e[j] = make_double2(jp[2 * j], jp[2 * j + 1]);
+      }
+      if (fpos >= 0) {
+        if (A.scale) {
+          const double* sc = A.scale + scam;
+#pragma unroll
+          for (int j = 0; j < CW; ++j) { const double v = sc[j]; jc[j] *= v; jc[CW + j] *= v; }
+        }
+        double2* fo = reinterpret_cast<double2*>(A.values + fpos);
+#pragma unroll
+        for (int j = 0; j < CW; ++j) fo[j] = make_double2(jc[2 * j], jc[2 * j + 1]);
+      }
+    } else if constexpr (JAC) {
       if (A.scale) {
         const double* sc = A.scale + A.cam_base + CW * int64_t(c);
         const double* sp = A.scale + 3 * int64_t(p);

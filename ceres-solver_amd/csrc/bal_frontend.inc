@@ -46,6 +46,21 @@ struct ceres_hip_bal {
   // the dogleg strategy's device vectors (a = gradient / diagonal, b = gn / diagonal) and partial sums, made on first use
   int32_t tr_strategy = CERES_HIP_LEVENBERG_MARQUARDT, dogleg_type = CERES_HIP_TRADITIONAL_DOGLEG;
   double *d_dl_a = nullptr, *d_dl_b = nullptr, *d_dl_parts = nullptr;
+  // ceres_hip_bal_create_with_constant_blocks (constant_blocks.inc): nc, np and n_a stay the caller's (the state is full), `no` is the
+  // number of KEPT rows, n_t the reduced tangent length.  Everything below is unset on a handle without constant blocks.
+  bool has_const = false;
+  int nfc = 0, nfp = 0;                        // free cameras / points (= nc, np without constants)
+  int64_t n_rows_e = 0, n_rows_f = 0;          // rows with an E cell (they come first) / with an F cell
+  std::vector<int32_t> cam_col, pt_col;        // block -> index among the free ones, -1: constant
+  std::vector<int32_t> all_cam, all_pt;        // the caller's observations, every one (the inner iterations' lists; the removed rows)
+  std::vector<double> all_obs;
+  int32_t *d_row_fpos = nullptr, *d_row_scam = nullptr, *d_row_spt = nullptr;   // BalEvalArgs' per-row positions
+  int64_t n_removed = 0;                       // rows removed (both blocks constant) and their camera / point / pixel: the fixed cost
+  int32_t *d_rm_cam = nullptr, *d_rm_pt = nullptr;
+  double2* d_rm_obs = nullptr;
+  int64_t* d_free_block = nullptr;             // BalFreeBlocks::block
+  int32_t *d_pack_cam = nullptr, *d_pack_scale = nullptr;   // BalEvalTilesArgs' camera records (constant cameras on the tile path)
+  double2* d_scrap = nullptr;
 };
 void bal_inner_free(ceres_hip_bal* p);
 
@@ -69,12 +84,17 @@ int bal_fail(ceres_hip_bal* p, int code) {
 int bal_evaluate_device(ceres_hip_bal* p, const double* d_state, bool jacobian, const double* d_scale, double* d_residuals,
                         double* cost, bool defer = false) {
   ceres_hip_solver* s = p->s;
-  BalEvalArgs A;
+  BalEvalConstArgs A;
   A.n_rows = p->no; A.row_cam = p->d_row_cam; A.row_pt = p->d_row_pt; A.row_obs = p->d_row_obs;
   A.state = d_state; A.cam_base = 3 * int64_t(p->np); A.scale = d_scale;
   A.residuals = d_residuals; A.values = jacobian ? p->d_vals : nullptr; A.partials = p->d_parts; A.loss = p->loss;
   int nparts = 0;
-  HIP_TRY(s, LaunchBalEvaluate(A, jacobian, &nparts, s->stream, p->camera_model));
+  if (p->has_const && jacobian) {   // a reduced program: the cells of constant blocks are neither scaled nor stored
+    A.row_fpos = p->d_row_fpos; A.row_scam = p->d_row_scam; A.row_spt = p->d_row_spt;
+    HIP_TRY(s, LaunchBalEvaluateConst(A, &nparts, s->stream, p->camera_model));
+  } else {
+    HIP_TRY(s, LaunchBalEvaluate(A, jacobian, &nparts, s->stream, p->camera_model));
+  }
   if (defer) { p->deferred_cost_parts = nparts; return 0; }
   HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nparts, hipMemcpyDeviceToHost, s->stream));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -90,6 +110,8 @@ bool bal_writes_tiles(const ceres_hip_bal* p) {
   const ceres_hip_solver* s = p->s;
   // (the tile evaluator computes the angle-axis Jacobian: quaternion cameras keep the two-pass form — the manifold's <2,3,9> included)
   if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) return false;
+  // (constant blocks: the tile evaluator's records exist for constant cameras alone — constant points leave remainder rows anyway)
+  if (p->has_const && !p->d_pack_cam) return false;
   if (const char* e = getenv("CERES_HIP_EVAL_TILES")) if (atoi(e) == 0) return false;
   // (DENSE_SCHUR forms S from the caller-layout values, E cells included: it keeps the two-pass form)
   return s->path == CERES_HIP_PATH_BAL && s->ops && s->ops->ne == 3 && s->ops->nf == 9 && s->ops->ns == 0 && !s->d_Jf && s->d_J && s->world <= 1 &&
@@ -125,7 +147,7 @@ void bal_set_camera_eval(ceres_hip_bal* p, bool on) {
 // exist (p->d_vals; the camera-major preconditioner pass reads them there).
 int bal_evaluate_into_tiles(ceres_hip_bal* p, const double* d_state, const double* d_scale, double* cost, int debug_flags = 0, bool defer = false) {
   ceres_hip_solver* s = p->s;
-  BalEvalTilesArgs T;
+  BalEvalTilesConstArgs T;
   T.debug_flags = debug_flags;
   T.e.n_rows = p->no; T.e.row_cam = p->d_row_cam; T.e.row_pt = p->d_row_pt; T.e.row_obs = p->d_row_obs;
   T.e.state = d_state; T.e.cam_base = 3 * int64_t(p->np); T.e.scale = d_scale;
@@ -134,10 +156,12 @@ int bal_evaluate_into_tiles(ceres_hip_bal* p, const double* d_state, const doubl
   T.n_tiles = s->plan.n_tiles; T.slot_bpos = s->d_slot_bpos; T.slot_fpos = s->d_slot_fpos;
   T.J_out = s->d_J; T.tile_pitch = s->ops->tile_pitch; T.b_out = s->d_bt;
   T.slot_cam = p->d_slot_cam; T.slot_pt = p->d_slot_pt; T.slot_obs = p->d_slot_obs; T.pt_pack = p->d_pt_pack; T.cam_pack = p->d_cam_pack;
+  T.pack_cam = p->d_pack_cam; T.pack_scale = p->d_pack_scale; T.n_pack_cams = p->nc; T.scrap = p->d_scrap;   // (constant cameras; nullptr otherwise)
   TRY(load_device(s, p->d_vals, p->d_res, nullptr));   // (marks the tiles stale: they are, until the launch below is enqueued)
   bal_set_camera_eval(p, cam_eval);
   int nparts = 0;
-  HIP_TRY(s, LaunchBalEvaluateTiles(T, p->np, p->nc, &nparts, s->stream));
+  if (p->has_const) HIP_TRY(s, LaunchBalEvaluateTilesConst(T, p->np, &nparts, s->stream));
+  else HIP_TRY(s, LaunchBalEvaluateTiles(T, p->np, p->nc, &nparts, s->stream));
   s->packed = true;
   s->tiles_only = true;   // (E cells are never written; F cells only for the camera-major pass that reads them)
   if (defer) { p->deferred_cost_parts = nparts; return 0; }
@@ -157,7 +181,10 @@ int bal_gradient_max(ceres_hip_bal* p, const double* d_scale, const double* d_x,
   ceres_hip_solver* s = p->s;
   int nparts = 0;
   static_assert(kMaxVecGrid <= kBalParts - kBalSecondParts, "room for the second kernel's partials");
-  if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD)
+  if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD && p->has_const)
+    HIP_TRY(s, LaunchBalGradientMaxQuatFree(BalFreeBlocks{p->d_free_block, p->nfp, p->nfc}, p->d_grad, d_scale, d_x, p->d_parts + kBalSecondParts, &nparts,
+                                            s->stream));
+  else if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD)
     HIP_TRY(s, LaunchBalGradientMaxQuat(p->d_grad, d_scale, d_x, p->np, p->nc, p->d_parts + kBalSecondParts, &nparts, s->stream));
   else
     HIP_TRY(s, LaunchBalGradientMax(p->d_grad, d_scale, p->n_t, p->d_parts + kBalSecondParts, &nparts, s->stream));
@@ -180,10 +207,32 @@ int bal_gradient_max(ceres_hip_bal* p, const double* d_scale, const double* d_x,
 // delta = step .* scale, cand = Plus(x, delta); |x|^2 partials at parts[0 ..), |delta|^2 at parts[*nparts ..)
 int bal_candidate(ceres_hip_bal* p, const double* x, const double* scale, double* cand, double* parts, int* nparts) {
   ceres_hip_solver* s = p->s;
-  if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD)
+  if (p->has_const)   // (Plus scattered into the free blocks; cand's constant blocks hold the state's values already: ceres_hip_bal_minimize)
+    HIP_TRY(s, LaunchBalCandidateFree(BalFreeBlocks{p->d_free_block, p->nfp, p->nfc}, p->camera_model, x, p->d_step, scale, p->d_delta, cand, parts,
+                                      nparts, s->stream));
+  else if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD)
     HIP_TRY(s, LaunchBalCandidateQuat(x, p->d_step, scale, p->d_delta, cand, p->np, p->nc, parts, nparts, s->stream));
   else   // (the angle-axis and the Euclidean quaternion camera: Plus is x + delta)
     HIP_TRY(s, LaunchBalCandidate(x, p->d_step, scale, p->d_delta, cand, p->n_a, parts, nparts, s->stream));
+  return 0;
+}
+
+// Solver::Summary::fixed_cost at a device state vector: the cost-only evaluator over the removed rows (both blocks constant), its
+// partial sums added in their fixed order
+int bal_fixed_cost_device(ceres_hip_bal* p, const double* d_state, double* cost) {
+  ceres_hip_solver* s = p->s;
+  *cost = 0.0;
+  if (p->n_removed == 0) return 0;
+  BalEvalArgs A;
+  A.n_rows = p->n_removed; A.row_cam = p->d_rm_cam; A.row_pt = p->d_rm_pt; A.row_obs = p->d_rm_obs;
+  A.state = d_state; A.cam_base = 3 * int64_t(p->np); A.partials = p->d_parts; A.loss = p->loss;
+  int nparts = 0;
+  HIP_TRY(s, LaunchBalEvaluate(A, false, &nparts, s->stream, p->camera_model));
+  HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nparts, hipMemcpyDeviceToHost, s->stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  double c = 0;
+  for (int i = 0; i < nparts; ++i) c += p->h_parts[i];
+  *cost = c;
   return 0;
 }
 
@@ -193,6 +242,7 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 
 }  // namespace
 
+#include "constant_blocks.inc"
 #include "inner_iterations.inc"
 #include "dogleg.inc"
 
@@ -231,10 +281,12 @@ void ceres_hip_bal_destroy(ceres_hip_bal* p) {
 
 namespace {
 
-// ceres_hip_bal_create and ceres_hip_bal_create_with_camera (`fn` names the entry point in the messages)
+// ceres_hip_bal_create, ceres_hip_bal_create_with_camera and ceres_hip_bal_create_with_constant_blocks (`fn` names the entry point in
+// the messages).  The masks may be NULL; with none set the reduction below is the identity and the handle is what it always was.
 ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras, int32_t num_points,
                           int64_t num_observations, const int32_t* camera_index, const int32_t* point_index,
-                          const double* observations) try {   // (host vectors sized by the caller's counts: no C++ exception crosses the C boundary)
+                          const double* observations, const uint8_t* camera_is_constant = nullptr,
+                          const uint8_t* point_is_constant = nullptr) try {   // (host vectors sized by the caller's counts: no C++ exception crosses the C boundary)
   const std::string name(fn);
   static_assert(kCamAngleAxis == CERES_HIP_CAMERA_ANGLE_AXIS && kCamQuaternion == CERES_HIP_CAMERA_QUATERNION &&
                 kCamQuaternionManifold == CERES_HIP_CAMERA_QUATERNION_MANIFOLD, "device camera models are the ABI's");
@@ -261,41 +313,69 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
       return nullptr;
     }
   }
+  bool has_const = false;
+  for (int c = 0; camera_is_constant && c < num_cameras; ++c) has_const = has_const || camera_is_constant[c] != 0;
+  for (int q = 0; point_is_constant && q < num_points; ++q) has_const = has_const || point_is_constant[q] != 0;
+  // Program::RemoveFixedBlocks and the Schur ordering (constant_blocks.inc).  Nothing constant: rows grouped by point, stable in
+  // observation order (points are elimination group 0), every block free.
+  BalReduction R;
+  {
+    const std::string why = bal_reduce(num_cameras, num_points, num_observations, camera_index, point_index, has_const ? camera_is_constant : nullptr,
+                                       has_const ? point_is_constant : nullptr, R);
+    if (!why.empty()) {
+      g_create_error = name + ": " + why;
+      return nullptr;
+    }
+  }
+  const int nfc = R.num_free_cameras, nfp = R.num_free_points;
+  if (has_const && 3 * int64_t(num_points) + cs * int64_t(num_cameras) > int64_t(INT32_MAX)) {
+    g_create_error = name + ": more than 2^31 state doubles with constant blocks";
+    return nullptr;
+  }
   ceres_hip_options o = *options;
-  o.num_eliminate_blocks = num_points;
+  o.num_eliminate_blocks = nfp;
   ceres_hip_solver* s = ceres_hip_create(&o);
   if (!s) return nullptr;
   ceres_hip_bal* p = new ceres_hip_bal;
   p->s = s;
-  p->nc = num_cameras; p->np = num_points; p->no = num_observations;
+  const int64_t no = int64_t(R.row_obs.size());   // kept rows
+  p->nc = num_cameras; p->np = num_points; p->no = no;
+  p->nfc = nfc; p->nfp = nfp; p->has_const = has_const;
   p->camera_model = camera_model; p->cs = cs; p->cw = cw;
   p->n_a = 3 * int64_t(num_points) + cs * int64_t(num_cameras);
-  p->n_t = 3 * int64_t(num_points) + cw * int64_t(num_cameras);
+  p->n_t = 3 * int64_t(nfp) + cw * int64_t(nfc);
   auto bail = [&](const char* what) -> ceres_hip_bal* {
     g_create_error = std::string(what) + ": " + s->err;
     ceres_hip_bal_destroy(p);
     return nullptr;
   };
-  // Rows grouped by point, stable in observation order (points are elimination group 0).
-  const int64_t no = num_observations;
-  p->row_obs.resize(no);
-  std::iota(p->row_obs.begin(), p->row_obs.end(), 0);
-  std::stable_sort(p->row_obs.begin(), p->row_obs.end(), [&](int32_t a, int32_t b) { return point_index[a] < point_index[b]; });
-  const int ncb = num_points + num_cameras;
-  std::vector<int32_t> rsz(no, 2), rpos(no), csz(ncb), cpos(ncb), rptr(no + 1), ccol(2 * no), cval(2 * no), rcam(no), rpt(no);
+  p->row_obs = R.row_obs;
+  const int64_t ne = R.num_rows_e;
+  const int ncb = nfp + nfc;
+  std::vector<int32_t> rsz(no, 2), rpos(no), csz(ncb), cpos(ncb), rptr(no + 1), ccol, cval, rcam(no), rpt(no), rfpos(no), rscam(no), rspt(no);
+  std::vector<int32_t> frow;   // F cell (in row order) -> row
   std::vector<double> robs(2 * no);
-  for (int q = 0; q < num_points; ++q) { csz[q] = 3; cpos[q] = 3 * q; }
-  for (int c = 0; c < num_cameras; ++c) { csz[num_points + c] = cw; cpos[num_points + c] = 3 * num_points + cw * c; }
-  for (int64_t r = 0; r < no; ++r) {
+  ccol.reserve(2 * no); cval.reserve(2 * no); frow.reserve(no);
+  for (int q = 0; q < nfp; ++q) { csz[q] = 3; cpos[q] = 3 * q; }
+  for (int c = 0; c < nfc; ++c) { csz[nfp + c] = cw; cpos[nfp + c] = 3 * nfp + cw * c; }
+  for (int64_t r = 0; r < no; ++r) if (R.camera_column[camera_index[p->row_obs[r]]] >= 0) frow.push_back(int32_t(r));
+  const int64_t nf = int64_t(frow.size());
+  p->n_rows_e = ne; p->n_rows_f = nf;
+  const int64_t nvals = 6 * ne + 2 * cw * nf;
+  for (int64_t r = 0, f = 0; r < no; ++r) {
     const int ob = p->row_obs[r];
     rpos[r] = int32_t(2 * r);
-    rptr[r] = int32_t(2 * r);
+    rptr[r] = int32_t(ccol.size());
     rcam[r] = camera_index[ob]; rpt[r] = point_index[ob];
     robs[2 * r] = observations[2 * int64_t(ob)]; robs[2 * r + 1] = observations[2 * int64_t(ob) + 1];
-    ccol[2 * r] = rpt[r];                    cval[2 * r] = int32_t(6 * r);                 // E cell
-    ccol[2 * r + 1] = num_points + rcam[r];  cval[2 * r + 1] = int32_t(6 * no + 2 * cw * r);  // F cell
+    const int pc = R.point_column[rpt[r]], cc = R.camera_column[rcam[r]];
+    rspt[r] = pc >= 0 ? 3 * pc : -1;
+    rscam[r] = cc >= 0 ? 3 * nfp + cw * cc : -1;
+    rfpos[r] = -1;
+    if (pc >= 0) { ccol.push_back(pc); cval.push_back(int32_t(6 * r)); }                             // E cell (rows with one come first)
+    if (cc >= 0) { rfpos[r] = int32_t(6 * ne + 2 * cw * f++); ccol.push_back(nfp + cc); cval.push_back(rfpos[r]); }   // F cell
   }
-  rptr[no] = int32_t(2 * no);
+  rptr[no] = int32_t(ccol.size());
   ceres_hip_block_structure flat{int32_t(no), ncb, rsz.data(), rpos.data(), csz.data(), cpos.data(), rptr.data(), ccol.data(),
                                  cval.data()};
   if (ceres_hip_set_structure(s, &flat) != CERES_HIP_OK) return bail((name + ": set_structure").c_str());
@@ -307,28 +387,68 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
   ok = ok && dev_alloc(s, &p->d_x, size_t(p->n_a)) == 0 && dev_alloc(s, &p->d_cand, size_t(p->n_a)) == 0 &&
        dev_alloc(s, &p->d_step, size_t(p->n_t)) == 0 && dev_alloc(s, &p->d_delta, size_t(p->n_t)) == 0 &&
        dev_alloc(s, &p->d_scale, size_t(p->n_t)) == 0 && dev_alloc(s, &p->d_grad, size_t(p->n_t)) == 0 &&
-       dev_alloc(s, &p->d_res, size_t(2 * no)) == 0 && dev_alloc(s, &p->d_vals, size_t(per_obs * no)) == 0 &&
+       dev_alloc(s, &p->d_res, size_t(2 * no)) == 0 && dev_alloc(s, &p->d_vals, size_t(nvals)) == 0 &&
        dev_alloc(s, &p->d_parts, size_t(kBalParts)) == 0;
-  // the rows' camera / point / pixel in slot order: the tile evaluator's and the evaluating camera-major pass's records (angle-axis only)
-  if (ok && s->path == CERES_HIP_PATH_BAL && !s->plan.slot_bpos.empty() && camera_model == CERES_HIP_CAMERA_ANGLE_AXIS) {
+  if (ok && has_const) {   // the reduced program's maps, the removed rows, the caller's observations (the inner iterations' lists)
+    p->cam_col = R.camera_column; p->pt_col = R.point_column;
+    p->all_cam.assign(camera_index, camera_index + num_observations);
+    p->all_pt.assign(point_index, point_index + num_observations);
+    p->all_obs.assign(observations, observations + 2 * num_observations);
+    std::vector<int64_t> fb;
+    fb.reserve(size_t(ncb));
+    for (int q = 0; q < num_points; ++q) if (R.point_column[q] >= 0) fb.push_back(3 * int64_t(q));
+    for (int c = 0; c < num_cameras; ++c) if (R.camera_column[c] >= 0) fb.push_back(3 * int64_t(num_points) + cs * int64_t(c));
+    ok = dev_upload(s, &p->d_row_fpos, rfpos) == 0 && dev_upload(s, &p->d_row_scam, rscam) == 0 && dev_upload(s, &p->d_row_spt, rspt) == 0 &&
+         dev_upload(s, &p->d_free_block, fb) == 0;
+    p->n_removed = int64_t(R.removed_obs.size());
+    if (ok && p->n_removed > 0) {
+      std::vector<int32_t> mc, mp;
+      std::vector<double> mo;
+      for (int32_t ob : R.removed_obs) {
+        mc.push_back(camera_index[ob]); mp.push_back(point_index[ob]);
+        mo.push_back(observations[2 * int64_t(ob)]); mo.push_back(observations[2 * int64_t(ob) + 1]);
+      }
+      double* md = nullptr;
+      ok = dev_upload(s, &p->d_rm_cam, mc) == 0 && dev_upload(s, &p->d_rm_pt, mp) == 0 && dev_upload(s, &md, mo) == 0;
+      p->d_rm_obs = reinterpret_cast<double2*>(md);
+    }
+  }
+  // the rows' camera / point / pixel in slot order: the tile evaluator's and the evaluating camera-major pass's records (angle-axis only;
+  // with constant blocks: constant cameras alone — every row then has its E cell, no row is outside the tiles)
+  if (ok && s->path == CERES_HIP_PATH_BAL && !s->plan.slot_bpos.empty() && camera_model == CERES_HIP_CAMERA_ANGLE_AXIS && nfp == num_points) {
     const size_t ns = s->plan.slot_bpos.size();
+    // camera records: the free cameras in the solver's order, the constant ones behind them (the identity without constants)
+    std::vector<int32_t> rec_of(num_cameras), pack_cam(num_cameras), pack_scale(num_cameras);
+    for (int c = 0, k = nfc; c < num_cameras; ++c) {
+      const int cc = R.camera_column[c];
+      rec_of[c] = cc >= 0 ? cc : k++;
+      pack_cam[rec_of[c]] = c;
+      pack_scale[rec_of[c]] = cc >= 0 ? 3 * nfp + 9 * cc : -1;
+    }
     std::vector<int32_t> scam(ns, 0), spt(ns, 0);
     std::vector<double> sobs(2 * ns, 0.0);
     for (size_t q = 0; q < ns; ++q) {
       const int bp = s->plan.slot_bpos[q];
       if (bp < 0) continue;
       const int64_t r = bp >> 1;
-      scam[q] = rcam[r]; spt[q] = rpt[r]; sobs[2 * q] = robs[2 * r]; sobs[2 * q + 1] = robs[2 * r + 1];
+      scam[q] = rec_of[rcam[r]]; spt[q] = rpt[r]; sobs[2 * q] = robs[2 * r]; sobs[2 * q + 1] = robs[2 * r + 1];
     }
     double* so = nullptr;
     ok = dev_upload(s, &p->d_slot_cam, scam) == 0 && dev_upload(s, &p->d_slot_pt, spt) == 0 && dev_upload(s, &so, sobs) == 0 &&
          dev_alloc(s, &p->d_pt_pack, size_t(6) * num_points) == 0 && dev_alloc(s, &p->d_cam_pack, size_t(18) * num_cameras) == 0;
     p->d_slot_obs = reinterpret_cast<double2*>(so);
-    if (ok && s->plan.cam_fpos.size() == size_t(no)) {   // camera-major entry -> its row (through the F cell's position) -> point, pixel
-      std::vector<int32_t> cpt(no);
-      std::vector<double> cobs(2 * size_t(no));
-      for (int64_t q = 0; q < no; ++q) {
-        const int64_t r = (int64_t(s->plan.cam_fpos[q]) - 6 * no) / 18;
+    if (ok && has_const) {
+      double* scrap = nullptr;
+      ok = dev_upload(s, &p->d_pack_cam, pack_cam) == 0 && dev_upload(s, &p->d_pack_scale, pack_scale) == 0 && dev_alloc(s, &scrap, 2 * ns) == 0;
+      p->d_scrap = reinterpret_cast<double2*>(scrap);
+    }
+    // camera-major entry -> its row (through the F cell's position) -> point, pixel: the lists of the free cameras
+    const std::vector<int32_t>& cp = s->plan.cam_ptr;
+    if (ok && cp.size() == size_t(nfc) + 1 && cp[nfc] == nf && (has_const ? s->plan.cam_fpos.size() >= size_t(nf) : s->plan.cam_fpos.size() == size_t(no))) {
+      std::vector<int32_t> cpt(nf);
+      std::vector<double> cobs(2 * size_t(nf));
+      for (int64_t q = 0; q < nf; ++q) {
+        const int64_t r = frow[(int64_t(s->plan.cam_fpos[q]) - 6 * ne) / 18];
         cpt[q] = rpt[r]; cobs[2 * q] = robs[2 * r]; cobs[2 * q + 1] = robs[2 * r + 1];
       }
       double* co = nullptr;
@@ -363,11 +483,39 @@ ceres_hip_bal* ceres_hip_bal_create_with_camera(const ceres_hip_options* options
                     point_index, observations);
 }
 
+ceres_hip_bal* ceres_hip_bal_create_with_constant_blocks(const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras,
+                                                         int32_t num_points, int64_t num_observations, const int32_t* camera_index,
+                                                         const int32_t* point_index, const double* observations,
+                                                         const uint8_t* camera_is_constant, const uint8_t* point_is_constant) {
+  return bal_create("ceres_hip_bal_create_with_constant_blocks", options, camera_model, num_cameras, num_points, num_observations, camera_index,
+                    point_index, observations, camera_is_constant, point_is_constant);
+}
+
+int ceres_hip_bal_reduced_sizes(const ceres_hip_bal* p, int64_t* num_rows, int64_t* num_rows_e, int64_t* num_rows_removed,
+                                int32_t* num_free_cameras, int32_t* num_free_points) {
+  if (!p) return CERES_HIP_E_INVALID;
+  if (num_rows) *num_rows = p->no;
+  if (num_rows_e) *num_rows_e = p->n_rows_e;
+  if (num_rows_removed) *num_rows_removed = p->n_removed;
+  if (num_free_cameras) *num_free_cameras = p->nfc;
+  if (num_free_points) *num_free_points = p->nfp;
+  return 0;
+}
+
+int ceres_hip_bal_fixed_cost(ceres_hip_bal* p, const double* state, double* fixed_cost) {
+  if (!p || !state || !fixed_cost) return CERES_HIP_E_INVALID;
+  ceres_hip_solver* s = p->s;
+  HIP_TRY(s, hipSetDevice(s->opt.device));
+  BAL_TRY(p, up(s, p->d_cand, state, size_t(p->n_a)));
+  BAL_TRY(p, bal_fixed_cost_device(p, p->d_cand, fixed_cost));
+  return 0;
+}
+
 int ceres_hip_bal_sizes(const ceres_hip_bal* p, int64_t* num_parameters, int64_t* num_residuals, int64_t* num_jacobian_values) {
   if (!p) return CERES_HIP_E_INVALID;
   if (num_parameters) *num_parameters = p->n_a;
   if (num_residuals) *num_residuals = 2 * p->no;
-  if (num_jacobian_values) *num_jacobian_values = (6 + 2 * p->cw) * p->no;
+  if (num_jacobian_values) *num_jacobian_values = 6 * p->n_rows_e + 2 * p->cw * p->n_rows_f;
   return 0;
 }
 
@@ -430,7 +578,7 @@ int ceres_hip_bal_evaluate(ceres_hip_bal* p, const double* state, double* cost, 
   if (jac) {
     bal_set_camera_eval(p, false);
     BAL_TRY(p, load_device(s, p->d_vals, p->d_res, nullptr));
-    if (jacobian_values) BAL_TRY(p, down(s, jacobian_values, p->d_vals, size_t((6 + 2 * p->cw) * p->no)));
+    if (jacobian_values) BAL_TRY(p, down(s, jacobian_values, p->d_vals, size_t(6 * p->n_rows_e + 2 * p->cw * p->n_rows_f)));
     if (gradient) {
       BAL_TRY(p, op_jtb(s, p->d_grad));
       BAL_TRY(p, down(s, gradient, p->d_grad, size_t(p->n_t)));
@@ -450,6 +598,7 @@ int ceres_hip_debug_bal_evaluate_tiles_timing(ceres_hip_bal* p, const double* st
   }
   HIP_TRY(s, hipSetDevice(s->opt.device));
   if (!bal_writes_tiles(p)) return fail(s, CERES_HIP_E_UNSUPPORTED, "the evaluator does not write this structure's tiles");
+  if (p->has_const && flags != 0) return fail(s, CERES_HIP_E_UNSUPPORTED, "the store experiments are not built for handles with constant cameras");
   BAL_TRY(p, up(s, p->d_x, state, size_t(p->n_a)));
   double cost = 0;
   hipEvent_t e0, e1;
@@ -459,16 +608,20 @@ int ceres_hip_debug_bal_evaluate_tiles_timing(ceres_hip_bal* p, const double* st
   for (int w = 0; w < 2 && !rc; ++w) rc = bal_evaluate_into_tiles(p, p->d_x, nullptr, &cost, flags);
   float ms = 0;
   if (!rc) {
-    BalEvalTilesArgs T;   // (the launches alone: no copy of the partial sums, no synchronisation in between)
+    BalEvalTilesConstArgs T;   // (the launches alone: no copy of the partial sums, no synchronisation in between)
     T.debug_flags = flags;
     T.e.n_rows = p->no; T.e.state = p->d_x; T.e.cam_base = 3 * int64_t(p->np); T.e.residuals = p->d_res; T.e.values = p->d_vals; T.e.partials = p->d_parts;
     T.e.loss = p->loss;   // (what ceres_hip_bal_minimize runs)
     T.n_tiles = s->plan.n_tiles; T.slot_bpos = s->d_slot_bpos; T.slot_fpos = s->d_slot_fpos;
     T.J_out = s->d_J; T.tile_pitch = s->ops->tile_pitch; T.b_out = s->d_bt;
     T.slot_cam = p->d_slot_cam; T.slot_pt = p->d_slot_pt; T.slot_obs = p->d_slot_obs; T.pt_pack = p->d_pt_pack; T.cam_pack = p->d_cam_pack;
+    T.pack_cam = p->d_pack_cam; T.pack_scale = p->d_pack_scale; T.n_pack_cams = p->nc; T.scrap = p->d_scrap;
     int nparts = 0;
     (void)hipEventRecord(e0, s->stream);
-    for (int i = 0; i < iters; ++i) (void)LaunchBalEvaluateTiles(T, p->np, p->nc, &nparts, s->stream);
+    for (int i = 0; i < iters; ++i) {
+      if (p->has_const) (void)LaunchBalEvaluateTilesConst(T, p->np, &nparts, s->stream);
+      else (void)LaunchBalEvaluateTiles(T, p->np, p->nc, &nparts, s->stream);
+    }
     (void)hipEventRecord(e1, s->stream);
     if (hipStreamSynchronize(s->stream) != hipSuccess || hipEventElapsedTime(&ms, e0, e1) != hipSuccess) rc = fail(s, CERES_HIP_E_HIP, "timing probe");
   }
@@ -492,10 +645,22 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
     p->err = "ceres_hip_bal_minimize: quaternion cameras are not supported on sharded handles";
     return CERES_HIP_E_UNSUPPORTED;
   }
+  if (p->has_const && s->world > 1) {
+    p->err = "ceres_hip_bal_minimize: constant parameter blocks are not supported on sharded handles";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
   const int64_t n = p->n_a;
   BAL_TRY(p, up(s, p->d_x, state, size_t(n)));
   double* x = p->d_x;
   double* cand = p->d_cand;
+  // Constant blocks: the candidate buffer starts as a copy of the state — Plus and the inner passes write free blocks only, so the
+  // constant blocks of both buffers stay the caller's doubles through every swap — and the removed rows' cost is taken once, here
+  // (TrustRegionMinimizer adds solver_summary_->fixed_cost to every cost it reports: I/trust_region_minimizer.cc:127, 228, 261, 490)
+  double fixed_cost = 0.0;
+  if (p->has_const) {
+    HIP_TRY(s, hipMemcpyAsync(cand, x, sizeof(double) * n, hipMemcpyDeviceToDevice, st));
+    BAL_TRY(p, bal_fixed_cost_device(p, x, &fixed_cost));
+  }
   const double* scale = o->jacobi_scaling ? p->d_scale : nullptr;
   double radius = o->initial_trust_region_radius, decrease_factor = 2.0;
   bool reuse_diagonal = false, one_success = false;
@@ -523,7 +688,10 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
   }
 
   auto log_iter = [&](const ceres_hip_iteration_summary& it) {
-    if (S->num_iterations_logged < CERES_HIP_MAX_LOGGED_ITERATIONS) S->iterations[S->num_iterations_logged++] = it;
+    if (S->num_iterations_logged < CERES_HIP_MAX_LOGGED_ITERATIONS) {
+      S->iterations[S->num_iterations_logged] = it;
+      S->iterations[S->num_iterations_logged++].cost += fixed_cost;   // (0.0 without constant blocks)
+    }
   };
   // EvaluateGradientAndJacobian, I/trust_region_minimizer.cc:246-314.  The Jacobian is written
   // already scaled; the gradient of the unscaled problem is recovered from (J S)^T f = S J^T f.
@@ -556,7 +724,7 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
     snprintf(S->message, sizeof(S->message), "%s", msg);
   };
   BAL_TRY(p, eval_jacobian());
-  S->initial_cost = x_cost;
+  S->initial_cost = x_cost + fixed_cost;
   S->termination_type = CERES_HIP_NO_CONVERGENCE_T;
   {
     ceres_hip_iteration_summary it0{};
@@ -711,7 +879,7 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
     it.trust_region_radius = radius;
     log_iter(it);
   }
-  S->final_cost = x_cost;
+  S->final_cost = x_cost + fixed_cost;
   BAL_TRY(p, down(s, state, x, size_t(n)));
   S->total_seconds = seconds_since(t_start);
   return 0;

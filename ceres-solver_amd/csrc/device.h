@@ -579,12 +579,25 @@ struct BalEvalArgs {
   double* partials = nullptr;         // cost partial per workgroup (<= 2048)
   LossParams loss;                    // cost = sum rho / 2, corrected residuals and Jacobian (kLossNone: the squared loss)
 };
+// A reduced program (constant parameter blocks, ceres_hip_bal_create_with_constant_blocks; the kernel's CONST instantiations): row_cam /
+// row_pt still index the full state; a row's F cell starts at row_fpos (-1: constant camera, no cell), its E cell at 6 r when the point
+// is free; row_scam / row_spt: where the block's entries start in the reduced scale vector (-1: constant block).  An argument type of
+// its own: the existing instantiations keep their kernel arguments byte for byte (the tile-order evaluator sits at the SGPR limit —
+// three more pointers in its arguments cost its robust instantiations two VGPRs and 16 bytes of scratch).
+struct BalEvalConstArgs : BalEvalArgs {
+  const int32_t* row_fpos = nullptr;
+  const int32_t* row_scam = nullptr;
+  const int32_t* row_spt = nullptr;
+};
 // Camera models of the BAL front end (CERES_HIP_CAMERA_* of include/ceres_hip.h): state doubles / Jacobian columns per camera 9 / 9,
 // 10 / 10 and 10 / 9.  The quaternion cameras are [q_w q_x q_y q_z | t(3) | f k1 k2] (snavely.h, snavely_quat).
 enum : int { kCamAngleAxis = 0, kCamQuaternion = 1, kCamQuaternionManifold = 2 };
 // camera_model != kCamAngleAxis: 10 state doubles per camera, F cells of 2 x 10 (kCamQuaternion) or 2 x 9 (the manifold's tangent) at
 // 6 n_rows + 2 width r; A.scale then indexes the tangent vector
 hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, hipStream_t stream, int camera_model = kCamAngleAxis);
+// the Jacobian evaluation of a reduced program: a missing cell is neither scaled nor stored (cost only: LaunchBalEvaluate — it stores no cell)
+hipError_t LaunchBalEvaluateConst(const BalEvalConstArgs& A, int* nparts, hipStream_t stream, int camera_model);
+hipError_t LaunchBalEvaluateConstQuat(const BalEvalConstArgs& A, int grid, hipStream_t stream, int camera_model);
 // the quaternion cameras' instantiations of the same kernel on `grid` workgroups (kernels_quaternion.hip; LaunchBalEvaluate calls it)
 hipError_t LaunchBalEvaluateQuat(const BalEvalArgs& A, bool jacobian, int grid, hipStream_t stream, int camera_model);
 // The same in TILE order for the <2,3,9> fused path: the Jacobian lands in the solver's tiles (J_out, b_out: BalArgs' layout), the F
@@ -605,6 +618,17 @@ struct BalEvalTilesArgs {
   double2* b_out = nullptr;
 };
 hipError_t LaunchBalEvaluateTiles(const BalEvalTilesArgs& T, int64_t n_points, int64_t n_cameras, int* nparts, hipStream_t stream);
+// Constant cameras (the kernel's CONST instantiations; an argument type of its own for the reason given at BalEvalConstArgs).  cam_pack
+// holds n_pack_cams records — the free cameras in the solver's order, the constant ones behind them — record k from camera pack_cam[k]
+// of e.state and from e.scale + pack_scale[k] (-1: constant); slot_cam indexes the records; a slot whose slot_fpos is negative has no
+// F cell: zeros in the tile, its F copy goes to `scrap` (one double2 per slot, never read).  debug_flags must be 0.
+struct BalEvalTilesConstArgs : BalEvalTilesArgs {
+  const int32_t* pack_cam = nullptr;
+  const int32_t* pack_scale = nullptr;
+  int64_t n_pack_cams = 0;
+  double2* scrap = nullptr;
+};
+hipError_t LaunchBalEvaluateTilesConst(const BalEvalTilesConstArgs& T, int64_t n_points, int* nparts, hipStream_t stream);
 // delta = step .* scale, cand = x + delta; partials[0..g) = |x|^2, [g..2g) = |delta|^2 partial sums
 hipError_t LaunchBalCandidate(const double* x, const double* step, const double* scale, double* delta, double* cand, int64_t n,
                               double* partials, int* nparts, hipStream_t stream);
@@ -620,6 +644,21 @@ hipError_t LaunchBalGradientMax(const double* g, const double* scale, int64_t n,
 hipError_t LaunchBalJacobiScale(const double* colnorm2, double* scale, int64_t n, hipStream_t stream);
 // partials[0..g) = |a - b|^2 partial sums (the outer loop's step norm |x - candidate| after an inner pass)
 hipError_t LaunchBalDiffNorm(const double* a, const double* b, int64_t n, double* partials, int* nparts, hipStream_t stream);
+
+// ---- the loop's vector kernels on a reduced program (kernels_constant.hip; ceres_hip_bal_create_with_constant_blocks) ----
+// The free blocks: n_free_points then n_free_cameras entries of `block` (the block's first double in the full state); block i's tangent
+// entries start at 3 i (points) or 3 n_free_points + cw (i - n_free_points) (cameras).
+struct BalFreeBlocks {
+  const int64_t* block = nullptr;
+  int64_t n_free_points = 0, n_free_cameras = 0;
+};
+// delta = step .* scale (reduced), cand = Plus(x, delta) on the free blocks only (cand's constant blocks are not touched);
+// partials[0..g) = |x|^2 over the free blocks, [g..2g) = |delta|^2
+hipError_t LaunchBalCandidateFree(const BalFreeBlocks& B, int camera_model, const double* x, const double* step, const double* scale,
+                                  double* delta, double* cand, double* partials, int* nparts, hipStream_t stream);
+// kCamQuaternionManifold on a reduced program: LaunchBalGradientMaxQuat over the free blocks
+hipError_t LaunchBalGradientMaxQuatFree(const BalFreeBlocks& B, const double* g, const double* scale, const double* x, double* partials,
+                                        int* nparts, hipStream_t stream);
 
 // ---- dogleg trust region of the BAL front end (kernels_dogleg.hip; dogleg.inc) ----
 constexpr int kDoglegGrid = 256;   // workgroups (and partial sums per scalar) of the two kernels below

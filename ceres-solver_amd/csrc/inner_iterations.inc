@@ -28,6 +28,10 @@ struct BalInner {
   int32_t* d_blocks = nullptr;           // n_p + n_c: the kind's blocks by group, then form
   int32_t *d_pt_ptr = nullptr, *d_cam_ptr = nullptr, *d_cam_pt = nullptr, *d_iters = nullptr;
   double2* d_cam_obs = nullptr;
+  // the camera and pixel of every entry of the points' lists: the handle's rows — or, with constant blocks, lists of their own over ALL
+  // the caller's observations (a free block's loop sees its observations against constant blocks too, removed rows included)
+  const int32_t* d_pt_cam = nullptr;
+  const double2* d_pt_obs = nullptr;
   std::vector<int32_t> pt_count;         // observations per point
 };
 
@@ -116,6 +120,82 @@ int inner_form_env() {
   return -1;
 }
 
+// The handle's blocks by group, then form (lane points, wave points, cameras), uploaded; I.group / I.num_groups / I.pt_count are set
+int bal_inner_blocks(ceres_hip_bal* p, BalInner& I, int form_env) {
+  ceres_hip_solver* s = p->s;
+  const int np = p->np, nc = p->nc;
+  std::vector<int32_t> blocks;
+  blocks.reserve(static_cast<size_t>(np) + nc);
+  I.seg.assign(3 * static_cast<size_t>(I.num_groups) + 1, 0);
+  for (int g = 0; g < I.num_groups; ++g) {
+    for (int f = 0; f < 3; ++f) {
+      I.seg[3 * g + f] = int32_t(blocks.size());
+      if (f < 2) {
+        for (int q = 0; q < np; ++q) {
+          if (I.group[q] != g) continue;
+          const bool lane = form_env >= 0 ? form_env == kInnerPointLane : I.pt_count[q] <= kInnerLaneMaxObservations;
+          if (lane == (f == 0)) blocks.push_back(q);
+        }
+      } else {
+        for (int c = 0; c < nc; ++c) if (I.group[np + c] == g) blocks.push_back(c);
+      }
+    }
+  }
+  I.seg[3 * static_cast<size_t>(I.num_groups)] = int32_t(blocks.size());
+  if (!blocks.empty()) {
+    HIP_TRY(s, hipMemcpyAsync(I.d_blocks, blocks.data(), sizeof(int32_t) * blocks.size(), hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+  }
+  I.kind = p->inner_blocks;
+  I.form_env = form_env;
+  return 0;
+}
+
+
+// bal_inner_plan on a handle with constant blocks: the ordering is the reduced program's — the Hessian graph of the free blocks, constant
+// blocks in no group — and the lists run over all of the caller's observations: points in observation order, stable; cameras likewise
+int bal_inner_plan_reduced(ceres_hip_bal* p, BalInner& I, int form_env) {
+  ceres_hip_solver* s = p->s;
+  const int np = p->np, nc = p->nc;
+  const int64_t na = int64_t(p->all_cam.size());
+  if (!I.d_blocks) {
+    std::vector<int32_t> pt_ptr(static_cast<size_t>(np) + 1, 0), cam_ptr(static_cast<size_t>(nc) + 1, 0);
+    for (int64_t i = 0; i < na; ++i) { ++pt_ptr[p->all_pt[i] + 1]; ++cam_ptr[p->all_cam[i] + 1]; }
+    I.pt_count.assign(pt_ptr.begin() + 1, pt_ptr.end());
+    for (int q = 0; q < np; ++q) pt_ptr[q + 1] += pt_ptr[q];
+    for (int c = 0; c < nc; ++c) cam_ptr[c + 1] += cam_ptr[c];
+    std::vector<int32_t> pcam(static_cast<size_t>(na)), cpt(static_cast<size_t>(na));
+    std::vector<double> pobs(2 * static_cast<size_t>(na)), cobs(2 * static_cast<size_t>(na));
+    std::vector<int32_t> curp(pt_ptr.begin(), pt_ptr.end() - 1), curc(cam_ptr.begin(), cam_ptr.end() - 1);
+    for (int64_t i = 0; i < na; ++i) {
+      const size_t a = size_t(curp[p->all_pt[i]]++), b = size_t(curc[p->all_cam[i]]++);
+      pcam[a] = p->all_cam[i]; pobs[2 * a] = p->all_obs[2 * i]; pobs[2 * a + 1] = p->all_obs[2 * i + 1];
+      cpt[b] = p->all_pt[i]; cobs[2 * b] = p->all_obs[2 * i]; cobs[2 * b + 1] = p->all_obs[2 * i + 1];
+    }
+    int32_t* pc = nullptr;
+    double *po = nullptr, *co = nullptr;
+    TRY(dev_alloc(s, &I.d_blocks, static_cast<size_t>(np) + nc));
+    TRY(dev_alloc(s, &I.d_iters, static_cast<size_t>(np) + nc));
+    TRY(dev_upload(s, &I.d_pt_ptr, pt_ptr));
+    TRY(dev_upload(s, &pc, pcam));
+    TRY(dev_upload(s, &po, pobs));
+    TRY(dev_upload(s, &I.d_cam_ptr, cam_ptr));
+    TRY(dev_upload(s, &I.d_cam_pt, cpt));
+    TRY(dev_upload(s, &co, cobs));
+    I.d_pt_cam = pc; I.d_pt_obs = reinterpret_cast<double2*>(po); I.d_cam_obs = reinterpret_cast<double2*>(co);
+    HIP_TRY(s, hipStreamSynchronize(s->stream));
+  }
+  if (I.kind != p->inner_blocks) {
+    std::vector<int32_t> fcam, fpt;   // the reduced program's residual blocks that join two free blocks: the graph's edges
+    for (int64_t i = 0; i < na; ++i)
+      if (p->cam_col[p->all_cam[i]] >= 0 && p->pt_col[p->all_pt[i]] >= 0) { fcam.push_back(p->all_cam[i]); fpt.push_back(p->all_pt[i]); }
+    I.num_groups = inner_ordering(nc, np, int64_t(fcam.size()), fcam.data(), fpt.data(), p->inner_blocks, I.group);
+    for (int q = 0; q < np; ++q) if (p->pt_col[q] < 0) I.group[q] = -1;
+    for (int c = 0; c < nc; ++c) if (p->cam_col[c] < 0) I.group[np + c] = -1;
+  }
+  return bal_inner_blocks(p, I, form_env);
+}
+
 // The handle's inner-iteration lists for p->inner_blocks (cached per kind and form switch)
 int bal_inner_plan(ceres_hip_bal* p) {
   ceres_hip_solver* s = p->s;
@@ -123,10 +203,12 @@ int bal_inner_plan(ceres_hip_bal* p) {
   BalInner& I = *p->inner;
   const int form_env = inner_form_env();
   if (I.kind == p->inner_blocks && I.form_env == form_env) return 0;
-  const int64_t no = p->no;
   const int np = p->np, nc = p->nc;
+  if (p->has_const) return bal_inner_plan_reduced(p, I, form_env);
+  const int64_t no = p->no;
   std::vector<int32_t> rcam, rpt;
-  if (!I.d_blocks) {   // the lists every kind uses: point row ranges, the camera-major list, iteration counts
+  if (!I.d_blocks) {
+    I.d_pt_cam = p->d_row_cam; I.d_pt_obs = p->d_row_obs;   // the lists every kind uses: point row ranges, the camera-major list, iteration counts
     rcam.resize(static_cast<size_t>(no)); rpt.resize(static_cast<size_t>(no));
     HIP_TRY(s, hipMemcpy(rcam.data(), p->d_row_cam, sizeof(int32_t) * no, hipMemcpyDeviceToHost));
     HIP_TRY(s, hipMemcpy(rpt.data(), p->d_row_pt, sizeof(int32_t) * no, hipMemcpyDeviceToHost));
@@ -176,32 +258,7 @@ int bal_inner_plan(ceres_hip_bal* p) {
       if (p->inner_blocks == CERES_HIP_INNER_AUTOMATIC) { I.automatic = I.group; I.automatic_groups = I.num_groups; }
     }
   }
-  // the blocks by group, then form: lane points, wave points, cameras
-  std::vector<int32_t> blocks;
-  blocks.reserve(static_cast<size_t>(np) + nc);
-  I.seg.assign(3 * static_cast<size_t>(I.num_groups) + 1, 0);
-  for (int g = 0; g < I.num_groups; ++g) {
-    for (int f = 0; f < 3; ++f) {
-      I.seg[3 * g + f] = int32_t(blocks.size());
-      if (f < 2) {
-        for (int q = 0; q < np; ++q) {
-          if (I.group[q] != g) continue;
-          const bool lane = form_env >= 0 ? form_env == kInnerPointLane : I.pt_count[q] <= kInnerLaneMaxObservations;
-          if (lane == (f == 0)) blocks.push_back(q);
-        }
-      } else {
-        for (int c = 0; c < nc; ++c) if (I.group[np + c] == g) blocks.push_back(c);
-      }
-    }
-  }
-  I.seg[3 * static_cast<size_t>(I.num_groups)] = int32_t(blocks.size());
-  if (!blocks.empty()) {
-    HIP_TRY(s, hipMemcpyAsync(I.d_blocks, blocks.data(), sizeof(int32_t) * blocks.size(), hipMemcpyHostToDevice, s->stream));
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
-  }
-  I.kind = p->inner_blocks;
-  I.form_env = form_env;
-  return 0;
+  return bal_inner_blocks(p, I, form_env);
 }
 
 // One CoordinateDescentMinimizer::Minimize pass at d_state (in place), enqueued on the solver's stream; iteration counts in I.d_iters.
@@ -216,7 +273,7 @@ int bal_inner_pass(ceres_hip_bal* p, double* d_state) {
       A.blocks = I.d_blocks + I.seg[3 * g + f];
       A.n_blocks = I.seg[3 * g + f + 1] - I.seg[3 * g + f];
       if (f < 2) {
-        A.ptr = I.d_pt_ptr; A.other = p->d_row_cam; A.obs = p->d_row_obs; A.iterations = I.d_iters;
+        A.ptr = I.d_pt_ptr; A.other = I.d_pt_cam; A.obs = I.d_pt_obs; A.iterations = I.d_iters;
       } else {
         A.ptr = I.d_cam_ptr; A.other = I.d_cam_pt; A.obs = I.d_cam_obs; A.iterations = I.d_iters + p->np;
       }

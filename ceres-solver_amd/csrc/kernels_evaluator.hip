@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <type_traits>
 
 #include "device.h"
 #include "robust_loss.h"
@@ -74,6 +75,31 @@ __global__ __launch_bounds__(kVecBlock) void bal_pack_state_kernel(const double*
   }
 }
 
+// The same records on a handle with constant cameras (BalEvalTilesConstArgs): the points as above (this path has no constant
+// point), camera record k from camera pack_cam[k] of the full state and from the reduced scale at pack_scale[k] (-1, a constant camera:
+// 1.0 — its Jacobian is dropped, only its state is used, by the E cells of the rows that see it).
+__global__ __launch_bounds__(kVecBlock) void bal_pack_state_const_kernel(const double* state, const double* scale, int64_t n_points, int64_t n_pack_cams,
+                                                                         const int32_t* pack_cam, const int32_t* pack_scale, double* pt_pack,
+                                                                         double* cam_pack) {
+  const int64_t e = int64_t(blockIdx.x) * kVecBlock + threadIdx.x, n_pt_pairs = 3 * n_points;
+  if (e < n_pt_pairs) {
+    const int64_t i = e / 3;
+    const int k = int(e - 3 * i);
+    double v[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) { const int j = 2 * k + h; v[h] = j < 3 ? state[3 * i + j] : (scale ? scale[3 * i + j - 3] : 1.0); }
+    reinterpret_cast<double2*>(pt_pack)[e] = make_double2(v[0], v[1]);
+  } else if (e < n_pt_pairs + 9 * n_pack_cams) {
+    const int64_t q = e - n_pt_pairs, c = q / 9, o = 3 * n_points + 9 * int64_t(pack_cam[c]);
+    const int64_t so = pack_scale[c];
+    const int k = int(q - 9 * c);
+    double v[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) { const int j = 2 * k + h; v[h] = j < 9 ? state[o + j] : (scale && so >= 0 ? scale[so + j - 9] : 1.0); }
+    reinterpret_cast<double2*>(cam_pack)[q] = make_double2(v[0], v[1]);
+  }
+}
+
 // Software pipeline, two stages deep: a tile's index words are loaded two iterations ahead, its parameter records one iteration ahead,
 // and nothing a wave waits for is ever queued BEHIND a store — the vector memory counter retires in order, so a load issued after tile
 // N's 23 store instructions cannot be consumed before every one of them is acknowledged (the first version did exactly that: its
@@ -97,8 +123,12 @@ __device__ __forceinline__ void issue_tile_rec(const BalEvalTilesArgs& T, const 
 
 // DBG: BalEvalTilesArgs::debug_flags, compile-time (a run-time flag's branches cost the static wait counts).  ROBUST: T.e.loss applies, as
 // in bal_evaluate_kernel (the corrected values go to the tiles, the b tiles, the residuals and the F copy; padding slots add no cost).
-template <int DBG, bool F_COPY, bool ROBUST>
-__global__ __launch_bounds__(kVecBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void bal_evaluate_tiles_kernel(BalEvalTilesArgs T) {
+// CONST: constant cameras — a valid slot whose slot_fpos is negative has no F cell: zeros for F in its tile (what plan.cc promises the
+// tile kernels), and its piece of the F copy goes to T.scrap (its own slot there, never read: a store all the same, for the reason
+// given at the b tile below).  A template flag: the !CONST instantiations are the kernel as it was, arguments included.
+template <int DBG, bool F_COPY, bool ROBUST, bool CONST = false>
+__global__ __launch_bounds__(kVecBlock) __attribute__((amdgpu_waves_per_eu(2, 2))) void bal_evaluate_tiles_kernel(
+    typename std::conditional<CONST, BalEvalTilesConstArgs, BalEvalTilesArgs>::type T) {
   static_assert(kVecBlock == 256, "four waves per workgroup");
   __shared__ double sh[4];
   __shared__ double2 cells[4][64 * 9];   // a wave's 64 F cells, cell-major (9 pairs each)
@@ -157,6 +187,12 @@ __global__ __launch_bounds__(kVecBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
 #pragma unroll
       for (int j = 0; j < 6; ++j) jp[j] = 0.0;
     }
+    if constexpr (CONST) {
+      if (fp < 0) {
+#pragma unroll
+        for (int j = 0; j < 18; ++j) jc[j] = 0.0;
+      }
+    }
     if constexpr (!ROBUST) cost += 0.5 * (res[0] * res[0] + res[1] * res[1]);
     // (padding lanes store their zeros into their own slot of the b tile — which holds zeros — instead of skipping the store: a store
     // under a lane predicate may be branched over, and the compiler then counts on fewer stores in flight, so that its wait for the
@@ -181,7 +217,9 @@ __global__ __launch_bounds__(kVecBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
         const int f = __shfl(fp, slot, 64);
         const double2 v = cells[wave][q];
         // (non-temporal: the camera-major pass reads these 720 MB three kernels later; 609 -> 485 us in the unpipelined kernel)
-        double2* const dst = f >= 0 ? reinterpret_cast<double2*>(A.values + f) + piece : T.b_out + (tile * 64 + slot);
+        double2* spare = T.b_out;
+        if constexpr (CONST) spare = T.scrap;
+        double2* const dst = f >= 0 ? reinterpret_cast<double2*>(A.values + f) + piece : spare + (tile * 64 + slot);
         if constexpr ((DBG & 16) != 0) *dst = v;
         else nt_store(dst, v.x, v.y);
       }
@@ -254,6 +292,37 @@ hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, h
   } else {
     if (jacobian) hipLaunchKernelGGL((bal_evaluate_kernel<true, true>), dim3(grid), dim3(kVecBlock), 0, stream, A);
     else hipLaunchKernelGGL((bal_evaluate_kernel<false, true>), dim3(grid), dim3(kVecBlock), 0, stream, A);
+  }
+  return hipGetLastError();
+}
+
+// the reduced program's Jacobian evaluation (the quaternion cameras' instantiations: kernels_quaternion.hip)
+hipError_t LaunchBalEvaluateConst(const BalEvalConstArgs& A, int* nparts, hipStream_t stream, int camera_model) {
+  int64_t g = (A.n_rows + kVecBlock - 1) / kVecBlock;
+  const int grid = int(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+  *nparts = grid;
+  if (!A.row_fpos || !A.row_scam || !A.row_spt || !A.values) return hipErrorInvalidValue;
+  if (camera_model != kCamAngleAxis) return LaunchBalEvaluateConstQuat(A, grid, stream, camera_model);
+  if (A.loss.type == kLossNone) hipLaunchKernelGGL((bal_evaluate_kernel<true, false, kCamAngleAxis, true>), dim3(grid), dim3(kVecBlock), 0, stream, A);
+  else hipLaunchKernelGGL((bal_evaluate_kernel<true, true, kCamAngleAxis, true>), dim3(grid), dim3(kVecBlock), 0, stream, A);
+  return hipGetLastError();
+}
+
+// constant cameras (no timing experiment on them: debug_flags 0)
+hipError_t LaunchBalEvaluateTilesConst(const BalEvalTilesConstArgs& T, int64_t n_points, int* nparts, hipStream_t stream) {
+  if (T.debug_flags != 0 || !T.scrap || !T.pack_cam || !T.pack_scale) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(bal_pack_state_const_kernel, dim3(unsigned((3 * n_points + 9 * T.n_pack_cams + kVecBlock - 1) / kVecBlock)), dim3(kVecBlock), 0,
+                     stream, T.e.state, T.e.scale, n_points, T.n_pack_cams, T.pack_cam, T.pack_scale, T.pt_pack, T.cam_pack);
+  const int64_t g = (T.n_tiles + 3) / 4;
+  const int grid = int(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+  *nparts = grid;
+  const bool robust = T.e.loss.type != kLossNone;
+  if (!T.e.values) {
+    if (robust) hipLaunchKernelGGL((bal_evaluate_tiles_kernel<0, false, true, true>), dim3(grid), dim3(kVecBlock), 0, stream, T);
+    else hipLaunchKernelGGL((bal_evaluate_tiles_kernel<0, false, false, true>), dim3(grid), dim3(kVecBlock), 0, stream, T);
+  } else {
+    if (robust) hipLaunchKernelGGL((bal_evaluate_tiles_kernel<0, true, true, true>), dim3(grid), dim3(kVecBlock), 0, stream, T);
+    else hipLaunchKernelGGL((bal_evaluate_tiles_kernel<0, true, false, true>), dim3(grid), dim3(kVecBlock), 0, stream, T);
   }
   return hipGetLastError();
 }

@@ -161,4 +161,19 @@ hipError_t LaunchBalEvaluateQuat(const BalEvalArgs& A, bool jacobian, int grid, 
 #undef EVAL_QUAT_CASE
 }
 
+hipError_t LaunchBalEvaluateConstQuat(const BalEvalConstArgs& A, int grid, hipStream_t stream, int camera_model) {
+  const bool robust = A.loss.type != kLossNone;
+#define EVAL_QUAT_CONST_CASE(CM)                                                                                                        \
+  case CM:                                                                                                                              \
+    if (robust) hipLaunchKernelGGL((bal_evaluate_kernel<true, true, CM, true>), dim3(grid), dim3(kVecBlock), 0, stream, A);              \
+    else hipLaunchKernelGGL((bal_evaluate_kernel<true, false, CM, true>), dim3(grid), dim3(kVecBlock), 0, stream, A);                    \
+    return hipGetLastError();
+  switch (camera_model) {
+    EVAL_QUAT_CONST_CASE(kCamQuaternion)
+    EVAL_QUAT_CONST_CASE(kCamQuaternionManifold)
+    default: return hipErrorInvalidValue;
+  }
+#undef EVAL_QUAT_CONST_CASE
+}
+
 }  // namespace chip

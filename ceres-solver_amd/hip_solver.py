@@ -200,6 +200,14 @@ ABI += [
     ("ceres_hip_bal_create", c_void_p, [POINTER(COptions), c_int32, c_int32, c_int64, POINTER(c_int32), POINTER(c_int32), _DP]),
     ("ceres_hip_bal_create_with_camera", c_void_p, [POINTER(COptions), c_int32, c_int32, c_int32, c_int64, POINTER(c_int32),
                                                     POINTER(c_int32), _DP]),
+    ("ceres_hip_bal_create_with_constant_blocks", c_void_p, [POINTER(COptions), c_int32, c_int32, c_int32, c_int64, POINTER(c_int32),
+                                                             POINTER(c_int32), _DP, POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8)]),
+    ("ceres_hip_bal_reduced_sizes", c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int32),
+                                              POINTER(c_int32)]),
+    ("ceres_hip_bal_fixed_cost", c_int32, [c_void_p, _DP, _DP]),
+    ("ceres_hip_debug_bal_reduce", c_int32, [c_int32, c_int32, c_int64, POINTER(c_int32), POINTER(c_int32), POINTER(ctypes.c_uint8),
+                                             POINTER(ctypes.c_uint8), POINTER(c_int64), POINTER(c_int64), POINTER(c_int32),
+                                             POINTER(c_int32), POINTER(c_int32)]),
     ("ceres_hip_bal_num_effective_parameters", c_int32, [c_void_p, POINTER(c_int64)]),
     ("ceres_hip_bal_destroy", None, [c_void_p]),
     ("ceres_hip_bal_last_error", c_char_p, [c_void_p]),
@@ -951,6 +959,50 @@ def inner_iteration_ordering(num_cameras, num_points, camera_index, point_index,
     return out, ng.value
 
 
+def _constant_mask(which, n, name):
+    """None / an empty sequence -> None; a boolean mask of length n or an array of block indices -> a uint8 mask."""
+    if which is None:
+        return None
+    a = np.asarray(which)
+    if a.size == 0:
+        return None
+    if a.dtype == np.bool_:
+        if a.shape != (n,):
+            raise ValueError(f"{name}: a boolean mask must have {n} entries")
+        return np.ascontiguousarray(a, dtype=np.uint8)
+    idx = a.astype(np.int64).reshape(-1)
+    if idx.min() < 0 or idx.max() >= n:
+        raise ValueError(f"{name}: block index out of range")
+    m = np.zeros(n, dtype=np.uint8)
+    m[idx] = 1
+    return m
+
+
+def _u8p(a):
+    return a.ctypes.data_as(POINTER(ctypes.c_uint8)) if a is not None else None
+
+
+def debug_bal_reduce(num_cameras, num_points, camera_index, point_index, constant_cameras=None, constant_points=None):
+    """ceres_hip_debug_bal_reduce (host code, no device): what ceres_hip_bal_create_with_constant_blocks makes of the problem.
+    Returns (row_observation[num_rows], num_rows_e, camera_column, point_column); HipError with the library's message when refused."""
+    lib = load_library()
+    cam = np.ascontiguousarray(camera_index, dtype=np.int32) if camera_index is not None else None
+    pt = np.ascontiguousarray(point_index, dtype=np.int32) if point_index is not None else None
+    no = int(cam.shape[0]) if cam is not None else (int(pt.shape[0]) if pt is not None else 0)
+    cm = _constant_mask(constant_cameras, int(num_cameras), "constant_cameras")
+    pm = _constant_mask(constant_points, int(num_points), "constant_points")
+    rows = np.empty(max(no, 1), dtype=np.int32)
+    ccol = np.empty(max(int(num_cameras), 1), dtype=np.int32)
+    pcol = np.empty(max(int(num_points), 1), dtype=np.int32)
+    nr, ne = c_int64(), c_int64()
+    i32 = lambda a: a.ctypes.data_as(POINTER(c_int32)) if a is not None else None
+    rc = lib.ceres_hip_debug_bal_reduce(int(num_cameras), int(num_points), no, i32(cam), i32(pt), _u8p(cm), _u8p(pm), byref(nr), byref(ne),
+                                        i32(rows), i32(ccol), i32(pcol))
+    if rc != 0:
+        raise HipError(f"ceres_hip error {rc}: {lib.ceres_hip_bal_last_error(None).decode()}")
+    return rows[:nr.value].copy(), ne.value, ccol[:int(num_cameras)], pcol[:int(num_points)]
+
+
 class BalProblem:
     """Bundle adjustment in BAL form on the device: the Evaluator of the reduced,
     Schur-ordered program (internal/ceres/evaluator.h:98-158) for the Snavely reprojection error
@@ -963,10 +1015,15 @@ class BalProblem:
     camera_model = "angle_axis" (the default), "quaternion" (bundle_adjuster --use_quaternions: cameras [q_w q_x q_y q_z | t | f k1 k2],
     Euclidean Plus) or "quaternion_manifold" (--use_quaternions --use_manifolds: QuaternionManifold on q) — or a CAMERA_* number.  The
     state is ambient (num_parameters: 10 per quaternion camera); gradients are tangent (num_effective_parameters: 9 per camera with
-    the manifold)."""
+    the manifold).
+
+    constant_cameras / constant_points (Problem::SetParameterBlockConstant): index arrays or boolean masks of the blocks to hold fixed;
+    None or empty takes the entry points above.  The state keeps its full layout (constant blocks are read, never written); the
+    gradient, the Jacobian's columns and minimize's step are the reduced program's — free points, then free cameras, ascending — see
+    ceres_hip_bal_create_with_constant_blocks in include/ceres_hip.h, `reduced_sizes` and `fixed_cost`."""
 
     def __init__(self, options: LinearSolverOptions, num_cameras, num_points, camera_index, point_index, observations,
-                 camera_model="angle_axis"):
+                 camera_model="angle_axis", constant_cameras=None, constant_points=None):
         self._lib = load_library()
         self.options = options
         if isinstance(camera_model, str):
@@ -986,7 +1043,13 @@ class BalProblem:
                      int(options.force_generic_path), options.cg_check_interval, options.jacobian_storage,
                      options.max_num_spse_iterations, int(options.use_spse_initialization), options.spse_tolerance,
                      int(options.use_explicit_schur_complement), int(options.visibility_clustering_type))
-        if self.camera_model == CAMERA_ANGLE_AXIS:
+        cm = _constant_mask(constant_cameras, self.num_cameras, "constant_cameras")
+        pm = _constant_mask(constant_points, self.num_points, "constant_points")
+        if cm is not None or pm is not None:
+            self._h = self._lib.ceres_hip_bal_create_with_constant_blocks(byref(c), self.camera_model, self.num_cameras, self.num_points,
+                                                                          self.num_observations, cam.ctypes.data_as(POINTER(c_int32)),
+                                                                          pt.ctypes.data_as(POINTER(c_int32)), _p(obs), _u8p(cm), _u8p(pm))
+        elif self.camera_model == CAMERA_ANGLE_AXIS:
             self._h = self._lib.ceres_hip_bal_create(byref(c), self.num_cameras, self.num_points, self.num_observations,
                                                      cam.ctypes.data_as(POINTER(c_int32)), pt.ctypes.data_as(POINTER(c_int32)),
                                                      _p(obs))
@@ -1002,6 +1065,7 @@ class BalProblem:
         self.num_parameters, self.num_residuals, self.num_jacobian_values = n.value, m.value, v.value
         self.num_effective_parameters = t.value
         self.camera_state_size = 9 if self.camera_model == CAMERA_ANGLE_AXIS else 10
+        self.num_rows = self.num_residuals // 2   # (= num_observations without constant blocks)
 
     @classmethod
     def from_file(cls, options: LinearSolverOptions, filename, camera_model="angle_axis"):
@@ -1034,9 +1098,10 @@ class BalProblem:
 
     def preconditioner_blocks(self, not_inverted=False):
         """The block-diagonal preconditioner of the LAST linear solve inside minimize (camera blocks; CGNR: point blocks first)."""
-        w = self.num_effective_parameters - 3 * self.num_points
-        w //= max(1, self.num_cameras)
-        n = w * w * self.num_cameras + (9 * self.num_points if self.options.type == CGNR else 0)
+        _, _, _, nfc, nfp = self.reduced_sizes()
+        w = self.num_effective_parameters - 3 * nfp
+        w //= max(1, nfc)
+        n = w * w * nfc + (9 * nfp if self.options.type == CGNR else 0)
         out = np.full(n, np.nan)
         inner = self._lib.ceres_hip_bal_linear_solver(self._h)
         rc = self._lib.ceres_hip_get_preconditioner_blocks(inner, int(not_inverted), _p(out), n)
@@ -1051,8 +1116,22 @@ class BalProblem:
         self._check(self._lib.ceres_hip_debug_bal_evaluate_tiles_timing(self._h, _p(x), int(flags), int(iters), _p(out)))
         return float(out[0])
 
+    def reduced_sizes(self):
+        """(rows kept, rows with an E cell — they come first —, rows removed because both blocks are constant, free cameras, free points)."""
+        a, b, c = c_int64(), c_int64(), c_int64()
+        d, e = c_int32(), c_int32()
+        self._check(self._lib.ceres_hip_bal_reduced_sizes(self._h, byref(a), byref(b), byref(c), byref(d), byref(e)))
+        return a.value, b.value, c.value, d.value, e.value
+
+    def fixed_cost(self, state):
+        """Solver::Summary::fixed_cost at state: the removed rows' cost with the loss in force (minimize's costs include it)."""
+        x = _f64(state, self.num_parameters)
+        out = np.zeros(1)
+        self._check(self._lib.ceres_hip_bal_fixed_cost(self._h, _p(x), _p(out)))
+        return float(out[0])
+
     def row_order(self):
-        out = np.empty(self.num_observations, dtype=np.int32)
+        out = np.empty(self.num_rows, dtype=np.int32)
         self._check(self._lib.ceres_hip_bal_get_row_order(self._h, out.ctypes.data_as(POINTER(c_int32))))
         return out
 

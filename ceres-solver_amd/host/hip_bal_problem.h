@@ -96,7 +96,15 @@ class HipBalProblem {
  public:
   // camera_model: CERES_HIP_CAMERA_* (bundle_adjuster --use_quaternions [--use_manifolds]: QUATERNION [_MANIFOLD]); BalData::State(camera_model)
   // is the matching state
-  HipBalProblem(const LinearSolver::Options& options, const BalData& d, int camera_model = CERES_HIP_CAMERA_ANGLE_AXIS) {
+  // camera_is_constant / point_is_constant (Problem::SetParameterBlockConstant; ParameterBlock::IsConstant() per block): empty = none
+  // constant, else one entry per camera / point, non-zero = constant.  With any entry the handle is the reduced program
+  // (ceres_hip_bal_create_with_constant_blocks): the state keeps its full layout, the gradient and the Jacobian's columns are the free
+  // blocks' (ReducedSizes); without, the entry point this class always used.
+  HipBalProblem(const LinearSolver::Options& options, const BalData& d, int camera_model = CERES_HIP_CAMERA_ANGLE_AXIS,
+                const std::vector<uint8_t>& camera_is_constant = {}, const std::vector<uint8_t>& point_is_constant = {}) {
+    if ((!camera_is_constant.empty() && camera_is_constant.size() != size_t(d.num_cameras)) ||
+        (!point_is_constant.empty() && point_is_constant.size() != size_t(d.num_points)))
+      throw std::invalid_argument("HipBalProblem: a constant-block mask has one entry per block");
     ceres_hip_options o{};
     o.solver_type = options.type;
     o.preconditioner_type = options.preconditioner_type;
@@ -104,9 +112,15 @@ class HipBalProblem {
     o.max_num_iterations = options.max_num_iterations;
     o.residual_reset_period = options.residual_reset_period;
     o.device = options.device;
-    handle_ = ceres_hip_bal_create_with_camera(&o, camera_model, d.num_cameras, d.num_points, int64_t(d.camera_index.size()),
-                                               d.camera_index.data(), d.point_index.data(), d.observations.data());
-    if (!handle_) throw std::runtime_error(std::string("ceres_hip_bal_create_with_camera: ") + ceres_hip_bal_last_error(nullptr));
+    if (camera_is_constant.empty() && point_is_constant.empty())
+      handle_ = ceres_hip_bal_create_with_camera(&o, camera_model, d.num_cameras, d.num_points, int64_t(d.camera_index.size()),
+                                                 d.camera_index.data(), d.point_index.data(), d.observations.data());
+    else
+      handle_ = ceres_hip_bal_create_with_constant_blocks(&o, camera_model, d.num_cameras, d.num_points, int64_t(d.camera_index.size()),
+                                                          d.camera_index.data(), d.point_index.data(), d.observations.data(),
+                                                          camera_is_constant.empty() ? nullptr : camera_is_constant.data(),
+                                                          point_is_constant.empty() ? nullptr : point_is_constant.data());
+    if (!handle_) throw std::runtime_error(std::string(ceres_hip_bal_last_error(nullptr)));
     ceres_hip_bal_sizes(handle_, &num_parameters_, &num_residuals_, &num_jacobian_values_);
     ceres_hip_bal_num_effective_parameters(handle_, &num_effective_parameters_);
   }
@@ -117,6 +131,19 @@ class HipBalProblem {
   int NumParameters() const { return int(num_parameters_); }   // Evaluator::NumParameters, I/evaluator.h:151
   int NumResiduals() const { return int(num_residuals_); }     // Evaluator::NumResiduals, :158
   int NumEffectiveParameters() const { return int(num_effective_parameters_); }   // Evaluator::NumEffectiveParameters: the gradient's length
+  // What Program::RemoveFixedBlocks left: rows kept, rows with an E cell (they come first), rows removed (both blocks constant), free
+  // cameras, free points; any pointer may be null
+  bool ReducedSizes(int64_t* num_rows, int64_t* num_rows_e, int64_t* num_rows_removed, int32_t* num_free_cameras, int32_t* num_free_points) const {
+    return ceres_hip_bal_reduced_sizes(handle_, num_rows, num_rows_e, num_rows_removed, num_free_cameras, num_free_points) == CERES_HIP_OK;
+  }
+  // Solver::Summary::fixed_cost at state: the removed rows' cost with the loss in force (Minimize's costs include it)
+  bool FixedCost(const double* state, double* fixed_cost) { return ceres_hip_bal_fixed_cost(handle_, state, fixed_cost) == CERES_HIP_OK; }
+  // row_observation[r] = the observation of kept row r (NumResiduals() / 2 entries)
+  std::vector<int32_t> RowOrder() const {
+    std::vector<int32_t> rows(size_t(num_residuals_ / 2));
+    if (ceres_hip_bal_get_row_order(handle_, rows.data()) != CERES_HIP_OK) throw std::runtime_error("ceres_hip_bal_get_row_order");
+    return rows;
+  }
   // The loss of every residual block, ScaledLoss(loss, scale): loss_type CERES_HIP_LOSS_*, a / b its constructor arguments
   // (bundle_adjuster --robustify: SetLoss(CERES_HIP_LOSS_HUBER, 1.0)).  Applies to the later Evaluate / Minimize calls.
   void SetLoss(int loss_type, double a, double b = 1.0, double scale = 1.0) {

@@ -485,6 +485,45 @@ ceres_hip_bal* ceres_hip_bal_create(const ceres_hip_options* options, int32_t nu
 ceres_hip_bal* ceres_hip_bal_create_with_camera(const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras,
                                                 int32_t num_points, int64_t num_observations, const int32_t* camera_index,
                                                 const int32_t* point_index, const double* observations);
+/* ceres_hip_bal_create_with_camera for a Problem in which SetParameterBlockConstant was called on some cameras and points: the handle
+ * is the REDUCED program Program::RemoveFixedBlocks leaves (I/program.cc:309-410), Schur-ordered.
+ * camera_is_constant[num_cameras], point_is_constant[num_points]: non-zero = constant; either may be NULL (none constant).  The masks
+ * are creation-time: one handle sees one sparsity (I/linear_solver.h:137-142), and the block structure depends on them.
+ *   - The caller's STATE keeps its full layout and length [3 per point | cs per camera] (ceres_hip_bal_sizes' first value).  Constant
+ *     blocks are read, never written: after ceres_hip_bal_minimize / ceres_hip_bal_inner_iterate their doubles are bit-identical.
+ *   - The TANGENT side is the reduced program's: ceres_hip_bal_num_effective_parameters = 3 free points + cw free cameras; gradient,
+ *     step, Jacobi scale and the Jacobian's columns are [free points in ascending index | free cameras in ascending index];
+ *     num_eliminate_blocks = free points.
+ *   - ROWS: an observation whose camera and point are both constant is removed (its cost is the fixed cost).  The others are grouped
+ *     by point, stable in observation order, the rows of constant points (no E cell) AFTER all rows that have one, stable in
+ *     observation order (the last bucket of LexicographicallyOrderResidualBlocks, I/reorder_program.cc:278-340).
+ *     ceres_hip_bal_get_row_order writes num_rows entries; ceres_hip_bal_sizes reports 2 num_rows residuals and the reduced number of
+ *     Jacobian values.
+ *   - JACOBIAN VALUES as BlockJacobianWriter lays out the reduced program: all E cells first (6 per row with a free point, in row
+ *     order), then the F cells (2 cw per row with a free camera, in row order).  A row has one cell or two.
+ *   - COST: ceres_hip_bal_evaluate is the Evaluator of the reduced program (kept rows only).  ceres_hip_bal_minimize reports what
+ *     TrustRegionMinimizer reports: initial_cost, final_cost and every iterations[i].cost INCLUDE the fixed cost
+ *     (I/trust_region_minimizer.cc:127, 228, 261, 490); the function-tolerance test and the relative decrease use the reduced
+ *     program's cost alone.  The fixed cost is evaluated once per minimize call, on the device, with the loss in force.
+ *   - Inner iterations: constant blocks are in no group (block_iterations = -1: a block outside the ordering); a free block's own loop
+ *     still sees ALL its observations, the ones against constant blocks included.
+ *   - With both masks NULL or all zero the handle is the one ceres_hip_bal_create_with_camera builds.
+ * NULL (message in ceres_hip_bal_last_error(NULL)), before any device call: no free camera or no free point (Ceres switches the linear
+ * solver there — LinearSolverForZeroEBlocks, I/linear_solver.cc:51, I/trust_region_preprocessor.cc:89 — which this front end does not), and what
+ * ceres_hip_bal_create_with_camera refuses.  ceres_hip_bal_minimize on a sharded handle with constant blocks: CERES_HIP_E_UNSUPPORTED.
+ * Constant cameras alone keep the tile-order evaluator of the fused path; constant points leave rows without an E cell (the remainder
+ * kernels) and the loop evaluates in the caller layout. */
+ceres_hip_bal* ceres_hip_bal_create_with_constant_blocks(const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras,
+                                                         int32_t num_points, int64_t num_observations, const int32_t* camera_index,
+                                                         const int32_t* point_index, const double* observations,
+                                                         const uint8_t* camera_is_constant, const uint8_t* point_is_constant);
+/* What the reduction made of the problem (all NULL-able): rows kept, rows with an E cell (they come first), rows dropped because both
+ * blocks are constant, free cameras, free points. */
+int ceres_hip_bal_reduced_sizes(const ceres_hip_bal* p, int64_t* num_rows, int64_t* num_rows_e, int64_t* num_rows_removed,
+                                int32_t* num_free_cameras, int32_t* num_free_points);
+/* Solver::Summary::fixed_cost: 1/2 sum rho(|r|^2) over the removed rows at `state` (full layout), with the handle's current loss
+ * (0 when no row was removed). */
+int ceres_hip_bal_fixed_cost(ceres_hip_bal* p, const double* state, double* fixed_cost);
 void ceres_hip_bal_destroy(ceres_hip_bal* p);
 const char* ceres_hip_bal_last_error(const ceres_hip_bal* p);
 /* The linear solver this problem drives (borrowed; operators, timing, info). */
@@ -656,6 +695,14 @@ int ceres_hip_debug_plan(const ceres_hip_block_structure* bs, int32_t num_elimin
 int ceres_hip_debug_inner_iteration_ordering(int32_t num_cameras, int32_t num_points, int64_t num_observations, const int32_t* camera_index,
                                              const int32_t* point_index, int32_t blocks, int32_t* group_of_block, int32_t* num_groups);
 
+/* Host-only (no device, like ceres_hip_debug_cluster_cameras): the reduction ceres_hip_bal_create_with_constant_blocks makes —
+ * row_observation[*num_rows] (room for num_observations entries), camera_column[num_cameras] / point_column[num_points] = index of the
+ * block among the free ones or -1.  CERES_HIP_E_INVALID (message in ceres_hip_bal_last_error(NULL)): NULL index arrays, an index out
+ * of range, no free camera, no free point. */
+int ceres_hip_debug_bal_reduce(int32_t num_cameras, int32_t num_points, int64_t num_observations, const int32_t* camera_index,
+                               const int32_t* point_index, const uint8_t* camera_is_constant, const uint8_t* point_is_constant,
+                               int64_t* num_rows, int64_t* num_rows_e, int32_t* row_observation, int32_t* camera_column,
+                               int32_t* point_column);
 /* Debug: the camera clustering of CLUSTER_JACOBI (csrc/visibility.cc; pure host code): membership[num_col_blocks - num_eliminate_blocks]
  * = the cluster of every F block, *num_clusters = their number (clusters numbered by ascending first member; the tie-break rule is
  * stated at ceres_hip_options.visibility_clustering_type).  CERES_HIP_E_INVALID for NULL pointers, a structure AnalyzeStructure

@@ -8,7 +8,10 @@ composed restatement (tests/frontend_reference.py): the evaluation, one inner pa
 (test_gpu_frontend_matrix.edge_scene; the loop's costs, radii and state compared only where the restatement's own sensitivity to the
 Jacobian's rounding, measured per case, allows: see EDGE_ILL_CONDITIONED), and the loop on a random clean scene (clean_scene).  One
 JSON line per case, then the worst deviation of every check.
-usage: fuzz_frontend.py [first_seed] [count] [--variants]"""
+--masks: --variants with constant cameras and points drawn too (ceres_hip_bal_create_with_constant_blocks), with the checks of
+tests/test_gpu_constant_blocks.py against tests/constant_blocks_reference.py: the evaluation, the fixed cost and one inner pass on a random
+edge scene, the loop on a random clean scene (no case is excluded there).
+usage: fuzz_frontend.py [first_seed] [count] [--variants | --masks]"""
 import json
 import os
 import sys
@@ -129,16 +132,58 @@ def run_variant(seed):
                 seconds=round(time.time() - t0, 2))
 
 
+def run_masked(seed):
+    import test_gpu_constant_blocks as T
+    import test_gpu_frontend_matrix as M
+    rng = np.random.default_rng(500009 * seed + 7)
+    while True:
+        case = tuple(levels[int(rng.integers(len(levels)))] for _, levels in M.FACTORS)
+        if M.allowed(case):
+            break
+    shape = dict(npts=int(rng.choice([90, 120, 160, 200])), track=int(rng.integers(5, 11)))
+    t0 = time.time()
+    sc = None
+    for k in range(5):
+        try:
+            sc = M.edge_scene(oracle, seed=seed * 10 + k + 1, **shape)
+            break
+        except AssertionError:
+            continue
+    if sc is None:
+        return dict(seed=seed, case=M.case_id(case), **shape, ok=False, error="no edge scene in five draws")
+    loop_sc = M.clean_scene(oracle, seed=seed + 1)
+    c = dict(zip(M.NAMES, case))
+    for name, v in (("CERES_HIP_EVAL_TILES", c["tiles"]), ("CERES_HIP_INNER_FORM", c["inner_form"])):
+        if v is None:
+            os.environ.pop(name, None)
+        else:
+            os.environ[name] = v
+    p_cam, p_pt = float(rng.choice([0.0, 0.05, 0.3])), float(rng.choice([0.0, 0.02, 0.3]))
+    dev, drawn = {}, {}
+    for key, scene, loop in (("edge", sc, False), ("clean", loop_sc, True)):
+        cc = np.flatnonzero(rng.random(scene[0]) < p_cam)[:scene[0] - 1]   # (at least one camera and one point stay free)
+        cp = np.flatnonzero(rng.random(scene[1]) < p_pt)[:scene[1] - 1]
+        if rng.random() < 0.3:
+            cc = np.union1d(cc, [0])
+        drawn[key] = [int(cc.size), int(cp.size)]
+        dev.update(T.one_side(hip, oracle, scene, ((cc.tolist(), cp.tolist()), case), loop=loop))
+    lim = {k: v for k, v in T.cb_limits(("none", case)).items() if not k.startswith("edge_")}
+    bad = M.exceeded(dev, lim)
+    return dict(seed=seed, case=M.case_id(case), constant=drawn, **shape, ok=not bad, bad=bad,
+                dev={k: (float(v) if isinstance(v, (int, float, np.floating)) else v) for k, v in dev.items()}, seconds=round(time.time() - t0, 2))
+
+
 def main():
     args = [a for a in sys.argv[1:] if not a.startswith("--")]
     first = int(args[0]) if args else 0
     count = int(args[1]) if len(args) > 1 else 40
-    variants = "--variants" in sys.argv
+    masks = "--masks" in sys.argv
+    variants = "--variants" in sys.argv or masks
     failed = 0
     worst = {}
     for seed in range(first, first + count):
         try:
-            r = run_variant(seed) if variants else run_case(seed)
+            r = run_masked(seed) if masks else run_variant(seed) if variants else run_case(seed)
             for k, v in r.get("dev", {}).items():
                 if isinstance(v, float) and not (worst.get(k, (-1.0,))[0] >= v):
                     worst[k] = (v, r["case"])
