@@ -6,6 +6,7 @@
 //   ceres_hip_bal_minimize  = TrustRegionMinimizer::Minimize   I/trust_region_minimizer.cc:68-845
 //                             with LevenbergMarquardtStrategy  I/levenberg_marquardt_strategy.cc:69-157
 //                             or DoglegStrategy                I/dogleg_strategy.cc (dogleg.inc)
+//   ceres_hip_bal_minimize_line_search = LineSearchMinimizer::Minimize   I/line_search_minimizer.cc (line_search.inc)
 // The loop below follows the reference statement by statement (the same restatement as
 // oracle/bal_harness.cc, which is what the parity tests compare it with); only the places
 // where vectors live differ: everything of size num_parameters / num_residuals stays in HBM.
@@ -61,8 +62,11 @@ struct ceres_hip_bal {
   int64_t* d_free_block = nullptr;             // BalFreeBlocks::block
   int32_t *d_pack_cam = nullptr, *d_pack_scale = nullptr;   // BalEvalTilesArgs' camera records (constant cameras on the tile path)
   double2* d_scrap = nullptr;
+  // ceres_hip_bal_evaluate_gradient / ceres_hip_bal_minimize_line_search (line_search.inc): their lists and vectors, made on first use
+  struct BalLineSearch* ls = nullptr;
 };
 void bal_inner_free(ceres_hip_bal* p);
+void bal_ls_free(ceres_hip_bal* p);
 
 namespace {
 
@@ -245,6 +249,7 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 #include "constant_blocks.inc"
 #include "inner_iterations.inc"
 #include "dogleg.inc"
+#include "line_search.inc"
 
 extern "C" {
 
@@ -273,6 +278,7 @@ void ceres_hip_bal_destroy(ceres_hip_bal* p) {
   if (!p) return;
   if (p->h_parts) (void)hipHostFree(p->h_parts);
   bal_inner_free(p);
+  bal_ls_free(p);
   if (p->s) ceres_hip_destroy(p->s);  // frees every device allocation made through dev_alloc
   delete p;
 }

@@ -689,5 +689,69 @@ struct InnerArgs {
 };
 hipError_t LaunchInnerBlocks(const InnerArgs& A, int form, hipStream_t stream);
 
+// ---- line search minimizer of the BAL front end (kernels_line_search.hip, kernels_line_search_quat.hip; line_search.inc) ----
+// Cost and gradient without a Jacobian in memory (line_search_gradient.h states the two passes and the order of every sum).
+constexpr int kLsChunkPitch = 10;   // doubles per chunk partial of the camera pass (the widest camera)
+struct LsGradArgs {
+  int64_t n_rows = 0;                  // the rows of BalEvalArgs, grouped by point
+  const int32_t *row_cam = nullptr, *row_pt = nullptr;
+  const double2* row_obs = nullptr;
+  const int32_t* row_pdst = nullptr;   // where the row's point starts in the tangent vector, -1: a constant point
+  const double* state = nullptr;
+  int64_t cam_base = 0;
+  double* grad = nullptr;              // tangent: free points, then free cameras
+  double* cost_partials = nullptr;     // one per workgroup of the point pass (<= 2048)
+  double* wave_parts = nullptr;        // 6 per chunk of 64 rows: the sums of the chunk's first and last run
+  int32_t n_long = 0;                  // points whose rows cross a chunk boundary: tangent position, first and last chunk
+  const int32_t *long_dst = nullptr, *long_w0 = nullptr, *long_w1 = nullptr;
+  // the camera pass: chunks of at most 64 entries of one camera's list; chunk_dst >= 0: the camera's only chunk, its tangent position;
+  // otherwise -(partial + 1)
+  int32_t n_chunks = 0;
+  const int32_t *chunk_cam = nullptr, *chunk_start = nullptr, *chunk_len = nullptr, *chunk_dst = nullptr;
+  const int32_t* cm_pt = nullptr;      // point and pixel of every entry of the camera-major list
+  const double2* cm_obs = nullptr;
+  double* chunk_parts = nullptr;       // kLsChunkPitch per partial
+  int32_t n_fin = 0;                   // cameras of more than one chunk: tangent position, first partial, number of partials
+  const int32_t *fin_dst = nullptr, *fin_first = nullptr, *fin_count = nullptr;
+  LossParams loss;
+};
+// gradient == false: the cost alone.  *nparts cost partials.
+hipError_t LaunchLsGradient(const LsGradArgs& A, bool gradient, int camera_model, int* nparts, hipStream_t stream);
+hipError_t LaunchLsGradientQuat(const LsGradArgs& A, bool gradient, int camera_model, int grid_points, int grid_cameras, hipStream_t stream);
+// out = Plus(x, t direction) on the free blocks (out's constant blocks are not touched); partials[0 .. g) = |x|^2 over the free blocks,
+// [g .. 2 g) = |out - x|^2 (ambient)
+hipError_t LaunchLsTrialPoint(const BalFreeBlocks& B, int camera_model, const double* x, const double* direction, double t, double* out,
+                              double* partials, int* nparts, hipStream_t stream);
+// x - Plus(x, -g) over the free blocks (EvaluateGradientNorms, I/line_search_minimizer.cc:67-83): partials[0 .. g) = its squared norm,
+// [g .. 2 g) = its max norm
+hipError_t LaunchLsGradientNorms(const BalFreeBlocks& B, int camera_model, const double* x, const double* g, double* partials, int* nparts,
+                                 hipStream_t stream);
+// partials[k g + b], k < 3: workgroup b's share of a.b, a.c (c == nullptr: 0) and its max |a|
+hipError_t LaunchLsDots(const double* a, const double* b, const double* c, int64_t n, double* partials, int* nparts, hipStream_t stream);
+// z = alpha x + beta y - gamma w (y, w may be nullptr)
+hipError_t LaunchLsCombine(double alpha, const double* x, double beta, const double* y, double gamma, const double* w, double* z, int64_t n,
+                           hipStream_t stream);
+
+// L-BFGS on the device (LowRankInverseHessian, I/low_rank_inverse_hessian.cc:87-177): the history and every scalar between the vector
+// operations stay in device memory — an update and a whole two-loop recursion run without a host synchronisation.
+struct LbfgsArgs {
+  int64_t n = 0;
+  int32_t rank = 0, use_scaling = 0;
+  double *S = nullptr, *Y = nullptr;   // rank x n each: delta_x and delta_gradient of slot k at k n
+  double* sy = nullptr;                // per slot: delta_x . delta_gradient
+  double* alpha = nullptr;             // per slot: the first loop's coefficient
+  double* scale = nullptr;             // approximate_eigenvalue_scale_
+  int32_t* order = nullptr;            // the live slots, oldest first
+  int32_t* count = nullptr;            // how many
+  double* parts = nullptr;             // 4 kMaxVecGrid: two alternating sets of dot partials, then d . g and max |d|
+  int32_t* accepted = nullptr;         // accepted[k] = 1 / 0: what update k did
+};
+hipError_t LaunchLbfgsReset(const LbfgsArgs& A, hipStream_t stream);
+// Update(a sv, y1 - y0) (y0 may be nullptr): the secant test, the circular buffer; accepted[log_index] records the decision
+hipError_t LaunchLbfgsUpdate(const LbfgsArgs& A, double a, const double* sv, const double* y1, const double* y0, int log_index, hipStream_t stream);
+// d = -H g with at most max_live live slots (the caller's bound on *count); parts[2 kMaxVecGrid + b], b < *nparts: d . g partials,
+// parts[3 kMaxVecGrid + b]: max |d| partials
+hipError_t LaunchLbfgsDirection(const LbfgsArgs& A, const double* g, double* d, int max_live, int* nparts, hipStream_t stream);
+
 }  // namespace chip
 #endif

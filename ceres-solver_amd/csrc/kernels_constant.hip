@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "device.h"
+#include "quaternion_plus.h"
 
 namespace chip {
 
@@ -21,22 +22,6 @@ __device__ __forceinline__ double wave_max_c(double v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
   return v;
-}
-
-// QuaternionPlusImpl (I/manifold.cc), as in kernels_quaternion.hip
-__device__ __forceinline__ void quaternion_plus_c(const double (&q)[4], double d0, double d1, double d2, double (&out)[4]) {
-  const double nd = norm3d(d0, d1, d2);
-  if (nd == 0.0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = q[k];
-    return;
-  }
-  const double s = sin(nd) / nd;
-  const double z[4] = {cos(nd), s * d0, s * d1, s * d2};
-  out[0] = z[0] * q[0] - z[1] * q[1] - z[2] * q[2] - z[3] * q[3];
-  out[1] = z[0] * q[1] + z[1] * q[0] + z[2] * q[3] - z[3] * q[2];
-  out[2] = z[0] * q[2] - z[1] * q[3] + z[2] * q[0] + z[3] * q[1];
-  out[3] = z[0] * q[3] + z[1] * q[2] - z[2] * q[1] + z[3] * q[0];
 }
 
 // CM: the camera model — SW state doubles, CW tangent entries per camera; the manifold's Plus on q, x + delta everywhere else
@@ -75,7 +60,7 @@ __global__ __launch_bounds__(kVecBlock) void bal_candidate_free_kernel(BalFreeBl
       double q[4], qp[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) { q[k] = x[a + k]; xn += q[k] * q[k]; }
-      quaternion_plus_c(q, d[0], d[1], d[2], qp);
+      quaternion_plus(q, d[0], d[1], d[2], qp);
 #pragma unroll
       for (int k = 0; k < 4; ++k) cand[a + k] = qp[k];
 #pragma unroll
@@ -122,7 +107,7 @@ __global__ __launch_bounds__(kVecBlock) void bal_gradient_max_quat_free_kernel(B
     double q[4], qp[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) q[k] = x[a + k];
-    quaternion_plus_c(q, -gt[0], -gt[1], -gt[2], qp);
+    quaternion_plus(q, -gt[0], -gt[1], -gt[2], qp);
 #pragma unroll
     for (int k = 0; k < 4; ++k) m = fmax(m, fabs(q[k] - qp[k]));
 #pragma unroll

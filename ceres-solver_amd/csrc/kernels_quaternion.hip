@@ -7,6 +7,7 @@
 
 #include "bal_evaluate.h"
 #include "device.h"
+#include "quaternion_plus.h"
 
 namespace chip {
 
@@ -21,23 +22,6 @@ __device__ __forceinline__ double wave_max_q(double v) {
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
   return v;
-}
-
-// QuaternionPlusImpl (I/manifold.cc): [cos |d|, sin |d| / |d| d] (x) q, the product of include/ceres/rotation.h's QuaternionProduct;
-// q itself when |d| is exactly zero
-__device__ __forceinline__ void quaternion_plus(const double (&q)[4], double d0, double d1, double d2, double (&out)[4]) {
-  const double nd = norm3d(d0, d1, d2);
-  if (nd == 0.0) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = q[k];
-    return;
-  }
-  const double s = sin(nd) / nd;
-  const double z[4] = {cos(nd), s * d0, s * d1, s * d2};
-  out[0] = z[0] * q[0] - z[1] * q[1] - z[2] * q[2] - z[3] * q[3];
-  out[1] = z[0] * q[1] + z[1] * q[0] + z[2] * q[3] - z[3] * q[2];
-  out[2] = z[0] * q[2] - z[1] * q[3] + z[2] * q[0] + z[3] * q[1];
-  out[3] = z[0] * q[3] + z[1] * q[2] - z[2] * q[1] + z[3] * q[0];
 }
 
 // bal_candidate_kernel for quaternion-manifold cameras: delta = step .* scale (tangent: 9 per camera), candidate = Plus(x, delta)

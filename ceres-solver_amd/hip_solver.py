@@ -229,6 +229,59 @@ ABI += [
 ]
 
 
+# ---- the line search minimizer (include/ceres_hip.h: ceres_hip_line_search_*) ----
+STEEPEST_DESCENT, NONLINEAR_CONJUGATE_GRADIENT, LBFGS, BFGS = 0, 1, 2, 3
+FLETCHER_REEVES, POLAK_RIBIERE, HESTENES_STIEFEL = 0, 1, 2
+ARMIJO, WOLFE = 0, 1
+BISECTION, QUADRATIC, CUBIC = 0, 1, 2
+
+
+class CLineSearchOptions(ctypes.Structure):
+    _fields_ = [("max_num_iterations", c_int32), ("line_search_direction_type", c_int32), ("nonlinear_conjugate_gradient_type", c_int32),
+                ("max_lbfgs_rank", c_int32), ("use_approximate_eigenvalue_bfgs_scaling", c_int32), ("line_search_type", c_int32),
+                ("line_search_interpolation_type", c_int32), ("max_num_line_search_step_size_iterations", c_int32),
+                ("max_num_line_search_direction_restarts", c_int32), ("reserved", c_int32), ("min_line_search_step_size", c_double),
+                ("line_search_sufficient_function_decrease", c_double), ("max_line_search_step_contraction", c_double),
+                ("min_line_search_step_contraction", c_double), ("line_search_sufficient_curvature_decrease", c_double),
+                ("max_line_search_step_expansion", c_double), ("function_tolerance", c_double), ("gradient_tolerance", c_double),
+                ("parameter_tolerance", c_double)]
+
+
+class CLineSearchIteration(ctypes.Structure):
+    _fields_ = [("cost", c_double), ("cost_change", c_double), ("gradient_max_norm", c_double), ("gradient_norm", c_double),
+                ("step_norm", c_double), ("step_size", c_double), ("line_search_function_evaluations", c_int32),
+                ("line_search_gradient_evaluations", c_int32), ("line_search_iterations", c_int32), ("reserved", c_int32)]
+
+
+class CLineSearchSummary(ctypes.Structure):
+    _fields_ = [("initial_cost", c_double), ("final_cost", c_double), ("num_iterations", c_int32), ("num_successful_steps", c_int32),
+                ("num_line_search_steps", c_int32), ("num_line_search_direction_restarts", c_int32), ("num_function_evaluations", c_int32),
+                ("num_gradient_evaluations", c_int32), ("termination_type", c_int32), ("num_iterations_logged", c_int32),
+                ("evaluation_seconds", c_double), ("direction_seconds", c_double), ("total_seconds", c_double),
+                ("lbfgs_history_bytes", c_int64), ("iterations", CLineSearchIteration * MAX_LOGGED_ITERATIONS),
+                ("message", ctypes.c_char * 256)]
+
+
+class CLineSearchResult(ctypes.Structure):
+    _fields_ = [("success", c_int32), ("num_function_evaluations", c_int32), ("num_gradient_evaluations", c_int32),
+                ("num_iterations", c_int32), ("optimal_step_size", c_double), ("optimal_value", c_double), ("error", ctypes.c_char * 512)]
+
+
+UNIVARIATE_FN = ctypes.CFUNCTYPE(c_int32, c_double, c_int32, _DP, _DP, c_void_p)
+
+ABI += [
+    ("ceres_hip_line_search_default_options", None, [POINTER(CLineSearchOptions)]),
+    ("ceres_hip_bal_evaluate_gradient", c_int32, [c_void_p, _DP, _DP, _DP]),
+    ("ceres_hip_bal_minimize_line_search", c_int32, [c_void_p, POINTER(CLineSearchOptions), _DP, POINTER(CLineSearchSummary)]),
+    # (the callback — a UNIVARIATE_FN — travels as a plain pointer, so that NULL can be passed like every other pointer)
+    ("ceres_hip_debug_line_search", c_int32, [POINTER(CLineSearchOptions), c_void_p, c_void_p, c_double, c_double, c_double,
+                                              POINTER(CLineSearchResult)]),
+    ("ceres_hip_debug_minimize_interpolating_polynomial", c_int32, [c_int32, _DP, _DP, POINTER(c_int32), _DP, POINTER(c_int32), c_double,
+                                                                    c_double, _DP, _DP, _DP]),
+    ("ceres_hip_debug_lbfgs_direction", c_int32, [c_int64, c_int32, c_int32, c_int32, _DP, _DP, _DP, _DP, POINTER(c_int32)]),
+]
+
+
 def load_library():
     """dlopen csrc/libceres_hip.so and bind every ABI symbol; raises if anything is missing."""
     global _lib
@@ -944,6 +997,71 @@ def dogleg_subspace_minimum(B, g, radius):
     return rc, x
 
 
+def line_search_options(**opts) -> CLineSearchOptions:
+    """ceres_hip_line_search_default_options with the given fields replaced."""
+    o = CLineSearchOptions()
+    load_library().ceres_hip_line_search_default_options(byref(o))
+    for k, val in opts.items():
+        if not hasattr(o, k):
+            raise TypeError(f"unknown line search option {k}")
+        setattr(o, k, val)
+    return o
+
+
+def debug_line_search(fn, step_size_estimate, initial_cost, initial_gradient, **opts) -> CLineSearchResult:
+    """ceres_hip_debug_line_search: one LineSearch::Search on fn(x, want_gradient) -> (value, gradient) or None (an invalid sample)."""
+    lib = load_library()
+    o = line_search_options(**opts)
+
+    def trampoline(x, want_gradient, value, gradient, user):
+        r = fn(x, bool(want_gradient))
+        if r is None:
+            return 1
+        value[0] = r[0]
+        gradient[0] = r[1]
+        return 0
+    out = CLineSearchResult()
+    cb = UNIVARIATE_FN(trampoline)   # (kept alive until the call returns)
+    rc = lib.ceres_hip_debug_line_search(byref(o), ctypes.cast(cb, c_void_p), None, float(step_size_estimate), float(initial_cost),
+                                         float(initial_gradient), byref(out))
+    if rc != 0:
+        raise HipError(f"ceres_hip_debug_line_search: error {rc}: {lib.ceres_hip_bal_last_error(None).decode()}")
+    return out
+
+
+def debug_minimize_interpolating_polynomial(x, value, value_valid, gradient, gradient_valid, x_min, x_max):
+    """ceres_hip_debug_minimize_interpolating_polynomial: (optimal_x, optimal_value, coefficients — highest power first)."""
+    lib = load_library()
+    xs = np.ascontiguousarray(x, dtype=np.float64)
+    v = np.ascontiguousarray(value, dtype=np.float64)
+    g = np.ascontiguousarray(gradient, dtype=np.float64)
+    vv = np.ascontiguousarray(value_valid, dtype=np.int32)
+    gv = np.ascontiguousarray(gradient_valid, dtype=np.int32)
+    ox, ov, coef = np.zeros(1), np.zeros(1), np.zeros(6)
+    rc = lib.ceres_hip_debug_minimize_interpolating_polynomial(xs.shape[0], _p(xs), _p(v), vv.ctypes.data_as(POINTER(c_int32)), _p(g),
+                                                               gv.ctypes.data_as(POINTER(c_int32)), float(x_min), float(x_max), _p(ox),
+                                                               _p(ov), _p(coef))
+    if rc != 0:
+        raise HipError(f"ceres_hip_debug_minimize_interpolating_polynomial: error {rc}: {lib.ceres_hip_bal_last_error(None).decode()}")
+    return float(ox[0]), float(ov[0]), coef[:int(vv.astype(bool).sum() + gv.astype(bool).sum())].copy()
+
+
+def debug_lbfgs_direction(rank, delta_x, delta_gradient, gradient, use_scaling=False):
+    """ceres_hip_debug_lbfgs_direction (device 0): (-H gradient, accepted flag per update) for the updates fed in order."""
+    lib = load_library()
+    g = np.ascontiguousarray(gradient, dtype=np.float64)
+    n = g.shape[0]
+    dx = np.ascontiguousarray(delta_x, dtype=np.float64).reshape(-1, n)
+    dg = np.ascontiguousarray(delta_gradient, dtype=np.float64).reshape(-1, n)
+    d = np.empty(n)
+    acc = np.zeros(max(dx.shape[0], 1), dtype=np.int32)
+    rc = lib.ceres_hip_debug_lbfgs_direction(n, int(rank), int(bool(use_scaling)), dx.shape[0], _p(dx), _p(dg), _p(g), _p(d),
+                                             acc.ctypes.data_as(POINTER(c_int32)))
+    if rc != 0:
+        raise HipError(f"ceres_hip_debug_lbfgs_direction: error {rc}: {lib.ceres_hip_bal_last_error(None).decode()}")
+    return d, acc[:dx.shape[0]].copy()
+
+
 def inner_iteration_ordering(num_cameras, num_points, camera_index, point_index, blocks="automatic"):
     """ceres_hip_debug_inner_iteration_ordering: (group of every block in state order — points, then cameras; -1 outside —, groups)."""
     lib = load_library()
@@ -1225,4 +1343,20 @@ class BalProblem:
         x = _f64(state, self.num_parameters).copy()
         S = CMinimizerSummary()
         self._check(self._lib.ceres_hip_bal_minimize(self._h, byref(o), _p(x), byref(S)))
+        return x, S
+
+    def evaluate_gradient(self, state, gradient=True):
+        """Evaluator::Evaluate(state, cost, nullptr, gradient, nullptr) without a Jacobian in memory: (cost, tangent gradient | None)."""
+        x = _f64(state, self.num_parameters)
+        cost = np.zeros(1)
+        g = np.empty(self.num_effective_parameters) if gradient else None
+        self._check(self._lib.ceres_hip_bal_evaluate_gradient(self._h, _p(x), _p(cost), _p(g)))
+        return float(cost[0]), g
+
+    def minimize_line_search(self, state, **opts):
+        """LineSearchMinimizer::Minimize (L-BFGS with a Wolfe line search by default).  Returns (state, CLineSearchSummary)."""
+        o = line_search_options(**opts)
+        x = _f64(state, self.num_parameters).copy()
+        S = CLineSearchSummary()
+        self._check(self._lib.ceres_hip_bal_minimize_line_search(self._h, byref(o), _p(x), byref(S)))
         return x, S

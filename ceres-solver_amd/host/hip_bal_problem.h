@@ -182,6 +182,19 @@ class HipBalProblem {
       throw std::runtime_error(std::string("ceres_hip_bal_minimize: ") + ceres_hip_bal_last_error(handle_));
     return s;
   }
+  // Evaluator::Evaluate(state, cost, nullptr, gradient, nullptr) without a Jacobian in memory; gradient (NumEffectiveParameters()
+  // doubles) may be null: the cost alone
+  bool EvaluateGradient(const double* state, double* cost, double* gradient) {
+    return ceres_hip_bal_evaluate_gradient(handle_, state, cost, gradient) == CERES_HIP_OK;
+  }
+  // LineSearchMinimizer::Minimize (Solver::Options::minimizer_type = LINE_SEARCH; bundle_adjuster --line_search); state in/out.
+  // Options from ceres_hip_line_search_default_options; an invalid combination throws with Ceres' message.
+  ceres_hip_line_search_summary MinimizeLineSearch(const ceres_hip_line_search_options& options, double* state) {
+    ceres_hip_line_search_summary s{};
+    if (ceres_hip_bal_minimize_line_search(handle_, &options, state, &s) != CERES_HIP_OK)
+      throw std::runtime_error(std::string(ceres_hip_bal_last_error(handle_)));
+    return s;
+  }
 
  private:
   ceres_hip_bal* handle_ = nullptr;

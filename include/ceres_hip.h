@@ -640,6 +640,97 @@ typedef struct ceres_hip_minimizer_summary {
  * steps.  state: host, in/out. */
 int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* options, double* state,
                            ceres_hip_minimizer_summary* summary);
+/* ---- the line search minimizer (Solver::Options::minimizer_type = LINE_SEARCH; bundle_adjuster --line_search) ----
+ * LineSearchMinimizer (internal/ceres/line_search_minimizer.cc) with its search directions (line_search_direction.cc,
+ * low_rank_inverse_hessian.cc) and line searches (line_search.cc, polynomial.cc), on the handle's problem: camera model, loss and
+ * constant blocks as ceres_hip_bal_minimize honours them.  No Jacobian is ever formed: cost and gradient come from a gradient-only
+ * evaluator, the L-BFGS history and recursion stay on the device.  The enum values are the reference's (include/ceres/types.h). */
+#define CERES_HIP_STEEPEST_DESCENT 0
+#define CERES_HIP_NONLINEAR_CONJUGATE_GRADIENT 1
+#define CERES_HIP_LBFGS 2
+#define CERES_HIP_BFGS 3 /* a dense n x n matrix: refused with CERES_HIP_E_UNSUPPORTED (use CERES_HIP_LBFGS) */
+#define CERES_HIP_FLETCHER_REEVES 0
+#define CERES_HIP_POLAK_RIBIERE 1
+#define CERES_HIP_HESTENES_STIEFEL 2
+#define CERES_HIP_ARMIJO 0
+#define CERES_HIP_WOLFE 1
+#define CERES_HIP_BISECTION 0
+#define CERES_HIP_QUADRATIC 1
+#define CERES_HIP_CUBIC 2
+/* Solver::Options of the line search minimizer (include/ceres/solver.h defaults in comments). */
+typedef struct ceres_hip_line_search_options {
+  int32_t max_num_iterations;                       /* 50 */
+  int32_t line_search_direction_type;               /* CERES_HIP_LBFGS */
+  int32_t nonlinear_conjugate_gradient_type;        /* CERES_HIP_FLETCHER_REEVES */
+  int32_t max_lbfgs_rank;                           /* 20 */
+  int32_t use_approximate_eigenvalue_bfgs_scaling;  /* 0 */
+  int32_t line_search_type;                         /* CERES_HIP_WOLFE */
+  int32_t line_search_interpolation_type;           /* CERES_HIP_CUBIC */
+  int32_t max_num_line_search_step_size_iterations; /* 20 */
+  int32_t max_num_line_search_direction_restarts;   /* 5 */
+  int32_t reserved;
+  double min_line_search_step_size;                 /* 1e-9 */
+  double line_search_sufficient_function_decrease;  /* 1e-4 */
+  double max_line_search_step_contraction;          /* 1e-3 */
+  double min_line_search_step_contraction;          /* 0.6 */
+  double line_search_sufficient_curvature_decrease; /* 0.9 */
+  double max_line_search_step_expansion;            /* 10 */
+  double function_tolerance;                        /* 1e-6 */
+  double gradient_tolerance;                        /* 1e-10 */
+  double parameter_tolerance;                       /* 1e-8 */
+} ceres_hip_line_search_options;
+void ceres_hip_line_search_default_options(ceres_hip_line_search_options* o);
+typedef struct ceres_hip_line_search_iteration {
+  double cost, cost_change, gradient_max_norm, gradient_norm, step_norm, step_size;
+  int32_t line_search_function_evaluations, line_search_gradient_evaluations, line_search_iterations, reserved;
+} ceres_hip_line_search_iteration;
+typedef struct ceres_hip_line_search_summary {
+  double initial_cost, final_cost;
+  int32_t num_iterations;       /* every iteration, logged or not (iteration 0 — the initial evaluation — not counted) */
+  int32_t num_successful_steps;
+  int32_t num_line_search_steps;
+  int32_t num_line_search_direction_restarts;
+  int32_t num_function_evaluations, num_gradient_evaluations;   /* the initial evaluation included */
+  int32_t termination_type;     /* CERES_HIP_CONVERGENCE / CERES_HIP_NO_CONVERGENCE_T / CERES_HIP_MINIMIZER_FAILURE */
+  int32_t num_iterations_logged;
+  double evaluation_seconds, direction_seconds, total_seconds;
+  int64_t lbfgs_history_bytes;  /* the history the handle holds: 2 rank n_t doubles, rank the largest asked for so far (0: none) */
+  ceres_hip_line_search_iteration iterations[CERES_HIP_MAX_LOGGED_ITERATIONS];   /* [0]: the initial evaluation */
+  char message[256];
+} ceres_hip_line_search_summary;
+/* Evaluator::Evaluate(state, cost, nullptr, gradient, nullptr): cost = 1/2 sum rho with the handle's loss; gradient (may be NULL: the
+ * cost alone) in the tangent space — ceres_hip_bal_num_effective_parameters doubles, free points then free cameras, unscaled; per
+ * observation rho' J^T r.  No Jacobian value and no per-observation contribution is written to memory; no floating-point atomics: two
+ * calls at one state give the same bits.  Works on every handle (any linear solver, any camera model, constant blocks); the solver's
+ * loaded values are not touched.  CERES_HIP_E_UNSUPPORTED on a sharded handle. */
+int ceres_hip_bal_evaluate_gradient(ceres_hip_bal* p, const double* state, double* cost, double* gradient);
+/* LineSearchMinimizer::Minimize.  state: host, in / out (constant blocks come back bit-identical; the reported costs include the fixed
+ * cost).  No Jacobi scaling (the reference applies none here); the handle's inner-iteration and trust-region settings are ignored.
+ * The options are validated first (LineSearchOptionsAreValid, internal/ceres/solver.cc, Ceres' wording): CERES_HIP_E_INVALID — also
+ * for BISECTION with max_line_search_step_contraction > 0.5 or min_line_search_step_contraction < 0.5, which the reference only warns
+ * about; CERES_HIP_E_UNSUPPORTED for CERES_HIP_BFGS and on a sharded handle.  The message is in ceres_hip_bal_last_error(p) — (NULL)
+ * for a NULL handle. */
+int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_search_options* options, double* state,
+                                       ceres_hip_line_search_summary* summary);
+/* Debug, host only: one LineSearch::Search (ARMIJO or WOLFE as the options say) on a caller's univariate function.  fn(x, want_gradient,
+ * value, gradient, user): a non-zero return or a non-finite value is an invalid sample.  direction_max_norm is taken as 1. */
+typedef int (*ceres_hip_univariate_fn)(double x, int want_gradient, double* value, double* gradient, void* user);
+typedef struct ceres_hip_line_search_result {
+  int32_t success, num_function_evaluations, num_gradient_evaluations, num_iterations;
+  double optimal_step_size, optimal_value;
+  char error[512];
+} ceres_hip_line_search_result;
+int ceres_hip_debug_line_search(const ceres_hip_line_search_options* options, ceres_hip_univariate_fn fn, void* user, double step_size_estimate,
+                                double initial_cost, double initial_gradient, ceres_hip_line_search_result* out);
+/* Debug, host only: MinimizeInterpolatingPolynomial (internal/ceres/polynomial.cc) on n samples with 1 to 6 valid values and gradients in all; coefficients_out (may be NULL):
+ * the interpolating polynomial, highest power first, one coefficient per valid value or gradient (at most 6). */
+int ceres_hip_debug_minimize_interpolating_polynomial(int32_t n, const double* x, const double* value, const int32_t* value_valid,
+                                                      const double* gradient, const int32_t* gradient_valid, double x_min, double x_max,
+                                                      double* optimal_x, double* optimal_value, double* coefficients_out);
+/* Debug, device 0: the L-BFGS operator the minimizer runs.  The num_updates pairs (row-major [num_updates][n]) go through the secant test
+ * and the circular buffer in order — accepted_out[k] = 1 / 0 — then direction_out = -H gradient by the two-loop recursion. */
+int ceres_hip_debug_lbfgs_direction(int64_t n, int32_t rank, int32_t use_scaling, int32_t num_updates, const double* delta_x,
+                                    const double* delta_gradient, const double* gradient, double* direction_out, int32_t* accepted_out);
 /* Timing probe of the evaluator that writes the solver's tiles (what ceres_hip_bal_minimize runs per Jacobian evaluation on the
  * fused <2,3,9> path): average microseconds of `iters` back-to-back launches at `state`; flags != 0 switch groups of its stores
  * off (experiments; the handle's Jacobian is unusable afterwards until the next evaluation).                                  */
