@@ -64,9 +64,12 @@ struct ceres_hip_bal {
   double2* d_scrap = nullptr;
   // ceres_hip_bal_evaluate_gradient / ceres_hip_bal_minimize_line_search (line_search.inc): their lists and vectors, made on first use
   struct BalLineSearch* ls = nullptr;
+  // ceres_hip_bal_covariance (covariance.inc): its lists and buffers, made on first use
+  struct BalCovariance* cov = nullptr;
 };
 void bal_inner_free(ceres_hip_bal* p);
 void bal_ls_free(ceres_hip_bal* p);
+void bal_cov_free(ceres_hip_bal* p);
 
 namespace {
 
@@ -250,6 +253,7 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 #include "inner_iterations.inc"
 #include "dogleg.inc"
 #include "line_search.inc"
+#include "covariance.inc"
 
 extern "C" {
 
@@ -279,6 +283,7 @@ void ceres_hip_bal_destroy(ceres_hip_bal* p) {
   if (p->h_parts) (void)hipHostFree(p->h_parts);
   bal_inner_free(p);
   bal_ls_free(p);
+  bal_cov_free(p);
   if (p->s) ceres_hip_destroy(p->s);  // frees every device allocation made through dev_alloc
   delete p;
 }

@@ -391,6 +391,30 @@ hipError_t LaunchSchurSparseDiag(const GenStructure& G, const SchurPairs& P, con
 hipError_t LaunchDenseCholesky(double* A, int n, int* fail_flag, hipStream_t stream);
 hipError_t LaunchDenseCholeskySolve(const double* A, int n, double* x, hipStream_t stream);
 
+// ---- covariance (kernels_covariance.hip, covariance.inc; design/17_covariance.md) ------------------
+// C_p (9 doubles per free point, symmetric) -> C_p^-1 in place by the Cholesky factorisation of the unit-diagonal-scaled block;
+// pivot[p] = its smallest pivot, 0 where a diagonal entry or a pivot is not positive (the block is then zeroed: never a NaN)
+hipError_t LaunchCovPointFactor(int n_points, double* blocks, double* pivot, hipStream_t stream);
+// out[0] = min over i < count of v[i stride] (squared if square != 0), out[1] = the first index that attains it; one workgroup, fixed order
+hipError_t LaunchCovMin(const double* v, int64_t count, int64_t stride, int square, double* out, hipStream_t stream);
+// lam = diag(S)^-1/2, S <- Lambda S Lambda (every entry); *flag = 1 when a diagonal entry is not positive and finite (its lam is 0)
+hipError_t LaunchCovScale(double* S, int n, double* lam, int* flag, hipStream_t stream);
+// A: the factor L of LaunchDenseCholesky in its lower triangle (overwritten by L^-1).  W (n x n) <- Lambda (L L^T)^-1 Lambda, exactly
+// symmetric; W is also the scratch of the triangular inversion.
+hipError_t LaunchCovInverseFromFactor(double* A, int n, const double* lam, double* W, hipStream_t stream);
+enum CovBlockKind { kCovConstPoint = 0, kCovPoint = 1, kCovCamera = 2, kCovConstCamera = 3 };
+struct CovBlocksArgs {
+  int n_pairs = 0, n = 0;                   // n = num_cols_f, the pitch of sinv
+  const int32_t *code_a = nullptr, *code_b = nullptr;   // per pair: 4 x (index among the free points / cameras) + CovBlockKind
+  const int64_t* out_off = nullptr;         // per pair: where its dim(a) x dim(b) row-major block starts in out
+  double* out = nullptr;
+  const double *values = nullptr, *cinv = nullptr, *sinv = nullptr;   // caller-layout Jacobian, C_p^-1 (9 per free point), S^-1
+  // per free point its observations by free cameras, entries [pt_ptr[q], pt_ptr[q + 1]): E cell, F cell, column of the camera
+  const int32_t *pt_ptr = nullptr, *ent_epos = nullptr, *ent_fpos = nullptr, *ent_ccol = nullptr;
+};
+// one wavefront per pair; cw = 9 or 10 (hipErrorInvalidValue otherwise)
+hipError_t LaunchCovBlocks(const CovBlocksArgs& P, int cw, hipStream_t stream);
+
 // ---- CLUSTER_JACOBI (kernels_cluster.hip): one dense factor per cluster of F blocks ------------------
 // Clusters of at most kClusterLdsDim scalars are factored and applied one workgroup per cluster with the matrix in LDS
 // (128 x 129 doubles = 129 KiB of the CU's 160); larger ones go through LaunchDenseCholesky / LaunchDenseCholeskySolve.

@@ -282,6 +282,24 @@ ABI += [
 ]
 
 
+# ---- covariance (include/ceres_hip.h: ceres_hip_bal_covariance; design/17_covariance.md) ----
+class CCovarianceOptions(ctypes.Structure):
+    _fields_ = [("apply_loss_function", c_int32), ("reserved", c_int32), ("min_scaled_pivot", c_double)]
+
+
+class CCovarianceSummary(ctypes.Structure):
+    _fields_ = [("termination_type", c_int32), ("reserved", c_int32), ("min_point_pivot", c_double), ("min_schur_pivot", c_double),
+                ("evaluate_seconds", c_double), ("eliminate_seconds", c_double), ("factor_seconds", c_double),
+                ("inverse_seconds", c_double), ("blocks_seconds", c_double), ("device_bytes", c_int64), ("message", ctypes.c_char * 256)]
+
+
+ABI += [
+    ("ceres_hip_covariance_default_options", None, [POINTER(CCovarianceOptions)]),
+    ("ceres_hip_bal_covariance", c_int32, [c_void_p, POINTER(CCovarianceOptions), _DP, c_int64, POINTER(c_int32), POINTER(c_int32), _DP,
+                                           POINTER(CCovarianceSummary)]),
+]
+
+
 def load_library():
     """dlopen csrc/libceres_hip.so and bind every ABI symbol; raises if anything is missing."""
     global _lib
@@ -1360,3 +1378,49 @@ class BalProblem:
         S = CLineSearchSummary()
         self._check(self._lib.ceres_hip_bal_minimize_line_search(self._h, byref(o), _p(x), byref(S)))
         return x, S
+
+    def covariance_block_size(self, block):
+        """Tangent size of a block numbered in state order (point q is q, camera c is num_points + c): 3, or 9 / 10 for a camera."""
+        if block < self.num_points:
+            return 3
+        return 10 if self.camera_model == CAMERA_QUATERNION else 9
+
+    def covariance_raw(self, state, pairs, apply_loss_function=True, min_scaled_pivot=1e-8, out=None):
+        """ceres_hip_bal_covariance without judging the outcome: (return code, flat output, CCovarianceSummary).  `out` (optional): the
+        flat output array to fill, at least the sum of dim(a) x dim(b) doubles; it is left as it is when the call fails."""
+        x = _f64(state, self.num_parameters)
+        pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        a, b = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
+        nblocks = self.num_points + self.num_cameras
+        # (sizes of in-range blocks only: an index out of range is the library's to refuse)
+        total = sum(self.covariance_block_size(int(i)) * self.covariance_block_size(int(j)) for i, j in pr
+                    if 0 <= i < nblocks and 0 <= j < nblocks)
+        if out is None:
+            out = np.zeros(max(total, 1))
+        elif out.dtype != np.float64 or not out.flags.c_contiguous or out.size < total:
+            raise ValueError("out must be a contiguous float64 array with room for every requested block")
+        o = CCovarianceOptions()
+        self._lib.ceres_hip_covariance_default_options(byref(o))
+        o.apply_loss_function = int(bool(apply_loss_function))
+        o.min_scaled_pivot = float(min_scaled_pivot)
+        S = CCovarianceSummary()
+        rc = self._lib.ceres_hip_bal_covariance(self._h, byref(o), _p(x), int(pr.shape[0]), a.ctypes.data_as(POINTER(c_int32)),
+                                                b.ctypes.data_as(POINTER(c_int32)), _p(out), byref(S))
+        return rc, out, S
+
+    def covariance(self, state, pairs, apply_loss_function=True, min_scaled_pivot=1e-8):
+        """ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for the (a, b) block pairs (state order: point q is q, camera c
+        is num_points + c): (J^T J)^-1 of the reduced program at state, in the Schur form on the device (DENSE_SCHUR handles only).
+        Returns (list of dim(a) x dim(b) arrays, CCovarianceSummary); pairs with a constant block are zeros.  Raises HipError with the
+        summary's message when the problem is rank deficient (a pivot of the unit-diagonal-scaled point blocks or Schur complement is
+        not above min_scaled_pivot) — ceres_hip_bal_covariance in include/ceres_hip.h."""
+        rc, out, S = self.covariance_raw(state, pairs, apply_loss_function, min_scaled_pivot)
+        self._check(rc)
+        if S.termination_type != SUCCESS:
+            raise HipError(S.message.decode())
+        blocks, at = [], 0
+        for i, j in np.asarray(pairs, dtype=np.int64).reshape(-1, 2):
+            da, db = self.covariance_block_size(int(i)), self.covariance_block_size(int(j))
+            blocks.append(out[at:at + da * db].reshape(da, db).copy())
+            at += da * db
+        return blocks, S

@@ -195,6 +195,18 @@ class HipBalProblem {
       throw std::runtime_error(std::string(ceres_hip_bal_last_error(handle_)));
     return s;
   }
+  // ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for the (a, b) block pairs, numbered in state order (point q is q,
+  // camera c is num_points + c): blocks_out = the dim(a) x dim(b) row-major blocks back to back (3 per point, 9 or 10 per camera; zeros
+  // for a pair with a constant block).  DENSE_SCHUR handles only.  Options from ceres_hip_covariance_default_options.  A refused call
+  // throws; a rank-deficient problem returns with termination_type = CERES_HIP_FAILURE and its message, blocks_out untouched.
+  ceres_hip_covariance_summary Covariance(const ceres_hip_covariance_options& options, const double* state,
+                                          const std::vector<int32_t>& block_a, const std::vector<int32_t>& block_b, double* blocks_out) {
+    if (block_a.size() != block_b.size()) throw std::invalid_argument("HipBalProblem::Covariance: block_a and block_b differ in length");
+    ceres_hip_covariance_summary s{};
+    if (ceres_hip_bal_covariance(handle_, &options, state, int64_t(block_a.size()), block_a.data(), block_b.data(), blocks_out, &s) != CERES_HIP_OK)
+      throw std::runtime_error(std::string(ceres_hip_bal_last_error(handle_)));
+    return s;
+  }
 
  private:
   ceres_hip_bal* handle_ = nullptr;

@@ -712,6 +712,48 @@ int ceres_hip_bal_evaluate_gradient(ceres_hip_bal* p, const double* state, doubl
  * for a NULL handle. */
 int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_search_options* options, double* state,
                                        ceres_hip_line_search_summary* summary);
+/* ---- covariance (ceres::Covariance: include/ceres/covariance.h, internal/ceres/covariance_impl.cc; design/17_covariance.md) ----
+ * Cov = (J^T J)^-1 with J the Evaluator's Jacobian of the reduced program at `state`: unscaled, no LM diagonal, loss-corrected when
+ * apply_loss_function is set (CovarianceImpl evaluates it so, covariance_impl.cc:71); columns [free points | free cameras].  Computed in
+ * the Schur form — C_p = E_p^T E_p, Y_p = C_p^-1 E_p^T F, S = F^T F - sum_p (E_p^T F)^T C_p^-1 (E_p^T F):
+ *     camera - camera: the block of S^-1;   point p - camera c: -Y_p S^-1[:, c];   point p - point q: delta_pq C_p^-1 + Y_p S^-1 Y_q^T
+ * with S dense, factored by the blocked Cholesky of DENSE_SCHUR and inverted from the factor on the matrix pipe.
+ * Blocks are in the TANGENT space (3 for a point, 9 for an angle-axis or quaternion-manifold camera, 10 for a Euclidean quaternion
+ * camera); a pair that involves a constant block is all zeros (covariance_impl.cc:143-165).  Not offered: lifting to the ambient space of
+ * a manifold camera, null_space_rank and the pseudo-inverse, sharded handles, handles whose linear solver is not CERES_HIP_DENSE_SCHUR.
+ * RANK.  An unpivoted Cholesky does not notice a lost gauge, so S and every C_p are factored with a unit diagonal (S~ = Lambda S Lambda,
+ * Lambda = diag(S)^-1/2; S^-1 = Lambda S~^-1 Lambda) and the call FAILS when a pivot is not above min_scaled_pivot, or when a diagonal
+ * entry is not positive (a point all of whose rows a loss switched off).  This guard is a property of the inputs — on bundle-adjustment
+ * problems a free gauge leaves pivots below 1e-10 and a fixed one pivots above 1e-3 (design/17_covariance.md) — NOT a rank-revealing
+ * factorization.  Ceres' SPARSE_QR path fails on the same problems, with "Jacobian matrix is rank deficient". */
+typedef struct ceres_hip_covariance_options {
+  int32_t apply_loss_function;   /* 1 (Covariance::Options::apply_loss_function); 0: the uncorrected Jacobian even when a loss is set */
+  int32_t reserved;
+  double  min_scaled_pivot;      /* 1e-8, see RANK above */
+} ceres_hip_covariance_options;
+void ceres_hip_covariance_default_options(ceres_hip_covariance_options* o);
+typedef struct ceres_hip_covariance_summary {
+  int32_t termination_type;      /* CERES_HIP_SUCCESS / CERES_HIP_FAILURE */
+  int32_t reserved;
+  double  min_point_pivot, min_schur_pivot;   /* smallest pivot of the unit-diagonal-scaled factorizations (0: not positive; the Schur
+                                                 one is -1 when the point stage already failed) */
+  double  evaluate_seconds, eliminate_seconds, factor_seconds, inverse_seconds, blocks_seconds;
+  int64_t device_bytes;          /* what this feature holds on the handle (the second n x n buffer, the point blocks, the lists) */
+  char    message[256];
+} ceres_hip_covariance_summary;
+/* Blocks are numbered in state order: point q is q, camera c is num_points + c.  blocks_out: the concatenation, in pair order, of
+ * dim(a) x dim(b) row-major blocks; the pair (b, a) gives the exact transpose of (a, b); a pair may repeat.  options NULL: the defaults.
+ * The handle's loss, camera model and constant masks are honoured as ceres_hip_bal_evaluate honours them; the solver's loaded values are
+ * overwritten as by that call; the loss, the inner-iteration and strategy settings and a later ceres_hip_bal_minimize are not affected.
+ * The second n x n buffer (n = tangent scalars of the free cameras) is allocated on the first call and released with the handle.
+ * Returns CERES_HIP_E_INVALID (message in ceres_hip_bal_last_error; of (NULL) for a NULL handle, which answers before any device call)
+ * for a NULL handle, state, summary or pair array, num_pairs < 0, a block index out of range, a non-finite or negative
+ * min_scaled_pivot; CERES_HIP_E_UNSUPPORTED for a handle whose linear solver is not CERES_HIP_DENSE_SCHUR and for a sharded handle.
+ * A rank-deficient problem returns 0 with termination_type = CERES_HIP_FAILURE, the message naming the factorization that failed and
+ * the pivot; blocks_out is then not written.  No floating-point atomics: two calls at one state give the same bits. */
+int ceres_hip_bal_covariance(ceres_hip_bal* p, const ceres_hip_covariance_options* options, const double* state,
+                             int64_t num_pairs, const int32_t* block_a, const int32_t* block_b,
+                             double* blocks_out, ceres_hip_covariance_summary* summary);
 /* Debug, host only: one LineSearch::Search (ARMIJO or WOLFE as the options say) on a caller's univariate function.  fn(x, want_gradient,
  * value, gradient, user): a non-zero return or a non-finite value is an invalid sample.  direction_max_norm is taken as 1. */
 typedef int (*ceres_hip_univariate_fn)(double x, int want_gradient, double* value, double* gradient, void* user);
