@@ -181,6 +181,7 @@ int bal_evaluate_into_tiles(ceres_hip_bal* p, const double* d_state, const doubl
 }
 
 constexpr int kBalSecondParts = 2048;   // d_parts / h_parts: an evaluation's cost partials in [0, 2048), a second kernel's from here on
+static_assert(kMaxEvalGrid <= kBalSecondParts, "one cost partial per workgroup of the evaluators");
 
 // max |g_i / scale_i| — with quaternion-manifold cameras |x - Plus(x, -g)|_inf at the state d_x; deferred_cost != nullptr: also the cost of
 // the evaluation enqueued before (bal_evaluate_*(…, defer = true))

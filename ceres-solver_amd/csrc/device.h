@@ -14,6 +14,12 @@ int BalBlockFor(int mode);                   // threads per workgroup of the fus
 constexpr size_t kMaxLdsBytes = 160 * 1024;  // LDS per CU on gfx950
 constexpr int kVecBlock = 256;
 constexpr int kMaxVecGrid = 512;             // partial sums per inner product
+// Grid caps of the BAL front end's kernels (a kernel walks what lies beyond its grid in a grid-stride loop; tests/test_frontend_scale_cpu.py
+// reads them from here): the evaluators — kVecBlock rows per workgroup in row order, four tiles per workgroup in tile order, four
+// 64-row chunks per workgroup in the gradient-only point pass (one cost partial per workgroup) — and the gradient-only camera pass
+// (four camera chunks per workgroup)
+constexpr int kMaxEvalGrid = 2048;
+constexpr int kMaxLsCameraGrid = 4096;
 
 // ---- one-shot peer-to-peer exchange (p2p.h: the device side; kernels_cg.hip: the stand-alone all-reduce) ----
 constexpr int kP2pMaxWorld = 8;    // one node: 8 GPUs on the xGMI mesh

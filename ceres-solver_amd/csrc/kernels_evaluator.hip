@@ -283,7 +283,7 @@ int grid_for(int64_t n) {
 hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, hipStream_t stream, int camera_model) {
   // one observation per thread and several per thread at scale: 2048 workgroups keep 256 CUs busy
   int64_t g = (A.n_rows + kVecBlock - 1) / kVecBlock;
-  const int grid = int(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+  const int grid = int(g < 1 ? 1 : (g > kMaxEvalGrid ? kMaxEvalGrid : g));
   *nparts = grid;
   if (camera_model != kCamAngleAxis) return LaunchBalEvaluateQuat(A, jacobian, grid, stream, camera_model);   // (kernels_quaternion.hip)
   if (A.loss.type == kLossNone) {
@@ -299,7 +299,7 @@ hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, h
 // the reduced program's Jacobian evaluation (the quaternion cameras' instantiations: kernels_quaternion.hip)
 hipError_t LaunchBalEvaluateConst(const BalEvalConstArgs& A, int* nparts, hipStream_t stream, int camera_model) {
   int64_t g = (A.n_rows + kVecBlock - 1) / kVecBlock;
-  const int grid = int(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+  const int grid = int(g < 1 ? 1 : (g > kMaxEvalGrid ? kMaxEvalGrid : g));
   *nparts = grid;
   if (!A.row_fpos || !A.row_scam || !A.row_spt || !A.values) return hipErrorInvalidValue;
   if (camera_model != kCamAngleAxis) return LaunchBalEvaluateConstQuat(A, grid, stream, camera_model);
@@ -314,7 +314,7 @@ hipError_t LaunchBalEvaluateTilesConst(const BalEvalTilesConstArgs& T, int64_t n
   hipLaunchKernelGGL(bal_pack_state_const_kernel, dim3(unsigned((3 * n_points + 9 * T.n_pack_cams + kVecBlock - 1) / kVecBlock)), dim3(kVecBlock), 0,
                      stream, T.e.state, T.e.scale, n_points, T.n_pack_cams, T.pack_cam, T.pack_scale, T.pt_pack, T.cam_pack);
   const int64_t g = (T.n_tiles + 3) / 4;
-  const int grid = int(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+  const int grid = int(g < 1 ? 1 : (g > kMaxEvalGrid ? kMaxEvalGrid : g));
   *nparts = grid;
   const bool robust = T.e.loss.type != kLossNone;
   if (!T.e.values) {
@@ -331,7 +331,7 @@ hipError_t LaunchBalEvaluateTiles(const BalEvalTilesArgs& T, int64_t n_points, i
   hipLaunchKernelGGL(bal_pack_state_kernel, dim3(unsigned((3 * n_points + 9 * n_cameras + kVecBlock - 1) / kVecBlock)), dim3(kVecBlock), 0, stream,
                      T.e.state, T.e.scale, n_points, n_cameras, T.pt_pack, T.cam_pack);
   const int64_t g = (T.n_tiles + 3) / 4;
-  const int grid = int(g < 1 ? 1 : (g > 2048 ? 2048 : g));
+  const int grid = int(g < 1 ? 1 : (g > kMaxEvalGrid ? kMaxEvalGrid : g));
   *nparts = grid;
   const bool robust = T.e.loss.type != kLossNone;
 #define EVAL_TILES_CASE(D)                                                                                                    \

@@ -319,8 +319,8 @@ hipError_t LaunchLsGradient(const LsGradArgs& A, bool gradient, int camera_model
   if (A.n_rows <= 0 || !A.row_cam || !A.row_pt || !A.row_obs || !A.state || !A.cost_partials) return hipErrorInvalidValue;
   if (gradient && (!A.row_pdst || !A.grad || !A.wave_parts || A.n_chunks <= 0 || !A.chunk_cam || !A.cm_pt || !A.cm_obs)) return hipErrorInvalidValue;
   const int64_t row_chunks = (A.n_rows + 63) / 64;
-  const int gp = int(std::min<int64_t>(2048, (row_chunks + 3) / 4));
-  const int gc = int(std::min<int64_t>(4096, (int64_t(A.n_chunks) + 3) / 4));
+  const int gp = int(std::min<int64_t>(kMaxEvalGrid, (row_chunks + 3) / 4));
+  const int gc = int(std::min<int64_t>(kMaxLsCameraGrid, (int64_t(A.n_chunks) + 3) / 4));
   *nparts = gp;
   if (camera_model != kCamAngleAxis) {
     hipError_t e = LaunchLsGradientQuat(A, gradient, camera_model, gp, gc, stream);

@@ -431,8 +431,11 @@ struct BalLineSearch {
 namespace {
 
 constexpr int kLsMaxSlots = 12;
-// h_parts / d_parts: cost partials [0, 2048), then six sets of kMaxVecGrid
-constexpr int kLsCostParts = 2048, kLsParts = kLsCostParts + 6 * kMaxVecGrid;
+// h_parts / d_parts: cost partials [0, 2048), then seven sets of kMaxVecGrid: two of the trial point, two of the gradient norms and
+// THREE of ls_dots_kernel (a . b, a . c, max |a|; with room for two, a tangent vector of more than 341 workgroups wrote — and the
+// host copied — up to kMaxVecGrid doubles past the end of both buffers)
+constexpr int kLsCostParts = 2048, kLsParts = kLsCostParts + 7 * kMaxVecGrid;
+static_assert(kMaxEvalGrid <= kLsCostParts, "one cost partial per workgroup of the evaluators");
 
 // give the history and the per-slot scalars back before a larger rank's replace them
 void ls_release_history(ceres_hip_solver* s, BalLineSearch* ls) {
@@ -692,6 +695,7 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
   double* hp = ls->h_parts;
   double* dp = ls->d_parts;
   constexpr int kTrial = kLsCostParts, kNorms = kLsCostParts + 2 * kMaxVecGrid, kDots = kLsCostParts + 4 * kMaxVecGrid;
+  static_assert(kDots + 3 * kMaxVecGrid <= kLsParts, "room for the three sets of ls_dots_kernel");
   auto sum_parts = [&](int off, int n) { double v = 0; for (int i = 0; i < n; ++i) v += hp[off + i]; return v; };
   auto max_parts = [&](int off, int n) { double v = 0; for (int i = 0; i < n; ++i) v = std::max(v, hp[off + i]); return v; };
   // cost, gradient and the gradient norms at slot k (vector_x already there); direction != nullptr: also direction . gradient

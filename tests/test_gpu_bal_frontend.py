@@ -69,12 +69,12 @@ def test_state_conversion_round_trip(hip, oracle):
     gp.close()
 
 
-def check_same_trajectory(Sa, Sb, cost_tol):
+def check_same_trajectory(Sa, Sb, cost_tol, cg_tol=1):
     assert Sa.num_iterations_logged == Sb.num_iterations_logged, (Sa.num_iterations_logged, Sb.num_iterations_logged)
     for i in range(Sa.num_iterations_logged):
         a, b = Sa.iterations[i], Sb.iterations[i]
         assert a.step_is_successful == b.step_is_successful and a.step_is_valid == b.step_is_valid, i
-        assert abs(a.linear_solver_iterations - b.linear_solver_iterations) <= 1, i
+        assert abs(a.linear_solver_iterations - b.linear_solver_iterations) <= cg_tol, i
         assert abs(a.cost - b.cost) <= cost_tol * abs(a.cost), (i, a.cost, b.cost)
         assert abs(a.radius - b.trust_region_radius) <= 1e-6 * a.radius, i
     assert abs(Sa.final_cost - Sb.final_cost) <= cost_tol * Sa.final_cost
