@@ -38,6 +38,13 @@ constexpr int kMaxPointsPerTile = 42;  // 3 * 42 = 126 <= 128 point-space scalar
 constexpr int kSlotCamBits = 20;
 constexpr int kSlotSpill = 0xFFF;
 constexpr int kSlotNoCamera = (1 << kSlotCamBits) - 1;   // camera field of a valid slot WITHOUT a camera cell when the accumulators are not all in LDS
+// Launch-time choices of the fused path by problem size (Fused, CameraItems, launch_stream at the end of kernels_bal.inc; the item length:
+// plan.cc).  Host-side only: no kernel reads them.  tests/dispatch_cases.py parses them from here.
+constexpr int kPipelineMinTilesPerWg = 40;    // tiles per workgroup from which the software-pipelined / 1024-thread kernels run (below: bal_fused_kernel<.., 512>)
+constexpr int kStagedXMinTilesPerWg = 100;    // tiles per workgroup from which a workgroup stages x in LDS (n_xhot, x_lds_scalars)
+constexpr int kCamItemLaneMinMean = 384;      // mean observations per camera item from which the lane-per-observation kernel runs (below: the matrix-pipe one)
+constexpr int kCamItemSpread = 8192;          // items of n_obs / kCamItemSpread observations (a multiple of kTile in kTile .. kCamChunk): small problems still spread over the chip
+constexpr int kNonTemporalTileMiB = 200;      // MiB of tiles above which the pipelined kernels read them with non-temporal loads (the Infinity Cache holds 256)
 
 // ---------------------------------------------------------------------------
 // Host-side analysis (plan.cc).  Pure C++, unit-testable without a GPU through

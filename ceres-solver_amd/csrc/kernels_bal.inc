@@ -3535,13 +3535,13 @@ static hipError_t launch_stream(const BalArgs& A, bool lds, int grid, hipStream_
   // tiles that fit the 256 MiB Infinity Cache are read with plain loads (see issue_pairs)
   if (A.Jf) {   // fp32 tiles (round 5: pipelined as well)
     if constexpr (kHasF32) {
-      const bool nt32 = A.n_tiles * int64_t(6 * kTile) * int64_t(sizeof(float4)) > (int64_t(200) << 20);
+      const bool nt32 = A.n_tiles * int64_t(6 * kTile) * int64_t(sizeof(float4)) > (int64_t(kNonTemporalTileMiB) << 20);
       return nt32 ? launch_stream2<MODE, true, true>(A, lds, grid, stream) : launch_stream2<MODE, false, true>(A, lds, grid, stream);
     } else {
       return hipErrorInvalidValue;   // fp32 tiles exist for the BAL shape only (solver.hip refuses the option for the others)
     }
   }
-  const bool nt = A.n_tiles * int64_t(kTilePitch) * int64_t(sizeof(double2)) > (int64_t(200) << 20);
+  const bool nt = A.n_tiles * int64_t(kTilePitch) * int64_t(sizeof(double2)) > (int64_t(kNonTemporalTileMiB) << 20);
   return nt ? launch_stream2<MODE, true>(A, lds, grid, stream) : launch_stream2<MODE, false>(A, lds, grid, stream);
 }
 
@@ -3565,15 +3565,15 @@ static hipError_t Fused(int mode, const BalArgs& A0, bool lds, int grid, hipStre
   if ((mode != kBackSub && mode != kJx) || lds) A.x_lds_scalars = 0;   // (only the modes whose LDS is free: load_xc)
   // a workgroup stages its copy of x once per launch: that pays from about a hundred tiles per workgroup on — of THIS launch's tiles and
   // workgroups (Ladybug-sized problems, 41 tiles per workgroup, lose 3 us of a 42 us pass to it: profiles/r05n_*)
-  if ((A.tile_end > 0 ? A.tile_end - A.tile_begin : A.n_tiles) < int64_t(100) * grid) { A.n_xhot = 0; A.x_lds_scalars = 0; }
+  if ((A.tile_end > 0 ? A.tile_end - A.tile_begin : A.n_tiles) < int64_t(kStagedXMinTilesPerWg) * grid) { A.n_xhot = 0; A.x_lds_scalars = 0; }
   const bool big = BalBlockFor(mode) == 1024;
   // A few dozen tiles per workgroup (one rank's eighth of the Venice shape: 38; the Ladybug shape: 41): a wave of the software-pipelined
   // kernel gets five tiles, hardly more than the pipeline's fill and drain — the plain 512-thread kernels are 10 us per S.x faster there
   // (0.367 -> 0.345 ms per step on that shard, profiles/r06m_*); from about 76 tiles per workgroup on the pipeline wins.  (Not where the
   // S.x pass finishes the CG iteration: that tail lives in the pipelined kernel.)
   // At 41 (Ladybug) the two are level in a step (0.320 vs 0.328 ms) while back-to-back launches of the pipelined kernel are 13 % faster
-  // (0.041 vs 0.047 ms per S.x: its code is warm in the instruction cache then): the line is drawn at 40.
-  const bool few_tiles = (A.tile_end > 0 ? A.tile_end - A.tile_begin : A.n_tiles) < int64_t(40) * grid && !A.tail.enabled && lds;
+  // (0.041 vs 0.047 ms per S.x: its code is warm in the instruction cache then): the line is drawn at kPipelineMinTilesPerWg = 40.
+  const bool few_tiles = (A.tile_end > 0 ? A.tile_end - A.tile_begin : A.n_tiles) < int64_t(kPipelineMinTilesPerWg) * grid && !A.tail.enabled && lds;
   const bool big_s = big && (lds || A.hyb_rows == 0) && !few_tiles;  // scattering modes with hybrid rows: the rows are sized for 8 waves' strips
 #if CERES_HIP_PIPELINED
   if (UsePipeline() && !few_tiles && (!A.Jf || F32Pipelined()) && !A.src_values && !A.cam_pos && !(A.flags & 1)) {
@@ -3709,7 +3709,7 @@ static hipError_t CameraItems(bool schur, const double* values, const CamItems& 
   // shape): the lane-per-observation kernel keeps 64 records in flight per wavefront and is 8 % ahead there.
   // CERES_HIP_CAM_ITEMS_MFMA=0 / 1 forces one of them (A/B).
   static const int forced = [] { const char* e = getenv("CERES_HIP_CAM_ITEMS_MFMA"); return e ? (atoi(e) != 0 ? 1 : 0) : -1; }();
-  const bool mfma = NR == 2 && (forced >= 0 ? forced == 1 : items.observations < int64_t(384) * items.count);
+  const bool mfma = NR == 2 && (forced >= 0 ? forced == 1 : items.observations < int64_t(kCamItemLaneMinMean) * items.count);
   if (mfma) {
 #if CERES_HIP_NR == 2
     if (schur) hipLaunchKernelGGL((bal_camera_items_mfma_kernel<true>), grid, dim3(256), 0, stream, values, items, cam_fpos, cam_slot, Mo, parts);

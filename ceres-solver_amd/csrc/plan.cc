@@ -738,7 +738,7 @@ void BuildBalPlan(const HostStructure& h, int reorder_mode, const HybridRequest&
   // lane-per-observation kernel alone, items under 256 observations spent more time reducing than accumulating).
   int64_t chunk_min = kTile;
   if (const char* e = getenv("CERES_HIP_CAM_CHUNK_MIN")) chunk_min = std::max<int64_t>(kTile, atoll(e));   // (experiments)
-  const int chunk = int(std::max<int64_t>(chunk_min, std::min<int64_t>(kCamChunk, ((P.n_obs / 8192 + kTile - 1) / kTile) * kTile)));
+  const int chunk = int(std::max<int64_t>(chunk_min, std::min<int64_t>(kCamChunk, ((P.n_obs / kCamItemSpread + kTile - 1) / kTile) * kTile)));
   P.cam_item_ptr.assign(P.n_cameras + 1, 0);
   for (int c = 0; c < P.n_cameras; ++c) {
     int b = P.cam_ptr[c];
