@@ -44,6 +44,9 @@ constexpr int kPipelineMinTilesPerWg = 40;    // tiles per workgroup from which 
 constexpr int kStagedXMinTilesPerWg = 100;    // tiles per workgroup from which a workgroup stages x in LDS (n_xhot, x_lds_scalars)
 constexpr int kCamItemLaneMinMean = 384;      // mean observations per camera item from which the lane-per-observation kernel runs (below: the matrix-pipe one)
 constexpr int kCamItemSpread = 8192;          // items of n_obs / kCamItemSpread observations (a multiple of kTile in kTile .. kCamChunk): small problems still spread over the chip
+// CG iterations whose per-point sums E^T F p the S.x passes keep (BalArgs::u_out): a solve of at most this many x-updates gets its point
+// step and model cost from them instead of a pass over J (design/20_point_tail.md).  24 bytes per point and iteration; what a captured pass costs: §20.6 there.
+constexpr int kPointTailMaxIterations = 4;
 constexpr int kNonTemporalTileMiB = 200;      // MiB of tiles above which the pipelined kernels read them with non-temporal loads (the Infinity Cache holds 256)
 
 // ---------------------------------------------------------------------------

@@ -161,6 +161,12 @@ struct BalArgs {
   // first pass of a solve (kInit / kCgnrInit; neither raises them): the step's finite-step and factorization flags, two adjacent ints,
   // are cleared here instead of by a memset command in front of the pass (a fill kernel and its launch per step)
   int* clear_flags = nullptr;
+  // Point tail (design/20_point_tail.md).  kSx: the lane or wave that holds a point's finished sum E^T F x stores it at
+  // u_out[ne * pt ..], the plan's point order (nullptr: off).  kInit: likewise the point's E^T b into etb_out.  kBackSub gated by run_after_cg: the
+  // pass also stays out when the point tail takes the solve (PointTailTakes of *run_after_cg and *skip_updates; nullptr: no such test)
+  double* u_out = nullptr;
+  double* etb_out = nullptr;
+  const int* skip_updates = nullptr;
   CgTail tail;                   // kSx, pipelined kernel, every camera's accumulator in LDS: finish the CG iteration (see CgTail)
 };
 
@@ -229,6 +235,27 @@ struct StripBlocks {
   int64_t out[kMaxSharedScalars] = {};
 };
 
+// The point tail of a short ITERATIVE_SCHUR solve (design/20_point_tail.md): U_p = sum_k alpha_k u_k[p] over the S.x passes' captured
+// sums, y_p = (E^T E + D^2)^-1 (E^T b - U_p), x = (y, z) (negated for an LM step), and the model cost change from point-space and
+// camera-space vectors alone.  Runs only if PointTailTakes(S->status, S->n_updates).
+struct PointTailArgs {
+  int n_points = 0, n_f = 0;
+  const int32_t* pt_pos = nullptr;   // nullptr: ne * p
+  const double* etei = nullptr;      // packed inverses, BalOps::etei_pitch doubles per point
+  const double* etb = nullptr;       // E^T b, indexed like y_e
+  const double* u_hist = nullptr;    // [kPointTailMaxIterations][u_stride], ne doubles per point in the PLAN's point order (ne * p)
+  int64_t u_stride = 0;
+  const double *D_e = nullptr, *D_f = nullptr;   // nullptr: no regularisation
+  const double *z = nullptr, *rhs = nullptr, *r = nullptr;   // camera space: CG's solution, right-hand side and residual
+  double *y_e = nullptr, *y_f = nullptr;
+  int negate = 0;
+  int* nonfinite = nullptr;          // negate: raised when an entry of the step is not finite
+  const CgScalars* S = nullptr;
+  double* cost_out = nullptr;        // one partial of the model cost change per workgroup (nullptr: not wanted)
+};
+constexpr int kPointTailBlock = 256;
+constexpr int kPointTailMaxGrid = 1023;   // partials that fit the read-back image beside the remainder's (2 kMaxVecGrid)
+
 // The fused kernels are compiled once per SHAPE (camera width nf, shared strip ns: common.h, kernels_bal.inc — one translation unit
 // per shape); this is one shape's launchers.
 struct BalOps {
@@ -271,6 +298,8 @@ struct BalOps {
   // shapes with a shared strip: the packed upper triangle of the strip's ns x ns matrix from the workgroups' partial sums (kBalShBlocks),
   // cut into the shared blocks' dense diagonal blocks (+ D^2) in the F-block store
   hipError_t (*strip_finish)(const double* parts, int nparts, const StripBlocks& sb, const double* D_f, double* blocks, hipStream_t stream);
+  // *n_parts: the partials it leaves in T.cost_out when it runs (0 without cost_out)
+  hipError_t (*point_tail)(const PointTailArgs& T, int* n_parts, hipStream_t stream);
 };
 const BalOps* GetBalOps(int nr, int ne, int nf, int ns);   // nullptr: not compiled (common.h: BalShapeCompiled)
 // the dynamic-LDS ceiling of a kernel, raised once per (kernel, device)
@@ -510,7 +539,18 @@ struct CgScalars {
   // against live at index i & 1, so that no multi-workgroup kernel reads a scalar another workgroup of the same
   // launch writes (iteration i reads [i & 1] and writes [(i + 1) & 1]).
   double rho_pp[2], Q0_pp[2];
+  // Point tail (design/20_point_tail.md): alpha of the first kPointTailMaxIterations completed x-updates of a solve that began at x = 0, and
+  // how many x-updates the solve has completed (a failed iteration leaves x alone and is not counted); written by cg_update_kernel
+  // and cg_iteration_tail where they write alpha, zeroed where the solve begins
+  double alpha_hist[kPointTailMaxIterations];
+  int n_updates, reserved;
 };
+// Does the point tail finish this solve (status and n_updates of its CgScalars)?  CG ended with a solution after at most
+// kPointTailMaxIterations x-updates.  The back-substitution pass over J takes every other terminal state that lets the solution be used.
+__host__ __device__ inline bool PointTailTakes(int status, int updates) {
+  return (status == kCgConvergedZeta || status == kCgConvergedResidual || status == kCgMaxIterations) && updates >= 1 &&
+         updates <= kPointTailMaxIterations;
+}
 
 struct CgBuffers {
   int64_t n = 0;

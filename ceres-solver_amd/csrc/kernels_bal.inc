@@ -922,6 +922,14 @@ __device__ __forceinline__ void store_point_solution(const BalArgs& A, int po, c
   if (A.negate_out && !isfinite(t)) atomicAdd(A.nonfinite, 1);
 }
 
+// Point tail (design/20_point_tail.md): a point's finished sum E^T F x of an S.x pass, kept for the tail (A.u_out != nullptr), and its
+// E^T b from kInit (A.etb_out); both indexed like y_e.  Called by the ONE lane that holds the point's sum.  Only the instantiations with
+// every camera's accumulator in LDS capture (the handles that take the point tail run no other): the others' code is what it was.
+__device__ __forceinline__ void store_point_capture(double* out, int po, const double* v) {
+#pragma unroll
+  for (int j = 0; j < NE; ++j) out[po + j] = v[j];
+}
+
 // sum over the slot's rows of m_r (b_r + half m_r): the observation's share of a model cost change
 __device__ __forceinline__ double cost_terms(const double (&m)[NR], const double (&b)[NR], double half) {
   double t = 0.0;
@@ -1012,7 +1020,9 @@ __device__ __forceinline__ void load_aux(const BalArgs& A, const Slot& s, int la
 }
 
 // The arithmetic of a streaming mode on one normal tile; issues no global loads.
-template <int MODE, bool LDS>
+// CAP: how a kSx pass keeps the points' sums — 0: where A.u_out is set (the unpipelined kernels), 1: always, with dense stores (the
+// capturing instantiation of the pipelined kernel), 2: never (its other instantiation: no capture code at all)
+template <int MODE, bool LDS, int CAP = 0>
 __device__ __forceinline__ void compute_stream(const BalArgs& A, const Slot& s, int lane, int span, int npts,
                                                const StreamAux& x, Ctx& acc, double& dot) {
   if constexpr (MODE == kSx || MODE == kSpseZ) {
@@ -1028,6 +1038,30 @@ __device__ __forceinline__ void compute_stream(const BalArgs& A, const Slot& s, 
 #if !(CERES_HIP_AB_ABLATE & 4)
     seg_allreduce<NE>(u, lane, s.first, s.last, span);
 #endif
+    if constexpr (MODE == kSx && LDS && CAP == 1) {
+#if CERES_HIP_PIPELINED
+      // The capturing instantiation of the pipelined kernel (launched only with A.u_out set: no store under a launch-uniform branch, the
+      // stage's s_waitcnt counts stay static): the tile's points are consecutive ids, their sums one contiguous range of u_out, and
+      // lane L stores scalar L (and 64 + L) of it, gathered from the point's last lane — JtJx's cooperative store of y_e.  One or two
+      // dense stores per tile.  Measured on the Venice shape (design/20_point_tail.md §20.6): the pass takes 199 - 208 us with them, 160 - 171
+      // without; three scattered 8-byte stores per point under a run-time branch took it to 208 - 217 us.
+      const int n3 = 3 * npts;
+      double* const out = A.u_out + 3 * int64_t(__builtin_amdgcn_readfirstlane(s.pt));
+      const int ta = (s.seg >> 17) & 63, tb = (s.seg >> 24) & 63;
+      {
+        const double v0 = shfl_idx(u[0], ta), v1 = shfl_idx(u[1], ta), v2 = shfl_idx(u[2], ta);
+        const int c = lane % 3;
+        if ((s.seg >> 23) & 1) out[lane] = c == 0 ? v0 : (c == 1 ? v1 : v2);
+      }
+      if (n3 > 64) {
+        const double v0 = shfl_idx(u[0], tb), v1 = shfl_idx(u[1], tb), v2 = shfl_idx(u[2], tb);
+        const int c = (lane + 1) % 3;  // (64 + lane) % 3
+        if ((s.seg >> 30) & 1) out[64 + lane] = c == 0 ? v0 : (c == 1 ? v1 : v2);
+      }
+#endif
+    } else if constexpr (MODE == kSx && LDS && CAP == 0) {
+      if (A.u_out && s.valid && lane == s.last) store_point_capture(A.u_out, NE * s.pt, u);
+    }
     sym_mul(x.ei, u, v);
     // kSx: F^T (F x - E (E^T E)^-1 E^T F x);  kSpseZ: only the second term, F^T E (E^T E)^-1 E^T F x
     // (ImplicitSchurComplement::InversePowerSeriesOperatorRightMultiplyAccumulate, :146-174)
@@ -1258,6 +1292,7 @@ __device__ __forceinline__ void process_tile(const BalArgs& A, int64_t tile, int
     invert_spd_e(a, ei);
     if (s.valid && lane == s.last) store_ete_inverse(A, s.pt, ei);
     if constexpr (MODE == kInit) {
+      if (A.etb_out && s.valid && lane == s.last) store_point_capture(A.etb_out, po, r + kTriE);
       double g[NE];
 #pragma unroll
       for (int j = 0; j < NE; ++j) g[j] = r[kTriE + j];
@@ -1509,6 +1544,7 @@ __device__ __forceinline__ void process_long_point(const BalArgs& A, int64_t til
       if (lane == 0) store_ete_inverse(A, pt, ei);
     }
     if constexpr (MODE == kInit) {
+      if (A.etb_out && lane == 0) store_point_capture(A.etb_out, po, r + kTriE);
       double g[NE];
 #pragma unroll
       for (int j = 0; j < NE; ++j) g[j] = r[kTriE + j];
@@ -1683,6 +1719,9 @@ __device__ __forceinline__ void fused_long_rounds(const BalArgs& A, int lane, bo
       load_ete_inverse(A, pt, ei);
 #pragma unroll
       for (int j = 0; j < NE; ++j) u[j] = tot[j];
+      if constexpr (MODE == kSx && LDS) {
+        if (A.u_out && finish) store_point_capture(A.u_out, NE * pt, u);
+      }
       sym_mul(ei, u, v);
       if constexpr (MODE == kBackSub) {
         if (finish) store_point_solution(A, po, v);
@@ -1726,6 +1765,7 @@ __device__ __forceinline__ void fused_long_rounds(const BalArgs& A, int lane, bo
         if (finish) store_ete_inverse(A, pt, ei);
       }
       if constexpr (MODE == kInit) {
+        if (A.etb_out && finish) store_point_capture(A.etb_out, po, tot + kTriE);
         if (apply) {
           double g[NE];
 #pragma unroll
@@ -1745,6 +1785,9 @@ __global__ __launch_bounds__(BLOCK) void bal_fused_kernel(BalArgs A) {
   }
   if (A.status && *A.status != 0) return;  // CG already terminated: nothing to do
   if (A.run_after_cg && !CgStatusAllowsSolution(*A.run_after_cg)) return;  // speculative tail: CG has not ended (or failed)
+  if constexpr (MODE == kBackSub) {   // ... or the point tail, enqueued beside this pass, finishes the solve (device.h)
+    if (A.run_after_cg && A.skip_updates && PointTailTakes(*A.run_after_cg, *A.skip_updates)) return;
+  }
   constexpr bool kScatters = (MODE == kSx || MODE == kJtJx || MODE == kJtb || MODE == kInit || MODE == kCgnrInit || MODE == kColNorm || MODE == kSpseZ);
   Ctx acc;
   ctx_init(A, acc, nullptr);
@@ -2067,7 +2110,13 @@ __device__ __forceinline__ void cg_iteration_tail(const BalArgs& A, double* lds)
     if (pq <= 0 || isinf(pq)) fail = kCgIndefinite;
     else { alpha = rho / pq; if (isinf(alpha)) fail = kCgFailAlpha; }
   }
-  if (threadIdx.x == 0) { S.pq = pq; S.alpha = alpha; S.rho_new = rho; S.fail_step = fail; }
+  if (threadIdx.x == 0) {
+    S.pq = pq; S.alpha = alpha; S.rho_new = rho; S.fail_step = fail;
+    if (!fail) {   // x-update `it` is done: the point tail's history (device.h), as cg_update_kernel keeps it
+      if (it <= kPointTailMaxIterations) S.alpha_hist[it - 1] = alpha;
+      S.n_updates = it;
+    }
+  }
   if (fail) {
     if (threadIdx.x == 0) S.status = fail;
     return;
@@ -2145,7 +2194,7 @@ __device__ __forceinline__ void cg_iteration_tail(const BalArgs& A, double* lds)
 // A point of more than kRoundWaves tiles (flag != 0, the round is its own: waves [0, cnt0), cnt0 from the round's first word): in its
 // kRoundSum rounds every wave adds the round's total to `carry`; its kRoundApply rounds finish the (L2-warm) tiles with that sum.
 // JtJx has nothing to finish: its sum rounds do all the work, the last one stores y_e.
-template <int MODE, bool LDS>
+template <int MODE, bool LDS, bool CAP = false>
 __device__ __forceinline__ void compute_long_round(const BalArgs& A, const Slot& s, int lane, const StreamAux& x, uint32_t word, uint32_t word0,
                                                    int flag, int wave, double (*red)[3], double (&carry)[3], Ctx& acc, double& dot) {
   const bool active = word != kRoundIdle;
@@ -2156,6 +2205,7 @@ __device__ __forceinline__ void compute_long_round(const BalArgs& A, const Slot&
     f_times(s, acc, x.xc, t0, t1);
     double u[3] = {s.e[0] * t0 + s.e[3] * t1, s.e[1] * t0 + s.e[4] * t1, s.e[2] * t0 + s.e[5] * t1};
     if (!s.valid) { u[0] = u[1] = u[2] = 0; }
+    const int pt = __builtin_amdgcn_readfirstlane(s.pt);   // one segment: every valid lane holds the point (an idle wave: unused)
     if (!(flag & kRoundApply)) {
       wave_allreduce<3>(u);
       if (lane == 0) { red[wave][0] = u[0]; red[wave][1] = u[1]; red[wave][2] = u[2]; }
@@ -2167,7 +2217,16 @@ __device__ __forceinline__ void compute_long_round(const BalArgs& A, const Slot&
     } else {
       u[0] = u[1] = u[2] = 0;
       for (int k = 0; k < cnt; ++k) { u[0] += red[w0 + k][0]; u[1] += red[w0 + k][1]; u[2] += red[w0 + k][2]; }
-      if (flag & kRoundSum) { carry[0] += u[0]; carry[1] += u[1]; carry[2] += u[2]; return; }
+      if (flag & kRoundSum) {
+        carry[0] += u[0]; carry[1] += u[1]; carry[2] += u[2];
+        if constexpr (MODE == kSx && LDS) {   // the point's last sum round: its sum is complete, stored once by its first wave
+          if (CAP && (flag & kRoundLast) && active && wave == w0 && lane == 0) store_point_capture(A.u_out, NE * pt, carry);
+        }
+        return;
+      }
+      if constexpr (MODE == kSx && LDS) {     // a point of up to kRoundWaves tiles: its first wave stores
+        if (CAP && active && wave == w0 && lane == 0) store_point_capture(A.u_out, NE * pt, u);
+      }
     }
     double v[3];
     sym_mul(x.ei, u, v);
@@ -2209,7 +2268,7 @@ __device__ __forceinline__ void compute_long_round(const BalArgs& A, const Slot&
   }
 }
 
-template <int MODE, bool LDS, bool NT, bool F32 = false>
+template <int MODE, bool LDS, bool NT, bool F32 = false, bool CAP = false>   // CAP: the instantiation that keeps the points' sums (A.u_out set)
 __global__ __launch_bounds__(512) void bal_stream_kernel(BalArgs A) {
   constexpr int BLOCK = 512;
   extern __shared__ double lds_acc[];
@@ -2311,7 +2370,7 @@ __global__ __launch_bounds__(512) void bal_stream_kernel(BalArgs A) {
       if (ckind != 0) c.valid = false;  // long points are handled below; their seg words carry no store bits
       widen_slot<F32>(c);
       if constexpr (LDS) take_hot_x(A, c, xh, cx);
-      compute_stream<MODE, LDS>(A, c, lane, caux & 0xff, ckind == 0 ? caux >> 8 : 0, cx, acc, dot);
+      compute_stream<MODE, LDS, CAP ? 1 : 2>(A, c, lane, caux & 0xff, ckind == 0 ? caux >> 8 : 0, cx, acc, dot);
       __builtin_amdgcn_sched_barrier(0);
       i1 = i2;
       tile = min(tile + pstep, last);
@@ -2371,7 +2430,7 @@ __global__ __launch_bounds__(512) void bal_stream_kernel(BalArgs A) {
       if (ckind != 0) c.valid = false;  // long points are handled below; their seg words carry no store bits
       widen_slot<F32>(c);
       if constexpr (LDS) take_hot_x(A, c, xh, cx);
-      compute_stream<MODE, LDS>(A, c, lane, caux & 0xff, ckind == 0 ? caux >> 8 : 0, cx, acc, dot);
+      compute_stream<MODE, LDS, CAP ? 1 : 2>(A, c, lane, caux & 0xff, ckind == 0 ? caux >> 8 : 0, cx, acc, dot);
       __builtin_amdgcn_sched_barrier(0);
       i1 = i2;
       tile = next;
@@ -2454,7 +2513,7 @@ __global__ __launch_bounds__(512) void bal_stream_kernel(BalArgs A) {
         __builtin_amdgcn_sched_barrier(0);
         widen_slot<F32>(c);
         if constexpr (LDS) take_hot_x(A, c, xh, cx);
-        compute_long_round<MODE, LDS>(A, c, lane, cx, cw, cw0, cf, wave, round_red[par], carry, acc, dot);
+        compute_long_round<MODE, LDS, CAP>(A, c, lane, cx, cw, cw0, cf, wave, round_red[par], carry, acc, dot);
         __builtin_amdgcn_sched_barrier(0);
         par ^= 1;
         i1 = i2;
@@ -3474,6 +3533,82 @@ __global__ __launch_bounds__(1024) void bal_strip_finish_kernel(const double* __
   }
 }
 
+// The point tail of a short ITERATIVE_SCHUR solve that began at x = 0 (PointTailArgs, device.h; design/20_point_tail.md).  CG built
+// z = sum_k alpha_k p_k, and S.x pass k kept u_k[p] = sum over the point's observations of E^T F p_k, so E_p^T F z = U_p = sum_k alpha_k u_k[p]
+// (ascending k) and the point part of the solution is y_p = Ei_p (t_p - U_p), t_p = E_p^T b, Ei_p = (E_p^T E_p + D_p^2)^-1: no pass over J.
+// Model cost change of the step -(y, z), with g = J^T b, rhs = F^T b - sum_p F^T E Ei_p t_p and r = rhs - S z (CG's residual):
+//   (y.t + z.rhs + sum_p U_p.(Ei_p t_p) + z.r + |D_e y|^2 + |D_f z|^2) / 2
+// since (J^T J + D^2) (y, z) = g - (0, r) — the point rows hold exactly — and z.F^T b = z.rhs + sum_p U_p.(Ei_p t_p).  Every term is a sum
+// of products of like sign or small.  One partial per workgroup (its points' and its camera scalars' share of all six terms, halved),
+// summed by the host in index order.
+__global__ __launch_bounds__(kPointTailBlock) void bal_point_tail_kernel(PointTailArgs T) {
+  const int status = T.S->status, n = T.S->n_updates;
+  if (!PointTailTakes(status, n)) return;
+  double al[kPointTailMaxIterations];
+#pragma unroll
+  for (int k = 0; k < kPointTailMaxIterations; ++k) al[k] = k < n ? T.S->alpha_hist[k] : 0.0;
+  const double sg = T.negate ? -1.0 : 1.0;
+  const int64_t tid = int64_t(blockIdx.x) * kPointTailBlock + threadIdx.x, nthreads = int64_t(gridDim.x) * kPointTailBlock;
+  double cost = 0.0;
+  int bad = 0;
+  for (int64_t p = tid; p < T.n_points; p += nthreads) {
+    const int po = T.pt_pos ? T.pt_pos[p] : NE * int(p);
+    const double2* q = reinterpret_cast<const double2*>(T.etei + p * kEteiPitch);
+    double2 rec[kEteiPitch / 2];
+#pragma unroll
+    for (int j = 0; j < kEteiPitch / 2; ++j) rec[j] = q[j];
+    double ei[kTriE], U[NE], t[NE], w[NE], y[NE], eit[NE];
+#pragma unroll
+    for (int i = 0; i < kTriE; ++i) ei[i] = (i & 1) ? rec[i / 2].y : rec[i / 2].x;
+#pragma unroll
+    for (int j = 0; j < NE; ++j) { U[j] = 0.0; t[j] = T.etb[po + j]; }
+#pragma unroll
+    for (int k = 0; k < kPointTailMaxIterations; ++k) {
+      if (k < n) {   // (launch-uniform; buffers beyond n hold an earlier solve's sums, or nothing)
+#pragma unroll
+        for (int j = 0; j < NE; ++j) U[j] += al[k] * T.u_hist[k * T.u_stride + NE * p + j];
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < NE; ++j) w[j] = t[j] - U[j];
+    sym_mul(ei, w, y);
+    double fin = 0.0;
+#pragma unroll
+    for (int j = 0; j < NE; ++j) { T.y_e[po + j] = sg * y[j]; fin += y[j]; }
+    if (!isfinite(fin)) ++bad;
+    if (T.cost_out) {
+      sym_mul(ei, t, eit);
+#pragma unroll
+      for (int j = 0; j < NE; ++j) {
+        const double d = T.D_e ? T.D_e[po + j] * y[j] : 0.0;
+        cost += y[j] * t[j] + U[j] * eit[j] + d * d;
+      }
+    }
+  }
+  for (int64_t i = tid; i < T.n_f; i += nthreads) {   // the camera part: x_f = z, and the camera-space terms
+    const double z = T.z[i];
+    T.y_f[i] = sg * z;
+    if (!isfinite(z)) ++bad;
+    if (T.cost_out) {
+      const double d = T.D_f ? T.D_f[i] * z : 0.0;
+      cost += z * T.rhs[i] + z * T.r[i] + d * d;
+    }
+  }
+  if (bad && T.negate) atomicAdd(T.nonfinite, bad);
+  if (T.cost_out) {
+    __shared__ double red[kPointTailBlock / 64];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) cost += __shfl_xor(cost, m, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cost;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      double s = 0.0;
+      for (int i = 0; i < kPointTailBlock / 64; ++i) s += red[i];
+      T.cost_out[blockIdx.x] = 0.5 * s;
+    }
+  }
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -3509,10 +3644,10 @@ static hipError_t launch_fused(const BalArgs& A, bool lds, int grid, hipStream_t
 }
 
 #if CERES_HIP_PIPELINED
-template <int MODE, bool NT, bool F32 = false>
+template <int MODE, bool NT, bool F32 = false, bool CAP = false>
 static hipError_t launch_stream2(const BalArgs& A, bool lds, int grid, hipStream_t stream) {
   if (lds) {
-    auto k = bal_stream_kernel<MODE, true, NT, F32>;
+    auto k = bal_stream_kernel<MODE, true, NT, F32, CAP>;
     if (hipError_t e = AllowMaxLds(reinterpret_cast<const void*>(k)); e != hipSuccess) return e;
     // (+ the scratch of the CG iteration tail: cg_iteration_tail)
     const size_t tail_bytes = (kHasCgTail && MODE == kSx && A.tail.enabled) ? size_t(512 + kCgTailMax) * sizeof(double) : 0;
@@ -3542,6 +3677,9 @@ static hipError_t launch_stream(const BalArgs& A, bool lds, int grid, hipStream_
     }
   }
   const bool nt = A.n_tiles * int64_t(kTilePitch) * int64_t(sizeof(double2)) > (int64_t(kNonTemporalTileMiB) << 20);
+  if constexpr (MODE == kSx) {   // the capturing instantiation (point tail): every camera's accumulator in LDS, fp64 tiles
+    if (A.u_out && lds) return nt ? launch_stream2<MODE, true, false, true>(A, lds, grid, stream) : launch_stream2<MODE, false, false, true>(A, lds, grid, stream);
+  }
   return nt ? launch_stream2<MODE, true>(A, lds, grid, stream) : launch_stream2<MODE, false>(A, lds, grid, stream);
 }
 
@@ -3741,6 +3879,14 @@ static hipError_t CameraChunk(const ZUnits& units, const double* ring, double* a
   return hipGetLastError();
 }
 
+static hipError_t PointTail(const PointTailArgs& T, int* n_parts, hipStream_t stream) {
+  const int64_t work = std::max<int64_t>(T.n_points, T.n_f);
+  const int grid = int(std::max<int64_t>(1, std::min<int64_t>((work + kPointTailBlock - 1) / kPointTailBlock, kPointTailMaxGrid)));
+  if (n_parts) *n_parts = T.cost_out ? grid : 0;
+  hipLaunchKernelGGL(bal_point_tail_kernel, dim3(grid), dim3(kPointTailBlock), 0, stream, T);
+  return hipGetLastError();
+}
+
 }  // namespace CERES_HIP_SHAPE
 
 // the table solver.hip dispatches through (GetBalOps, kernels_bal_common.hip)
@@ -3750,7 +3896,7 @@ const BalOps* CERES_HIP_CAT(BalOps_, CERES_HIP_SHAPE)() {
   namespace sh = CERES_HIP_SHAPE;
   static const BalOps ops = {sh::NR, sh::NE, sh::NF, sh::NS, sh::kPairs, sh::kTilePitch, sh::kCamPart, sh::kEteiPitch, sh::kBPairs, sh::kMoPitch, sh::kHasF32 ? 1 : 0, sh::kHasCgTail ? 1 : 0,
                              sh::Fused, sh::SxRunsPipelined, sh::ReducePartials, sh::ReduceExchange, sh::StreamProbe, sh::AddFDiagonal, sh::Pack, sh::Invert, sh::CameraExchange,
-                             sh::CameraItems, sh::CameraFinish, sh::CameraChunk, sh::StripFinish};
+                             sh::CameraItems, sh::CameraFinish, sh::CameraChunk, sh::StripFinish, sh::PointTail};
   return &ops;
 }
 

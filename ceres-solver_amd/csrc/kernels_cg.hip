@@ -197,7 +197,7 @@ __global__ __launch_bounds__(kVecBlock) void cg_init_kernel(CgBuffers B, double 
     S.Q1 = 0; S.zeta = 0; S.norm_r = S.norm_rhs; S.norm_p = 0; S.norm_q = 0;
     S.iter = 1; S.min_it = min_it; S.max_it = max_it;
     S.status = kCgRunning;
-    S.fail_dir = 0; S.fail_step = 0;
+    S.fail_dir = 0; S.fail_step = 0; S.n_updates = 0;
     if (S.norm_rhs == 0.0) S.status = kCgZeroRhs;
     else if (min_it == 0 && S.norm_r <= S.tol_r) S.status = kCgInitialResidual;
     if (B.setup_fail && *B.setup_fail != 0) S.status = kCgSetupFailed;
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(kVecBlock) void cg_init_from_guess_finish_kernel(Cg
   S.Q0_pp[0] = Q0; S.Q0_pp[1] = Q0; S.rho_pp[0] = 1.0; S.rho_pp[1] = 1.0;
   S.iter = 1; S.min_it = min_it; S.max_it = max_it;
   S.status = kCgRunning;
-  S.fail_dir = 0; S.fail_step = 0;
+  S.fail_dir = 0; S.fail_step = 0; S.n_updates = 0;
   if (S.norm_rhs == 0.0) S.status = kCgZeroRhs;  // the host zeroes x in that case
   else if (min_it == 0 && S.norm_r <= S.tol_r) S.status = kCgInitialResidual;
   if (B.setup_fail && *B.setup_fail != 0) S.status = kCgSetupFailed;
@@ -559,6 +559,10 @@ __global__ __launch_bounds__(kVecBlock) void cg_update_kernel(CgBuffers B, GenSt
     S.alpha = alpha;
     S.rho_new = rho;
     S.fail_step = fail;
+    if (!fail) {   // x-update `it` is done: the point tail's history (device.h)
+      if (it <= kPointTailMaxIterations) S.alpha_hist[it - 1] = alpha;
+      S.n_updates = it;
+    }
   }
 }
 
@@ -590,7 +594,7 @@ __global__ __launch_bounds__(kVecBlock) void cg_begin_kernel(CgBuffers B, double
     S.Q0 = 0.0; S.Q1 = 0; S.zeta = 0; S.norm_r = norm_rhs; S.norm_p = 0; S.norm_q = 0;
     S.Q0_pp[0] = 0.0; S.Q0_pp[1] = 0.0; S.rho_pp[0] = 1.0; S.rho_pp[1] = rho;
     S.iter = 1; S.min_it = min_it; S.max_it = max_it;
-    S.fail_dir = fail_dir; S.fail_step = 0;
+    S.fail_dir = fail_dir; S.fail_step = 0; S.n_updates = 0;
     S.status = status;
   }
 }

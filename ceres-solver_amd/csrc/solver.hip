@@ -116,6 +116,20 @@ struct ceres_hip_solver {
   bool spec_tail_done = false;      // the gated tail and the copy sit in front of the last poll
   int spec_cgnr_parts = 0;
   int backsub_cost_parts = 0;       // partials it left in scalar_partials
+  // Point tail (design/20_point_tail.md): a short ITERATIVE_SCHUR solve from x = 0 gets its point part and model cost from the per-point
+  // sums its S.x passes kept instead of the back-substitution pass over J.  Which of the two finishes a solve depends on the options,
+  // the structure and THAT solve's CG outcome only (PointTailTakes, device.h) — never on earlier calls of the handle.
+  bool point_tail = true;           // CERES_HIP_POINT_TAIL (0: every solve back-substitutes over J)
+  bool point_tail_eligible = false; // options and structure allow it (set_structure): the buffers below exist
+  double* d_u_hist = nullptr;       // [kPointTailMaxIterations][num_cols_e]: E^T F p of CG iteration k + 1, indexed like y_e
+  double* d_etb = nullptr;          // [num_cols_e]: E^T b, left by kInit
+  bool pt_tail_armed = false;       // this solve captures (eligible, x0 = 0, fused CG iteration)
+  int cg_capture_it = 0;            // run_cg: the iteration whose S.p pass is being enqueued while it is one that captures, else 0
+  int cg_enqueued = 0;              // run_cg: iterations enqueued when before_poll runs
+  bool pt_tail_enqueued = false, backsub_enqueued = false;   // what the last before_poll put in front of the poll
+  bool backsub_skips_for_tail = false;   // op_back_substitute, gated: the pass also stays out where the point tail takes the solve
+  int pt_tail_parts = 0;            // cost partials the point tail leaves when it runs
+  int last_backsub_route = 0;       // ceres_hip_debug_last_backsub_route: 0 = the pass over J, 1 = the point tail
   bool lm_fuse_active = false;      // this step forms D inside the set-up kernels (no separate column-norm pass)
   ceres_hip_lm_options lm_opts{};
   double* d_camsq = nullptr;
@@ -682,6 +696,13 @@ int bal_scatter(ceres_hip_solver* s, int mode, BalArgs& A, const double* x_f, do
   return 0;
 }
 
+// Point tail: where the S.x pass of the CG iteration being enqueued keeps its per-point sums E^T F p (BalArgs::u_out) — only the
+// application to CG's direction (run_cg also applies S to x, every residual_reset_period-th iteration), nullptr otherwise.
+double* point_tail_capture(const ceres_hip_solver* s, const double* x) {
+  if (s->cg_capture_it < 1 || s->cg_capture_it > kPointTailMaxIterations || x != s->cg.p || !s->d_u_hist) return nullptr;
+  return s->d_u_hist + size_t(s->cg_capture_it - 1) * size_t(s->hs.num_cols_e);
+}
+
 // y = S x on F-space vectors.  ImplicitSchurComplement::RightMultiplyAndAccumulate.
 int op_sx(ceres_hip_solver* s, const double* x, double* y, const int* status, double* pq = nullptr, int* n_pq = nullptr) {
   const HostStructure& h = s->hs;
@@ -690,6 +711,7 @@ int op_sx(ceres_hip_solver* s, const double* x, double* y, const int* status, do
     TRY(ensure_packed(s));
     BalArgs A = bal_args(s);
     A.x_f = x;
+    A.u_out = point_tail_capture(s, x);
     return bal_scatter(s, kBalSx, A, x, y, true, status, pq, n_pq);
   }
   const double* v = s->values;
@@ -783,6 +805,7 @@ int op_schur_init(ceres_hip_solver* s, bool want_Mo) {
     BalArgs A = bal_args(s);
     A.D_e = s->D;
     A.Mo = want_Mo ? s->d_Mo : nullptr;
+    if (s->point_tail_eligible && s->have_b) A.etb_out = s->d_etb;   // E^T b per point, for the point tail
     if (s->clear_flags_pending) { A.clear_flags = s->d_nonfinite; s->clear_flags_pending = false; }
     PackGuard g = use_gather_if_unpacked(s, A);  // the step's first pass over J also writes the tiles
     if (s->have_b) {
@@ -835,7 +858,10 @@ int op_back_substitute(ceres_hip_solver* s, const double* z, double* x) {
     s->backsub_cost_parts = 0;
     if (s->lm_want_model_cost && z != nullptr) { A.scalar_out = s->scalar_partials; s->backsub_cost_parts = s->fused_grid; }
     if (h.num_cols_f > 0 && z != nullptr) { A.copy_src = z; A.copy_dst = x + h.num_cols_e; A.copy_n = h.num_cols_f; }
-    if (s->gate_on_cg_status) A.run_after_cg = &s->cg.S->status;
+    if (s->gate_on_cg_status) {
+      A.run_after_cg = &s->cg.S->status;
+      if (s->backsub_skips_for_tail) A.skip_updates = &s->cg.S->n_updates;
+    }
     if (s->lm_negate_in_solve && z != nullptr) {
       if (!s->nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), st));
       s->nonfinite_clean = false;
@@ -1201,6 +1227,26 @@ int enqueue_model_cost_change(ceres_hip_solver* s, const double* x, const double
   *dev_parts = s->cg.comm;
   return 0;
 }
+// The point tail of a solve that captured (pt_tail_armed): point part, camera copy (negated and checked for an LM step) and the model
+// cost's partials from point-space vectors; the kernel runs only where PointTailTakes (device.h) says so.  The caller has cleared the
+// finite-step flag.
+int op_point_tail(ceres_hip_solver* s, const double* z, double* x) {
+  const HostStructure& h = s->hs;
+  PointTailArgs T;
+  T.n_points = s->plan.n_points; T.n_f = h.num_cols_f;
+  T.pt_pos = s->plan.points_contiguous ? nullptr : s->d_pt_pos;
+  T.etei = s->etei; T.etb = s->d_etb; T.u_hist = s->d_u_hist; T.u_stride = h.num_cols_e;
+  T.D_e = s->D; T.D_f = s->D ? s->D + h.num_cols_e : nullptr;
+  T.z = z; T.rhs = s->rhs_f; T.r = s->cg.r;
+  T.y_e = x; T.y_f = x + h.num_cols_e;
+  T.negate = s->lm_negate_in_solve ? 1 : 0;
+  T.nonfinite = s->d_nonfinite;
+  T.S = s->cg.S;
+  T.cost_out = s->lm_want_model_cost ? s->scalar_partials : nullptr;
+  HIP_TRY(s, s->ops->point_tail(T, &s->pt_tail_parts, s->stream));
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // Conjugate gradients driver (I/conjugate_gradients_solver.h:108-306).
 // ---------------------------------------------------------------------------
@@ -1382,6 +1428,11 @@ int run_cg(ceres_hip_solver* s, const CgSpec& spec, double q_tol, double r_tol, 
   s->h_scalars->status = kCgRunning;
   s->timing.operator_applications = 0;
   int it = 1;
+  // point tail: the S.p passes of the first kPointTailMaxIterations iterations keep their per-point sums (op_sx, spec.iteration) — of a
+  // solve from x = 0 on the fused iteration, whose kernels keep alpha's history; no other caller's S.x pass ever captures
+  const bool capture = s->pt_tail_armed && fused_start;
+  s->pt_tail_armed = capture;
+  struct CaptureOff { ceres_hip_solver* s; ~CaptureOff() { s->cg_capture_it = 0; } } capture_off{s};
   auto precondition = [&]() -> int {
     if (spec.precondition) {
       TRY(spec.precondition(B.r, B.z));
@@ -1401,6 +1452,7 @@ int run_cg(ceres_hip_solver* s, const CgSpec& spec, double q_tol, double r_tol, 
     const int batch_end = std::min(max_it, it + interval - 1);
     for (; it <= batch_end; ++it) {
       const int reset = (it % reset_period == 0) ? 1 : 0;
+      s->cg_capture_it = (capture && it <= kPointTailMaxIterations) ? it : 0;
       if (fused && spec.iteration && !reset) {
         const int done = spec.iteration(it);
         if (done < 0) return CERES_HIP_E_HIP;
@@ -1447,6 +1499,8 @@ int run_cg(ceres_hip_solver* s, const CgSpec& spec, double q_tol, double r_tol, 
       TRY(collapse_and_reduce(s, 2, 2));
       HIP_TRY(s, LaunchCgFinalize(B, st));
     }
+    s->cg_capture_it = 0;
+    s->cg_enqueued = it - 1;
     if (spec.before_poll) TRY(spec.before_poll());
     TRY(poll_scalars(s));
     if (adaptive) { interval = first_batch ? 2 : std::min(16, interval * 2); first_batch = false; }
@@ -1883,6 +1937,7 @@ int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x
         if (!s->ops->sx_runs_pipelined(A)) return 0;
         CgBuffers& B = s->cg;
         A.x_f = B.p;
+        A.u_out = point_tail_capture(s, B.p);
         A.status = status;
         A.tail.enabled = 1; A.tail.it = it; A.tail.ticket = s->d_cg_ticket;
         A.tail.x = B.x; A.tail.r = B.r; A.tail.p = B.p; A.tail.z = B.z; A.tail.rhs = B.rhs;
@@ -1904,11 +1959,33 @@ int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x
       spec.x0_nonzero = true;
     }
     s->spec_tail_done = false;
+    // point tail: this solve captures if the handle is eligible, CG starts from x = 0 and runs the fused iteration (run_cg has the last word)
+    s->pt_tail_armed = s->point_tail_eligible && s->have_b && !spec.x0_nonzero && !spec.precondition && h.num_cols_f > 0;
+    s->pt_tail_enqueued = s->backsub_enqueued = false;
+    s->last_backsub_route = 0;
     if (s->lm_speculate && s->path == CERES_HIP_PATH_BAL && h.num_cols_f > 0) {
       spec.before_poll = [s, x]() {
-        s->gate_on_cg_status = true;
-        const int rc = op_back_substitute(s, s->cg.x, x);
-        s->gate_on_cg_status = false;
+        // The point tail and the pass over J carry complementary gates (PointTailTakes): the device runs one of them, by the solve's
+        // own outcome.  The pass over J is left out only while the iterations enqueued cannot go past the tail's reach.
+        int rc = 0;
+        s->pt_tail_enqueued = s->pt_tail_armed;
+        s->backsub_enqueued = !s->pt_tail_armed || s->cg_enqueued > kPointTailMaxIterations;
+        if (s->pt_tail_enqueued) {
+          if (s->lm_negate_in_solve) {   // (one clear for the two launches; op_back_substitute then skips its own)
+            if (!s->nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), s->stream));
+            s->nonfinite_clean = s->backsub_enqueued;
+            s->lm_negated = true;
+          }
+          rc = op_point_tail(s, s->cg.x, x);
+          if (rc) return rc;
+        }
+        if (s->backsub_enqueued) {
+          s->gate_on_cg_status = true;
+          s->backsub_skips_for_tail = s->pt_tail_enqueued;
+          rc = op_back_substitute(s, s->cg.x, x);
+          s->gate_on_cg_status = false;
+          s->backsub_skips_for_tail = false;
+        }
         if (rc) return rc;
         // sharded: {finite-step flag, this rank's share of the model cost} summed over ranks into the read-back image, in the same tail
         // (the exchange runs whether CG has ended or not — a handshake per epoch on every rank, p2p.h; its sums only mean something once it has)
@@ -1927,10 +2004,38 @@ int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x
         return 0;
       };
     }
-    TRY(run_cg(s, spec, q_tol, r_tol, summary));
+    const int rc_cg = run_cg(s, spec, q_tol, r_tol, summary);
+    const bool armed = s->pt_tail_armed;
+    s->pt_tail_armed = false;
+    TRY(rc_cg);
     TRY(rec(s, 5));
-    if (summary->termination_type != CERES_HIP_FAILURE && summary->termination_type != CERES_HIP_FATAL_ERROR && !s->spec_tail_done)
-      TRY(op_back_substitute(s, s->cg.x, x));
+    const bool usable = summary->termination_type != CERES_HIP_FAILURE && summary->termination_type != CERES_HIP_FATAL_ERROR;
+    // what the device decided, or what the host now decides, by the same rule: the solve's own status and update count
+    const bool tail_takes = armed && PointTailTakes(s->h_scalars->status, s->h_scalars->n_updates);
+    if (s->spec_tail_done) {
+      if (s->pt_tail_enqueued && tail_takes) {
+        s->last_backsub_route = 1;
+        s->backsub_cost_parts = s->pt_tail_parts;
+      } else if (!s->backsub_enqueued && usable) {
+        // CG ended inside the tail's reach in a state the tail does not take (a zero right-hand side, an indefinite matrix): nothing
+        // ran behind the poll — back-substitute now, ungated
+        s->spec_tail_done = false;
+        TRY(op_back_substitute(s, s->cg.x, x));
+      }
+    } else if (usable) {
+      if (tail_takes) {
+        if (s->lm_negate_in_solve) {
+          if (!s->nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), s->stream));
+          s->nonfinite_clean = false;
+          s->lm_negated = true;
+        }
+        TRY(op_point_tail(s, s->cg.x, x));
+        s->last_backsub_route = 1;
+        s->backsub_cost_parts = s->pt_tail_parts;
+      } else {
+        TRY(op_back_substitute(s, s->cg.x, x));
+      }
+    }
     TRY(rec(s, 6));
     return 0;
   }
@@ -2375,6 +2480,9 @@ static int set_structure_impl(ceres_hip_solver* s, const ceres_hip_block_structu
   TRY(dev_alloc(s, &s->cg_pq_parts, size_t(kMaxPqParts)));
   { const char* e = getenv("CERES_HIP_CG_FUSED"); s->cg_fused = !(e && atoi(e) == 0); }
   { const char* e = getenv("CERES_HIP_SPECULATE"); s->speculate = !(e && atoi(e) == 0); }
+  { const char* e = getenv("CERES_HIP_POINT_TAIL"); s->point_tail = !(e && atoi(e) == 0); }   // (A/B switch, and the tests' reference)
+  s->point_tail_eligible = false;
+  s->d_u_hist = s->d_etb = nullptr;
   s->cg.S = reinterpret_cast<CgScalars*>(s->scalar_partials + kScalarsOffset);
   HIP_TRY(s, hipMemsetAsync(s->cg.S, 0, sizeof(CgScalars), s->stream));
   // (+ 18 doubles per F block: room for the step's other camera-space sums right behind the blocks, see merged_layout)
@@ -2483,6 +2591,18 @@ static int set_structure_impl(ceres_hip_solver* s, const ceres_hip_block_structu
       s->chunk_grid = P.hybrid ? P.hyb_groups : int(std::max<int64_t>(1, std::min<int64_t>(s->num_cus, (chunk_tiles + 15) / 16)));
     }
     TRY(dev_alloc(s, &s->d_camsq, n9));
+    // Point tail: the plain one-GPU path with the cameras' accumulators in LDS, implicit ITERATIVE_SCHUR with a block-diagonal (or no)
+    // preconditioner on fp64 tiles, long points in rounds; everything else back-substitutes over J as before
+    s->point_tail_eligible = s->point_tail && s->opt.solver_type == CERES_HIP_ITERATIVE_SCHUR && !s->opt.use_explicit_schur_complement &&
+                             !is_cluster_jacobi(s) && s->opt.preconditioner_type != CERES_HIP_SCHUR_POWER_SERIES_EXPANSION && s->cg_fused &&
+                             s->world <= 1 && s->lds_mode && P.n_rem_rows == 0 && P.ns == 0 && s->opt.jacobian_storage != 1 &&
+                             h.num_cols_e > 0 && h.num_cols_f > 0 && s->ops->point_tail != nullptr &&
+                             // every long point is taken in rounds (plan.cc): the one-wave walk of a long point (tile kind 1) keeps no sums
+                             P.long_behind && P.n_tiles < (int64_t(1) << 26);
+    if (s->point_tail_eligible) {
+      TRY(dev_alloc(s, &s->d_u_hist, size_t(kPointTailMaxIterations) * size_t(h.num_cols_e)));
+      TRY(dev_alloc(s, &s->d_etb, size_t(h.num_cols_e)));
+    }
     if (P.ns > 0) TRY(dev_alloc(s, &s->d_strip_parts, size_t(s->fused_grid) * size_t(P.ns * (P.ns + 1) / 2)));
     if (s->cgnr_internal) TRY(dev_alloc(s, &s->D_int, size_t(h.num_cols_e)));
     if (s->world > 1 && (is_schur(s) ? (P.cameras_contiguous && P.cam_base == 0) : P.caller_contiguous) && int64_t(n9) == int64_t(h.num_cols_f)) {

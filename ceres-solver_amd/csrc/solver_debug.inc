@@ -1,5 +1,9 @@
 // solver_debug.inc — part of solver.hip (included there, after the solver struct and the operators): debug exports of the host-side plans (testable without a GPU) and DenseCholesky on a caller-supplied matrix
 
+// which way the last ITERATIVE_SCHUR solve of the handle got its point part (design/20_point_tail.md): 0 = the back-substitution pass over
+// J, 1 = the point tail; < 0: no handle
+int ceres_hip_debug_last_backsub_route(const ceres_hip_solver* s) { return s ? s->last_backsub_route : CERES_HIP_E_INVALID; }
+
 // ---- debug exports: the host-side packing plan, testable without a GPU -------
 int ceres_hip_debug_staged_x_plan(const ceres_hip_block_structure* bs, int32_t num_eliminate_blocks, int64_t counts[4], int32_t* staged_cam,
                                   int32_t* slot_word, int64_t staged_capacity, int64_t slot_capacity) {

@@ -106,6 +106,7 @@ ABI = [
     ("ceres_hip_comm_p2p_selftest", c_int32, [c_void_p]),
     ("ceres_hip_comm_p2p_disable", c_int32, [c_void_p]),
     ("ceres_hip_debug_allreduce_timing", c_int32, [c_void_p, c_int64, c_int32, _DP]),
+    ("ceres_hip_debug_last_backsub_route", c_int32, [c_void_p]),
     ("ceres_hip_solve", c_int32, [c_void_p, _DP, _DP, _DP, c_double, c_double, _DP, POINTER(CSummary)]),
     ("ceres_hip_solve_device", c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, POINTER(CSummary)]),
     ("ceres_hip_solve_unchanged_values", c_int32, [c_void_p, _DP, c_double, c_double, _DP, POINTER(CSummary)]),
@@ -460,6 +461,10 @@ class HipLinearSolver:
         out = np.zeros(1)
         self._check(self._lib.ceres_hip_debug_allreduce_timing(self._h, int(n), int(iters), _p(out)))
         return float(out[0])
+
+    def last_backsub_route(self) -> int:
+        """ceres_hip_debug_last_backsub_route: 0 = the last ITERATIVE_SCHUR solve back-substituted over J, 1 = it took the point tail."""
+        return int(self._lib.ceres_hip_debug_last_backsub_route(self._h))
 
     def p2p_disable(self):
         self._check(self._lib.ceres_hip_comm_p2p_disable(self._h))

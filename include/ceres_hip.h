@@ -242,6 +242,10 @@ int ceres_hip_comm_p2p_selftest(ceres_hip_solver* s);
 int ceres_hip_comm_p2p_disable(ceres_hip_solver* s);
 /* Debug / measurement (collective): average microseconds of `iters` back-to-back all-reduces of n doubles. */
 int ceres_hip_debug_allreduce_timing(ceres_hip_solver* s, int64_t n, int32_t iters, double* avg_us);
+/* Debug: how the last ITERATIVE_SCHUR solve of the handle got the point part of its solution — 0: the back-substitution pass over the
+ * Jacobian, 1: the point tail (short CG solves on the fused one-GPU path, formed from the S.x passes' per-point sums; CERES_HIP_POINT_TAIL=0
+ * in the environment of ceres_hip_set_structure switches it off).  Negative: no handle.                              */
+int ceres_hip_debug_last_backsub_route(const ceres_hip_solver* s);
 
 /* ---- the boundary call ----------------------------------------------------
  * LinearSolver::Solve (I/linear_solver.h:339-342).  values: num_nonzeros
