@@ -124,7 +124,7 @@ bool bal_writes_tiles(const ceres_hip_bal* p) {
   return s->path == CERES_HIP_PATH_BAL && s->ops && s->ops->ne == 3 && s->ops->nf == 9 && s->ops->ns == 0 && !s->d_Jf && s->d_J && s->world <= 1 &&
          !has_remainder(s) && !is_dense_schur(s) && !is_cluster_jacobi(s) && p->d_slot_obs &&   // (CLUSTER_JACOBI eliminates from the caller layout too)
          // (cameras' sums outside LDS AND no block preconditioner: the LM diagonal's column norms come from the generic kernel on every
-         // fresh step — lm_step_loaded, lm_fuse_active — which reads the caller layout)
+         // fresh step — lm_step_loaded, StepRequest::fuse — which reads the caller layout)
          (s->lds_mode || s->opt.preconditioner_type != CERES_HIP_IDENTITY);
 }
 

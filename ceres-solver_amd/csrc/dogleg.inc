@@ -15,7 +15,7 @@
 // u a + v b on the device, and u gradient + v gn in the strategy's scaled space.  One pass over J per Jacobian (kernels_dogleg.hip)
 // gives |Ja|^2, Ja.Jb, |Jb|^2, Ja.f, Jb.f, from which the Cauchy point, the subspace model and the model cost change of every step
 // follow on the host; a rejected step (reuse) costs no pass at all.  The Gauss-Newton solve forms no model cost change of its own
-// (lm_skip_model_cost: no kJx pass, no back-substitution partials).  A fresh step synchronises with the host twice: once for the
+// (lm_step_loaded's no_model_cost: no kJx pass, no back-substitution partials).  A fresh step synchronises with the host twice: once for the
 // solve's status and finite check (which decide a mu retry), once for the partial sums of the two kernels below.  Ceres forms J step
 // explicitly for the model cost change (I/trust_region_minimizer.cc:420-438); the scalar form -(u Ja + v Jb).(f + (u Ja + v Jb) / 2)
 // agrees with it up to rounding.
@@ -224,10 +224,8 @@ int dogleg_step(ceres_hip_bal* p, DoglegState& st, const ceres_hip_minimizer_opt
       ceres_hip_lm_options lo{};
       lo.radius = 1.0 / st.mu; lo.min_diagonal = o->min_lm_diagonal; lo.max_diagonal = o->max_lm_diagonal; lo.eta = 0.0;
       lo.reuse_diagonal = reuse_diagonal ? 1 : 0;
-      s->lm_skip_model_cost = true;   // (the LM step's own model cost change: no pass over J, the Gram pass below gives every step's)
-      const int rc = lm_step_loaded(s, &lo, p->d_dl_b, lr);
-      s->lm_skip_model_cost = false;
-      TRY(rc);
+      // (no_model_cost: the LM step forms no model cost change of its own — no pass over J, the Gram pass below gives every step's)
+      TRY(lm_step_loaded(s, &lo, p->d_dl_b, lr, true));
       HIP_TRY(s, hipStreamSynchronize(stream));
       ++*solves;
       reuse_diagonal = true;

@@ -93,45 +93,23 @@ struct ceres_hip_solver {
   double* d_cam_packed = nullptr;  // [cameras][kCamPart] sharded: the cameras' sums over their items and over ranks (camera_exchange)
   ZUnits zunits;                   // chunked camera-major pass (cameras not in LDS): all chunks' units
   int chunk_grid = 0;              // workgroups of one chunk's tile pass
-  // f1: LM step state
+  // f1: LM step state that outlives a step (what one call asks for and reports travels in StepRequest / StepOutcome / SolveCtx below)
   double *lm_diag = nullptr, *lm_D = nullptr, *scalar_partials = nullptr;
   int* d_nonfinite = nullptr;
-  bool clear_flags_pending = false;   // the solve's first fused pass still has to clear the two flags (solve_loaded_impl)
-  bool fail_flag_clean = false, nonfinite_clean = false;  // cleared together at the start of a solve: the per-operator memsets are skipped once
   bool have_lm_diag = false;
-  bool lm_want_model_cost = false;  // op_back_substitute also accumulates the model cost change (fused <2,3,9> path)
-  bool lm_skip_model_cost = false;  // set by the caller of lm_step_loaded (the dogleg strategy): Schur solvers form no model cost change
-  // LM step on the fused path: the last kernel that touches the solution writes the negated step and checks it for finiteness
-  // (ITERATIVE_SCHUR: the back-substitution kernel; CGNR: the model-cost kernel, which then also replaces the copy-out of x)
-  bool lm_negate_in_solve = false;
-  bool lm_negated = false;          // set by whoever did it (or, for CGNR, deferred it: lm_cgnr_copy_pending)
-  bool lm_cgnr_copy_pending = false;
   // Speculative tail (one host synchronisation per LM step instead of two): before each poll of the CG status word the solvers
   // enqueue the rest of the step — back-substitution (ITERATIVE_SCHUR) or the model-cost kernel (CGNR), negation and finite
   // check folded in, and the read-back copy of {cost partials, flags} — gated ON THE DEVICE by the status word, so that the
   // poll that sees CG end has the step's results behind it already.  CERES_HIP_SPECULATE=0 switches it off.
   bool speculate = true;            // CERES_HIP_SPECULATE
-  bool lm_speculate = false;        // asked for by lm_step_loaded (fused path, one rank)
-  bool gate_on_cg_status = false;   // op_back_substitute: launch gated
-  bool spec_tail_done = false;      // the gated tail and the copy sit in front of the last poll
-  int spec_cgnr_parts = 0;
-  int backsub_cost_parts = 0;       // partials it left in scalar_partials
   // Point tail (design/20_point_tail.md): a short ITERATIVE_SCHUR solve from x = 0 gets its point part and model cost from the per-point
   // sums its S.x passes kept instead of the back-substitution pass over J.  Which of the two finishes a solve depends on the options,
-  // the structure and THAT solve's CG outcome only (PointTailTakes, device.h) — never on earlier calls of the handle.
+  // the structure and THAT solve's CG outcome only (PointTailTakes, device.h).
   bool point_tail = true;           // CERES_HIP_POINT_TAIL (0: every solve back-substitutes over J)
   bool point_tail_eligible = false; // options and structure allow it (set_structure): the buffers below exist
   double* d_u_hist = nullptr;       // [kPointTailMaxIterations][num_cols_e]: E^T F p of CG iteration k + 1, indexed like y_e
   double* d_etb = nullptr;          // [num_cols_e]: E^T b, left by kInit
-  bool pt_tail_armed = false;       // this solve captures (eligible, x0 = 0, fused CG iteration)
-  int cg_capture_it = 0;            // run_cg: the iteration whose S.p pass is being enqueued while it is one that captures, else 0
-  int cg_enqueued = 0;              // run_cg: iterations enqueued when before_poll runs
-  bool pt_tail_enqueued = false, backsub_enqueued = false;   // what the last before_poll put in front of the poll
-  bool backsub_skips_for_tail = false;   // op_back_substitute, gated: the pass also stays out where the point tail takes the solve
-  int pt_tail_parts = 0;            // cost partials the point tail leaves when it runs
   int last_backsub_route = 0;       // ceres_hip_debug_last_backsub_route: 0 = the pass over J, 1 = the point tail
-  bool lm_fuse_active = false;      // this step forms D inside the set-up kernels (no separate column-norm pass)
-  ceres_hip_lm_options lm_opts{};
   double* d_camsq = nullptr;
   int64_t *d_pt_diag_off = nullptr, *d_cam_diag_off = nullptr;  // into the all-blocks store (CGNR JACOBI)
   int64_t* d_pt_eoff = nullptr;                                 // into the E-block store (ceres_hip_get_ete_inverse)
@@ -144,10 +122,8 @@ struct ceres_hip_solver {
   // kernels (compact row space), the residual offset of the first of them, a row-space temporary and their F^T F per camera
   // Sharded <2,3,9> steps sum their per-step camera-space quantities in ONE all-reduce: the buffers sit back to back
   // (ITERATIVE_SCHUR: [preconditioner blocks 81 n_c | rhs 9 n_c | camera column norms 9 n_c]; CGNR: [camera blocks 81 n_c | J^T f,
-  // camera part 9 n_c]) and the first producer defers its collective to the last one (solve_loaded sets merge_step_reduce).
+  // camera part 9 n_c]) and the first producer defers its collective to the last one (the solve passes `merge` to it).
   bool merged_layout = false;       // the buffers were allocated back to back (set_structure)
-  bool merge_step_reduce = false;   // this solve may defer
-  bool rhs_reduce_pending = false;  // rhs holds this rank's raw sums; the all-reduce is still owed
   double* cgnr_rhs_tail = nullptr;  // CGNR: 9 n_c doubles behind the camera blocks of `precond`
   GenStructure GR;
   int rem_rows = 0, rem_b0 = 0;   // rem_b0: where the remainder's residuals begin in b when its rows trail, -1: gathered through d_rem_row_map
@@ -424,6 +400,44 @@ bool is_schur(const ceres_hip_solver* s) { return s->opt.solver_type == CERES_HI
 bool is_cluster_jacobi(const ceres_hip_solver* s) { return s->opt.solver_type == CERES_HIP_ITERATIVE_SCHUR && s->opt.preconditioner_type == CERES_HIP_CLUSTER_JACOBI; }
 
 // ---------------------------------------------------------------------------
+// One solve's arguments, results and promises (design/21_solve_context.md).  A field goes on the handle only if it outlives the call.
+// ---------------------------------------------------------------------------
+// What the caller asks of this solve (lm_step_loaded fills it).  Default-constructed: a plain Solve.
+struct StepRequest {
+  // LM step on the fused path: the last kernel that touches the solution writes the negated step and checks it for finiteness
+  // (ITERATIVE_SCHUR: the back-substitution kernel or the point tail; CGNR: the model-cost kernel, which then also replaces the copy-out of x)
+  bool negate_in_solve = false;
+  bool want_model_cost = false;   // op_back_substitute / op_point_tail also accumulate the model cost change (fused <2,3,9> path)
+  bool skip_model_cost = false;   // the caller of lm_step_loaded (the dogleg strategy) wants no model cost change from a Schur solver
+  bool speculate = false;         // enqueue the step's tail in front of every poll of the CG status word, gated on the device
+  const ceres_hip_lm_options* fuse = nullptr;   // != nullptr: this step forms D inside the set-up kernels, from these options (no column-norm pass)
+};
+// What the solve did (lm_step_loaded reads it back).
+struct StepOutcome {
+  bool negated = false;             // somebody wrote the negated, checked step (or, for CGNR, deferred it: cgnr_copy_pending)
+  bool cgnr_copy_pending = false;
+  bool spec_tail_done = false;      // the gated tail and the read-back sit in front of the last poll
+  int spec_cgnr_parts = 0;          // cost partials the gated CGNR model-cost kernel left
+  int backsub_cost_parts = 0;       // cost partials in scalar_partials (op_back_substitute, or the point tail where it took the solve)
+  int pt_tail_parts = 0;            // cost partials the point tail leaves when it runs
+  bool pt_tail_enqueued = false, backsub_enqueued = false;   // what the last before_poll put in front of the poll
+  int route = -1;                   // implicit ITERATIVE_SCHUR that reached CG: 0 = the pass over J, 1 = the point tail (-> last_backsub_route)
+};
+// The context solve_loaded owns for one solve: request, outcome, and what one phase promises a later one.  An operator-level call
+// (solver_ops.inc, ceres_hip_time_op) passes a fresh one: a plain request, nothing promised — it clears its own flags and issues its
+// own all-reduce.
+struct SolveCtx {
+  const StepRequest rq{};
+  StepOutcome out;
+  bool clear_flags_pending = false;   // the solve's first fused pass still has to clear the two flags
+  bool fail_flag_clean = false, nonfinite_clean = false;  // cleared together at the start of the solve: the per-operator memsets are skipped once
+  bool rhs_reduce_pending = false;    // rhs holds this rank's raw sums; the all-reduce is still owed
+  SolveCtx() = default;
+  explicit SolveCtx(const StepRequest& r) : rq(r) {}
+};
+enum class BacksubGate { kNone, kOnCgStatus, kOnCgStatusBehindTail };   // op_back_substitute: ungated; gated; gated and staying out where the point tail takes the solve
+
+// ---------------------------------------------------------------------------
 // Operators.  All take device pointers and enqueue on s->stream.
 // ---------------------------------------------------------------------------
 // Camera space small enough for the S.x pass to finish the CG iteration itself (CgTail, device.h)?  ITERATIVE_SCHUR on the fused path,
@@ -437,7 +451,7 @@ bool cg_tail_possible(const ceres_hip_solver* s) {
          h.num_cols_f > 0 && h.num_cols_f <= kCgTailMax && s->fused_grid <= kCgTailLoads * (512 / std::max(1, h.num_cols_f));
 }
 
-BalArgs bal_args(ceres_hip_solver* s) {
+BalArgs bal_args(ceres_hip_solver* s, const StepRequest& rq = StepRequest()) {
   BalArgs A;
   A.J = s->d_J; A.Jf = s->d_Jf; A.b = s->d_bt;
   A.slot_cam = s->d_slot_cam; A.tile_pt0 = s->d_tile_pt0; A.slot_seg = s->d_slot_seg;
@@ -459,8 +473,8 @@ BalArgs bal_args(ceres_hip_solver* s) {
   for (int j = 0; j < kMaxSharedScalars; ++j) A.sh_pos[j] = j < s->plan.ns_used ? s->plan.sh_pos[j] : -1;
   A.have_b = s->have_b ? 1 : 0;
   A.flags = s->bal_flags;
-  if (s->lm_fuse_active) {
-    A.lm_radius = s->lm_opts.radius; A.lm_min = s->lm_opts.min_diagonal; A.lm_max = s->lm_opts.max_diagonal;
+  if (rq.fuse) {   // (read by the set-up passes only: kInit, kCgnrInit)
+    A.lm_radius = rq.fuse->radius; A.lm_min = rq.fuse->min_diagonal; A.lm_max = rq.fuse->max_diagonal;
     A.lm_diag_e = s->lm_diag; A.lm_D_e = s->lm_D;
   }
   return A;
@@ -509,10 +523,10 @@ int ensure_packed(ceres_hip_solver* s) {
   return g.commit(0);
 }
 
-LmFuse lm_fuse_for_cameras(ceres_hip_solver* s, bool schur_blocks) {
+LmFuse lm_fuse_for_cameras(ceres_hip_solver* s, const StepRequest& rq, bool schur_blocks) {
   LmFuse f;
-  if (!s->lm_fuse_active) return f;
-  f.radius = s->lm_opts.radius; f.min_d = s->lm_opts.min_diagonal; f.max_d = s->lm_opts.max_diagonal;
+  if (!rq.fuse) return f;
+  f.radius = rq.fuse->radius; f.min_d = rq.fuse->min_diagonal; f.max_d = rq.fuse->max_diagonal;
   f.camsq = schur_blocks ? s->d_camsq : nullptr;
   f.cam_pos = s->plan.cameras_contiguous ? nullptr : s->d_cam_pos;
   f.cam_base = s->plan.cam_base;
@@ -696,22 +710,22 @@ int bal_scatter(ceres_hip_solver* s, int mode, BalArgs& A, const double* x_f, do
   return 0;
 }
 
-// Point tail: where the S.x pass of the CG iteration being enqueued keeps its per-point sums E^T F p (BalArgs::u_out) — only the
-// application to CG's direction (run_cg also applies S to x, every residual_reset_period-th iteration), nullptr otherwise.
-double* point_tail_capture(const ceres_hip_solver* s, const double* x) {
-  if (s->cg_capture_it < 1 || s->cg_capture_it > kPointTailMaxIterations || x != s->cg.p || !s->d_u_hist) return nullptr;
-  return s->d_u_hist + size_t(s->cg_capture_it - 1) * size_t(s->hs.num_cols_e);
+// Point tail: where the S.x pass of CG iteration `it` keeps its per-point sums E^T F p (BalArgs::u_out); nullptr beyond the tail's reach.
+// run_cg hands it to the application to CG's direction only (it also applies S to x, every residual_reset_period-th iteration).
+double* point_tail_capture(const ceres_hip_solver* s, int it) {
+  if (it < 1 || it > kPointTailMaxIterations || !s->d_u_hist) return nullptr;
+  return s->d_u_hist + size_t(it - 1) * size_t(s->hs.num_cols_e);
 }
 
 // y = S x on F-space vectors.  ImplicitSchurComplement::RightMultiplyAndAccumulate.
-int op_sx(ceres_hip_solver* s, const double* x, double* y, const int* status, double* pq = nullptr, int* n_pq = nullptr) {
+int op_sx(ceres_hip_solver* s, const double* x, double* y, const int* status, double* pq = nullptr, int* n_pq = nullptr, double* u_out = nullptr) {
   const HostStructure& h = s->hs;
   if (n_pq) *n_pq = 0;
   if (s->path == CERES_HIP_PATH_BAL) {
     TRY(ensure_packed(s));
     BalArgs A = bal_args(s);
     A.x_f = x;
-    A.u_out = point_tail_capture(s, x);
+    A.u_out = u_out;
     return bal_scatter(s, kBalSx, A, x, y, true, status, pq, n_pq);
   }
   const double* v = s->values;
@@ -798,20 +812,21 @@ int op_jtb(ceres_hip_solver* s, double* y) {
 }
 
 // ImplicitSchurComplement::Init: (E^T E + D_e^2)^-1 blocks and rhs.
-int op_schur_init(ceres_hip_solver* s, bool want_Mo) {
+// merge: a sharded solve whose preconditioner pass takes rhs along in its all-reduce (cx.rhs_reduce_pending)
+int op_schur_init(ceres_hip_solver* s, SolveCtx& cx, bool want_Mo, bool merge = false) {
   const HostStructure& h = s->hs;
   hipStream_t st = s->stream;
   if (s->path == CERES_HIP_PATH_BAL) {
-    BalArgs A = bal_args(s);
+    BalArgs A = bal_args(s, cx.rq);
     A.D_e = s->D;
     A.Mo = want_Mo ? s->d_Mo : nullptr;
     if (s->point_tail_eligible && s->have_b) A.etb_out = s->d_etb;   // E^T b per point, for the point tail
-    if (s->clear_flags_pending) { A.clear_flags = s->d_nonfinite; s->clear_flags_pending = false; }
+    if (cx.clear_flags_pending) { A.clear_flags = s->d_nonfinite; cx.clear_flags_pending = false; }
     PackGuard g = use_gather_if_unpacked(s, A);  // the step's first pass over J also writes the tiles
     if (s->have_b) {
-      const bool defer = s->world > 1 && s->merge_step_reduce && s->merged_layout;
+      const bool defer = s->world > 1 && merge && s->merged_layout;
       TRY(g.commit(bal_scatter(s, kBalInit, A, nullptr, s->rhs_f, false, nullptr, nullptr, nullptr, nullptr, defer)));
-      s->rhs_reduce_pending = defer;
+      cx.rhs_reduce_pending = defer;
       return 0;
     }
     // no residuals: only the inverses (and M_o) are needed; nothing is scattered
@@ -846,7 +861,7 @@ int op_schur_init(ceres_hip_solver* s, bool want_Mo) {
 
 // ImplicitSchurComplement::BackSubstitute: z (F space, may be nullptr if there are no F
 // blocks) -> x (full space).
-int op_back_substitute(ceres_hip_solver* s, const double* z, double* x) {
+int op_back_substitute(ceres_hip_solver* s, SolveCtx& cx, const double* z, double* x, BacksubGate gate = BacksubGate::kNone) {
   const HostStructure& h = s->hs;
   hipStream_t st = s->stream;
   if (!s->have_b) return fail(s, CERES_HIP_E_INVALID, "no residual vector loaded");
@@ -855,23 +870,23 @@ int op_back_substitute(ceres_hip_solver* s, const double* z, double* x) {
     BalArgs A = bal_args(s);
     A.x_f = z; A.y_e = x;
     // f1: the LM step wants the model cost change of -x; the kernel has J x in hand (one partial per workgroup)
-    s->backsub_cost_parts = 0;
-    if (s->lm_want_model_cost && z != nullptr) { A.scalar_out = s->scalar_partials; s->backsub_cost_parts = s->fused_grid; }
+    cx.out.backsub_cost_parts = 0;
+    if (cx.rq.want_model_cost && z != nullptr) { A.scalar_out = s->scalar_partials; cx.out.backsub_cost_parts = s->fused_grid; }
     if (h.num_cols_f > 0 && z != nullptr) { A.copy_src = z; A.copy_dst = x + h.num_cols_e; A.copy_n = h.num_cols_f; }
-    if (s->gate_on_cg_status) {
+    if (gate != BacksubGate::kNone) {
       A.run_after_cg = &s->cg.S->status;
-      if (s->backsub_skips_for_tail) A.skip_updates = &s->cg.S->n_updates;
+      if (gate == BacksubGate::kOnCgStatusBehindTail) A.skip_updates = &s->cg.S->n_updates;
     }
-    if (s->lm_negate_in_solve && z != nullptr) {
-      if (!s->nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), st));
-      s->nonfinite_clean = false;
+    if (cx.rq.negate_in_solve && z != nullptr) {
+      if (!cx.nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), st));
+      cx.nonfinite_clean = false;
       A.negate_out = 1; A.nonfinite = s->d_nonfinite;
-      s->lm_negated = true;
+      cx.out.negated = true;
     }
     HIP_TRY(s, s->ops->fused(kBalBackSub, A, false, s->fused_grid, st));
-    if (s->backsub_cost_parts > 0 && has_remainder(s)) {  // the rows outside the tiles: one more partial sum behind the workgroups'
-      TRY(rem_model_cost(s, z, 0, s->scalar_partials + s->backsub_cost_parts));
-      ++s->backsub_cost_parts;
+    if (cx.out.backsub_cost_parts > 0 && has_remainder(s)) {  // the rows outside the tiles: one more partial sum behind the workgroups'
+      TRY(rem_model_cost(s, z, 0, s->scalar_partials + cx.out.backsub_cost_parts));
+      ++cx.out.backsub_cost_parts;
     }
     return 0;
   } else {
@@ -936,21 +951,21 @@ int shared_preconditioner_blocks(ceres_hip_solver* s, bool schur, double* out, b
 // Preconditioner blocks into `out`; invert = false leaves them as assembled.
 //   ITERATIVE_SCHUR: SCHUR_JACOBI (diag blocks of S) or JACOBI (blockdiag(F^T F + D_f^2)), F blocks
 //   CGNR:            JACOBI, all column blocks
-int op_preconditioner(ceres_hip_solver* s, int type, double* out, bool invert) {
+int op_preconditioner(ceres_hip_solver* s, SolveCtx& cx, int type, double* out, bool invert) {
   const HostStructure& h = s->hs;
   hipStream_t st = s->stream;
   const double* D_f = s->D ? s->D + h.num_cols_e : nullptr;
-  if (!s->fail_flag_clean) HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
-  s->fail_flag_clean = false;
+  if (!cx.fail_flag_clean) HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
+  cx.fail_flag_clean = false;
   if (is_schur(s)) {
     const int nf = h.ncb - h.nelim;
     const int64_t len = h.diag_off_f.back();
     if (s->path == CERES_HIP_PATH_BAL) {
       const bool schur = type == CERES_HIP_SCHUR_JACOBI;
-      const bool fuse = s->lm_fuse_active && invert;
+      const bool fuse = cx.rq.fuse && invert;
       HIP_TRY(s, s->ops->camera_items(schur, s->values, s->cam_items, s->d_cam_fpos, s->d_cam_slot, s->d_Mo, s->d_cam_parts, st));
       TRY(ensure_rem_blocks(s));  // rows without a point cell add their F^T F to the diagonal cells (NoEBlockRowsUpdate) and to the column norms
-      if (s->world > 1 && invert && camera_blocks_exchange(s) && !s->rhs_reduce_pending) {
+      if (s->world > 1 && invert && camera_blocks_exchange(s) && !cx.rhs_reduce_pending) {
         // sharded: the inversion kernel adds up this rank's items, sums the packed blocks (and column norms) over ranks (p2p.h), adds
         // D_f^2 — or forms the fused LM diagonal from the summed norms — and inverts: one launch, one exchange
         HIP_TRY(s, s->ops->camera_exchange(s->d_cam_parts, s->d_cam_item_ptr, s->plan.n_cameras, rem_extra_blocks(s), s->d_cam_packed, next_exchange(s),
@@ -960,7 +975,7 @@ int op_preconditioner(ceres_hip_solver* s, int type, double* out, bool invert) {
         g.D_f = fuse ? nullptr : D_f;
         g.cam_pos = s->plan.cameras_contiguous ? nullptr : s->d_cam_pos;
         g.cam_base = s->plan.cam_base;
-        HIP_TRY(s, s->ops->invert(out, cam_f_offsets(s), s->plan.n_cameras, s->d_fail_flag, fuse ? lm_fuse_for_cameras(s, false) : LmFuse(), g, st));
+        HIP_TRY(s, s->ops->invert(out, cam_f_offsets(s), s->plan.n_cameras, s->d_fail_flag, fuse ? lm_fuse_for_cameras(s, cx.rq, false) : LmFuse(), g, st));
       } else if (s->world <= 1 && invert) {
         // the inversion kernel adds up a camera's items itself (+ D_f^2, or the fused LM diagonal it forms from them)
         CamGather g;
@@ -969,7 +984,7 @@ int op_preconditioner(ceres_hip_solver* s, int type, double* out, bool invert) {
         g.D_f = fuse ? nullptr : D_f;
         g.cam_pos = s->plan.cameras_contiguous ? nullptr : s->d_cam_pos;
         g.cam_base = s->plan.cam_base;
-        HIP_TRY(s, s->ops->invert(out, cam_f_offsets(s), s->plan.n_cameras, s->d_fail_flag, fuse ? lm_fuse_for_cameras(s, false) : LmFuse(), g, st));
+        HIP_TRY(s, s->ops->invert(out, cam_f_offsets(s), s->plan.n_cameras, s->d_fail_flag, fuse ? lm_fuse_for_cameras(s, cx.rq, false) : LmFuse(), g, st));
         TRY(shared_preconditioner_blocks(s, schur, out, true));
       } else {
         // raw sums in memory first (no diagonal when sharded: the ranks' sums are added up, then D_f^2 joins once)
@@ -979,10 +994,10 @@ int op_preconditioner(ceres_hip_solver* s, int type, double* out, bool invert) {
         if (s->world > 1) TRY(shared_preconditioner_blocks(s, schur, out, false, false));   // this rank's raw sums join the all-reduce of the block store
         if (s->world > 1) {
           const size_t n9c = size_t(h.num_cols_f);   // rhs / column norms: every camera-side scalar (the cameras' and a shared strip's)
-          if (s->rhs_reduce_pending && out == s->precond && s->merged_layout) {
+          if (cx.rhs_reduce_pending && out == s->precond && s->merged_layout) {
             // ONE collective for the step's camera-space sums: [blocks | rhs | column norms] are contiguous (set_structure)
             TRY(allreduce(s, out, size_t(len) + n9c + ((fuse && schur) ? n9c : 0)));
-            s->rhs_reduce_pending = false;
+            cx.rhs_reduce_pending = false;
           } else {
             TRY(allreduce(s, out, size_t(len)));
             if (fuse && schur) TRY(allreduce(s, s->d_camsq, n9c));  // column norms of the camera columns
@@ -990,7 +1005,7 @@ int op_preconditioner(ceres_hip_solver* s, int type, double* out, bool invert) {
           // fused LM diagonal: D_f does not exist yet, bal_invert9_kernel forms it from the reduced sums and adds it
           if (D_f && !fuse) HIP_TRY(s, LaunchAddBlockDiagonalSquares(s->G, h.nelim, nf, s->G.diag_off_f, s->D, out, st));
         }
-        if (invert) HIP_TRY(s, s->ops->invert(out, cam_f_offsets(s), s->plan.n_cameras, s->d_fail_flag, fuse ? lm_fuse_for_cameras(s, schur) : LmFuse(), CamGather(), st));
+        if (invert) HIP_TRY(s, s->ops->invert(out, cam_f_offsets(s), s->plan.n_cameras, s->d_fail_flag, fuse ? lm_fuse_for_cameras(s, cx.rq, schur) : LmFuse(), CamGather(), st));
         if (s->world > 1) { if (invert) TRY(invert_shared_blocks(s, out)); }
         else TRY(shared_preconditioner_blocks(s, schur, out, invert));
       }
@@ -1046,15 +1061,16 @@ int op_preconditioner(ceres_hip_solver* s, int type, double* out, bool invert) {
 // point blocks; the camera blocks follow from the camera-major pass.  Replaces
 // BlockSparseJacobiPreconditioner::UpdateImpl + A->LeftMultiplyAndAccumulate(b)
 // (I/cgnr_solver.cc:152-191) = two passes over J, and absorbs the re-layout pass.
-int op_cgnr_setup_bal(ceres_hip_solver* s, bool jacobi, double* rhs, double* blocks) {
+// merge_step_reduce: a sharded solve may let the camera part of rhs ride in the camera blocks' all-reduce
+int op_cgnr_setup_bal(ceres_hip_solver* s, SolveCtx& cx, bool jacobi, double* rhs, double* blocks, bool merge_step_reduce = false) {
   const HostStructure& h = s->hs;
   hipStream_t st = s->stream;
   const double* D_f = s->D ? s->D + h.num_cols_e : nullptr;
   const int64_t len = h.diag_off_all.back();
-  if (!s->fail_flag_clean) HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
-  s->fail_flag_clean = false;
-  BalArgs A = bal_args(s);
-  if (s->clear_flags_pending) { A.clear_flags = s->d_nonfinite; s->clear_flags_pending = false; }
+  if (!cx.fail_flag_clean) HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
+  cx.fail_flag_clean = false;
+  BalArgs A = bal_args(s, cx.rq);
+  if (cx.clear_flags_pending) { A.clear_flags = s->d_nonfinite; cx.clear_flags_pending = false; }
   A.etei = nullptr;
   A.D_e = s->D;
   A.y_e = rhs;
@@ -1063,11 +1079,11 @@ int op_cgnr_setup_bal(ceres_hip_solver* s, bool jacobi, double* rhs, double* blo
   if (s->cgnr_internal) {  // rhs and the point blocks in CG's order; D read at the caller's offsets and left in CG's order on the way
     use_internal_points(s, A);
     A.D_int_out = s->D_int;
-    s->D_int_valid = jacobi && (s->D != nullptr || s->lm_fuse_active);
+    s->D_int_valid = jacobi && (s->D != nullptr || cx.rq.fuse);
     if (jacobi && blocks == s->precond) s->precond_internal = true;
   }
   // sharded with JACOBI: the camera part of J^T f is left raw behind the camera blocks and rides in their all-reduce
-  const bool merge = s->world > 1 && jacobi && s->merge_step_reduce && s->merged_layout && blocks == s->precond && s->cgnr_rhs_tail;
+  const bool merge = s->world > 1 && jacobi && merge_step_reduce && s->merged_layout && blocks == s->precond && s->cgnr_rhs_tail;
   {
     PackGuard g = use_gather_if_unpacked(s, A);
     TRY(g.commit(bal_scatter(s, kBalCgnrInit, A, nullptr, merge ? s->cgnr_rhs_tail : rhs + h.num_cols_e, false, nullptr, nullptr, nullptr, nullptr, merge)));
@@ -1081,8 +1097,8 @@ int op_cgnr_setup_bal(ceres_hip_solver* s, bool jacobi, double* rhs, double* blo
     g.parts = s->d_cam_parts; g.cam_item_ptr = s->d_cam_item_ptr; g.few = s->cam_items_few ? 1 : 0; g.cam_pos = cam_pos;
     g.cam_base = s->plan.cam_base;
     g.extra = rem_extra_blocks(s);
-    g.D_f = s->lm_fuse_active ? nullptr : D_f;  // fused LM diagonal: bal_invert9_kernel forms D_f from the block's own diagonal and adds it
-    HIP_TRY(s, s->ops->invert(blocks, s->d_cam_diag_off, s->plan.n_cameras, s->d_fail_flag, lm_fuse_for_cameras(s, false), g, st));
+    g.D_f = cx.rq.fuse ? nullptr : D_f;  // fused LM diagonal: bal_invert9_kernel forms D_f from the block's own diagonal and adds it
+    HIP_TRY(s, s->ops->invert(blocks, s->d_cam_diag_off, s->plan.n_cameras, s->d_fail_flag, lm_fuse_for_cameras(s, cx.rq, false), g, st));
     TRY(shared_preconditioner_blocks(s, false, blocks, true));
     return 0;
   }
@@ -1092,8 +1108,8 @@ int op_cgnr_setup_bal(ceres_hip_solver* s, bool jacobi, double* rhs, double* blo
     CamGather g;
     g.packed = s->d_cam_packed; g.cam_pos = cam_pos;
     g.cam_base = s->plan.cam_base;
-    g.D_f = s->lm_fuse_active ? nullptr : D_f;
-    HIP_TRY(s, s->ops->invert(blocks, s->d_cam_diag_off, s->plan.n_cameras, s->d_fail_flag, lm_fuse_for_cameras(s, false), g, st));
+    g.D_f = cx.rq.fuse ? nullptr : D_f;
+    HIP_TRY(s, s->ops->invert(blocks, s->d_cam_diag_off, s->plan.n_cameras, s->d_fail_flag, lm_fuse_for_cameras(s, cx.rq, false), g, st));
     return 0;
   }
   // sharded: raw F^T F sums, all-reduce, then the diagonal (camera blocks are contiguous
@@ -1108,27 +1124,27 @@ int op_cgnr_setup_bal(ceres_hip_solver* s, bool jacobi, double* rhs, double* blo
   } else {
     TRY(allreduce(s, blocks + first, size_t(len - first)));
   }
-  if (s->D && !s->lm_fuse_active)  // fused LM diagonal: bal_invert9_kernel forms D_f from the reduced diagonal and adds it
+  if (s->D && !cx.rq.fuse)  // fused LM diagonal: bal_invert9_kernel forms D_f from the reduced diagonal and adds it
     HIP_TRY(s, LaunchAddBlockDiagonalSquares(s->G, h.nelim, h.ncb - h.nelim, s->G.diag_off_all + h.nelim, s->D, blocks + first, st));
-  HIP_TRY(s, s->ops->invert(blocks, s->d_cam_diag_off, s->plan.n_cameras, s->d_fail_flag, lm_fuse_for_cameras(s, false), CamGather(), st));
+  HIP_TRY(s, s->ops->invert(blocks, s->d_cam_diag_off, s->plan.n_cameras, s->d_fail_flag, lm_fuse_for_cameras(s, cx.rq, false), CamGather(), st));
   TRY(invert_shared_blocks(s, blocks));
   return 0;
 }
 
 // ---- SCHUR_POWER_SERIES_EXPANSION ---------------------------------------
-int ensure_ftf_inverse(ceres_hip_solver* s) {
+int ensure_ftf_inverse(ceres_hip_solver* s, SolveCtx& cx) {
   if (s->ftf_inv_valid) return 0;
-  TRY(op_preconditioner(s, CERES_HIP_JACOBI, s->ftf_inv, true));
+  TRY(op_preconditioner(s, cx, CERES_HIP_JACOBI, s->ftf_inv, true));
   s->ftf_inv_valid = true;
   return 0;
 }
 
 // y += (F^T F)^-1 F^T E (E^T E)^-1 E^T F x.  InversePowerSeriesOperatorRightMultiplyAccumulate.
 // Uses spse_b as the F-space temporary.
-int op_power_series(ceres_hip_solver* s, const double* x, double* y, const int* status) {
+int op_power_series(ceres_hip_solver* s, SolveCtx& cx, const double* x, double* y, const int* status) {
   const HostStructure& h = s->hs;
   hipStream_t st = s->stream;
-  TRY(ensure_ftf_inverse(s));
+  TRY(ensure_ftf_inverse(s, cx));
   double* t = s->spse_b;
   if (s->path == CERES_HIP_PATH_BAL) {
     TRY(ensure_packed(s));
@@ -1154,11 +1170,11 @@ int op_power_series(ceres_hip_solver* s, const double* x, double* y, const int* 
 
 // y = sum_k Z^k (F^T F)^-1 x.  PowerSeriesExpansionPreconditioner::RightMultiplyAndAccumulate.
 // tolerance == 0 (the preconditioner's setting) runs a fixed number of terms with no host sync.
-int op_spse_apply(ceres_hip_solver* s, const double* x, double* y, int max_iters, double tolerance, const int* status) {
+int op_spse_apply(ceres_hip_solver* s, SolveCtx& cx, const double* x, double* y, int max_iters, double tolerance, const int* status) {
   const HostStructure& h = s->hs;
   hipStream_t st = s->stream;
   const int64_t n = h.num_cols_f;
-  TRY(ensure_ftf_inverse(s));
+  TRY(ensure_ftf_inverse(s, cx));
   HIP_TRY(s, hipMemsetAsync(y, 0, sizeof(double) * n, st));
   HIP_TRY(s, LaunchGenBlockDiagonalApply(s->G, h.nelim, h.ncb - h.nelim, s->G.diag_off_f, s->ftf_inv, x, y, status, st));
   double* prev = s->spse_a;
@@ -1176,7 +1192,7 @@ int op_spse_apply(ceres_hip_solver* s, const double* x, double* y, int max_iters
   if (tolerance > 0.0) { double ny = 0; TRY(host_norm(y, &ny)); threshold = tolerance * ny; }
   for (int i = 1;; ++i) {
     HIP_TRY(s, hipMemsetAsync(term, 0, sizeof(double) * n, st));
-    TRY(op_power_series(s, prev, term, status));
+    TRY(op_power_series(s, cx, prev, term, status));
     HIP_TRY(s, LaunchAxpby(1.0, y, 1.0, term, y, n, st));
     if (i >= max_iters) break;
     if (tolerance > 0.0) { double nt = 0; TRY(host_norm(term, &nt)); if (nt < threshold) break; }
@@ -1227,10 +1243,10 @@ int enqueue_model_cost_change(ceres_hip_solver* s, const double* x, const double
   *dev_parts = s->cg.comm;
   return 0;
 }
-// The point tail of a solve that captured (pt_tail_armed): point part, camera copy (negated and checked for an LM step) and the model
+// The point tail of a solve that captured (run_cg): point part, camera copy (negated and checked for an LM step) and the model
 // cost's partials from point-space vectors; the kernel runs only where PointTailTakes (device.h) says so.  The caller has cleared the
 // finite-step flag.
-int op_point_tail(ceres_hip_solver* s, const double* z, double* x) {
+int op_point_tail(ceres_hip_solver* s, SolveCtx& cx, const double* z, double* x) {
   const HostStructure& h = s->hs;
   PointTailArgs T;
   T.n_points = s->plan.n_points; T.n_f = h.num_cols_f;
@@ -1239,11 +1255,11 @@ int op_point_tail(ceres_hip_solver* s, const double* z, double* x) {
   T.D_e = s->D; T.D_f = s->D ? s->D + h.num_cols_e : nullptr;
   T.z = z; T.rhs = s->rhs_f; T.r = s->cg.r;
   T.y_e = x; T.y_f = x + h.num_cols_e;
-  T.negate = s->lm_negate_in_solve ? 1 : 0;
+  T.negate = cx.rq.negate_in_solve ? 1 : 0;
   T.nonfinite = s->d_nonfinite;
   T.S = s->cg.S;
-  T.cost_out = s->lm_want_model_cost ? s->scalar_partials : nullptr;
-  HIP_TRY(s, s->ops->point_tail(T, &s->pt_tail_parts, s->stream));
+  T.cost_out = cx.rq.want_model_cost ? s->scalar_partials : nullptr;
+  HIP_TRY(s, s->ops->point_tail(T, &cx.out.pt_tail_parts, s->stream));
   return 0;
 }
 
@@ -1256,11 +1272,13 @@ struct CgSpec {
   std::function<int(const double*, double*)> apply;     // y = A x (assigns)
   // optional: y = A x AND the partial sums of x . y into pq[0 .. *n_pq) (n_pq <= kMaxPqParts); *n_pq = 0 if not produced
   // sharded: *extra = device pointer to the shard's share of x . y, already summed over ranks (nullptr if not produced)
-  std::function<int(const double*, double*, double*, int*, const double**)> apply_dot;
-  std::function<int()> before_poll;                     // enqueued before every poll of the status word (speculative LM tail)
+  // u_out: where this application keeps its per-point sums for the point tail (point_tail_capture), nullptr: it keeps none
+  std::function<int(const double*, double*, double*, int*, const double**, double* u_out)> apply_dot;
+  std::function<int(int enqueued)> before_poll;         // before every poll of the status word, `enqueued` iterations in (speculative LM tail)
   // optional (small camera spaces, CgTail in device.h): q = A p AND the rest of fused iteration `it` in one launch; returns 1 if it
   // did, 0 if this launch cannot (the caller then runs the iteration the usual way), < 0 on error
-  std::function<int(int)> iteration;
+  std::function<int(int it, double* u_out)> iteration;
+  bool capture_if_fused_start = false;                  // point tail: the first kPointTailMaxIterations S.p passes keep their per-point sums
   bool shard_fused = false;                             // sharded CG vectors, and apply_dot + the block layout support the fused iteration
   std::function<int(const double*, double*)> precondition;  // z = M^-1 r as an operator (SPSE); empty = block diagonal
   bool x0_nonzero = false;                              // B.x holds an initial guess
@@ -1368,8 +1386,8 @@ int collapse_and_reduce(ceres_hip_solver* s, int first_slot, int count) {
   return allreduce(s, s->cg.comm + first_slot, size_t(count));
 }
 
-// rhs in s->cg_rhs; solution left in s->cg.x.
-int run_cg(ceres_hip_solver* s, const CgSpec& spec, double q_tol, double r_tol, ceres_hip_summary* summary) {
+// rhs in s->cg_rhs; solution left in s->cg.x.  *captured: the solve kept the per-point sums spec.capture_if_fused_start asked for.
+int run_cg(ceres_hip_solver* s, const CgSpec& spec, double q_tol, double r_tol, ceres_hip_summary* summary, bool* captured = nullptr) {
   hipStream_t st = s->stream;
   CgBuffers& B = s->cg;
   B.n = spec.n;
@@ -1429,10 +1447,9 @@ int run_cg(ceres_hip_solver* s, const CgSpec& spec, double q_tol, double r_tol, 
   s->timing.operator_applications = 0;
   int it = 1;
   // point tail: the S.p passes of the first kPointTailMaxIterations iterations keep their per-point sums (op_sx, spec.iteration) — of a
-  // solve from x = 0 on the fused iteration, whose kernels keep alpha's history; no other caller's S.x pass ever captures
-  const bool capture = s->pt_tail_armed && fused_start;
-  s->pt_tail_armed = capture;
-  struct CaptureOff { ceres_hip_solver* s; ~CaptureOff() { s->cg_capture_it = 0; } } capture_off{s};
+  // solve from x = 0 on the fused iteration, whose kernels keep alpha's history; no other S.x pass is handed a buffer
+  const bool capture = spec.capture_if_fused_start && fused_start;
+  if (captured) *captured = capture;
   auto precondition = [&]() -> int {
     if (spec.precondition) {
       TRY(spec.precondition(B.r, B.z));
@@ -1452,16 +1469,16 @@ int run_cg(ceres_hip_solver* s, const CgSpec& spec, double q_tol, double r_tol, 
     const int batch_end = std::min(max_it, it + interval - 1);
     for (; it <= batch_end; ++it) {
       const int reset = (it % reset_period == 0) ? 1 : 0;
-      s->cg_capture_it = (capture && it <= kPointTailMaxIterations) ? it : 0;
+      double* const u_out = capture ? point_tail_capture(s, it) : nullptr;
       if (fused && spec.iteration && !reset) {
-        const int done = spec.iteration(it);
+        const int done = spec.iteration(it, u_out);
         if (done < 0) return CERES_HIP_E_HIP;
         if (done > 0) { ++s->timing.operator_applications; continue; }
       }
       if (fused) {
         int n_pq = 0;
         const double* extra = nullptr;
-        if (spec.apply_dot) TRY(spec.apply_dot(B.p, B.z, s->cg_pq_parts, &n_pq, &extra));
+        if (spec.apply_dot) TRY(spec.apply_dot(B.p, B.z, s->cg_pq_parts, &n_pq, &extra, u_out));
         else TRY(spec.apply(B.p, B.z));
         B.pq_extra = extra;
         if (n_pq > 0) { B.pq_parts = s->cg_pq_parts; B.n_pq = n_pq; }
@@ -1499,9 +1516,7 @@ int run_cg(ceres_hip_solver* s, const CgSpec& spec, double q_tol, double r_tol, 
       TRY(collapse_and_reduce(s, 2, 2));
       HIP_TRY(s, LaunchCgFinalize(B, st));
     }
-    s->cg_capture_it = 0;
-    s->cg_enqueued = it - 1;
-    if (spec.before_poll) TRY(spec.before_poll());
+    if (spec.before_poll) TRY(spec.before_poll(it - 1));
     TRY(poll_scalars(s));
     if (adaptive) { interval = first_batch ? 2 : std::min(16, interval * 2); first_batch = false; }
     if (it > max_it && s->h_scalars->status == kCgRunning)
@@ -1551,23 +1566,23 @@ int cluster_jacobi_eliminate(ceres_hip_solver* s) {
   HIP_TRY(s, LaunchSchurSparseEliminate(s->G, s->cluster_pairs, s->values, ei, s->D, s->d_Cblk, st));
   return 0;
 }
-int cluster_jacobi_assemble_and_factor(ceres_hip_solver* s) {
+int cluster_jacobi_assemble_and_factor(ceres_hip_solver* s, SolveCtx& cx) {
   hipStream_t st = s->stream;
   const int64_t mat_values = s->cluster_host.mat_off.back();
   HIP_TRY(s, hipMemsetAsync(s->d_Cmat, 0, sizeof(double) * size_t(mat_values), st));
   HIP_TRY(s, LaunchClusterAssemble(s->G, s->cluster_pairs, s->cluster, s->d_Cblk, s->cluster_storage.num_values(), s->d_Cmat, st));
-  if (!s->fail_flag_clean) HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
-  s->fail_flag_clean = false;
+  if (!cx.fail_flag_clean) HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
+  cx.fail_flag_clean = false;
   HIP_TRY(s, LaunchClusterFactorSmall(s->cluster, s->d_Cmat, s->d_fail_flag, st));
   for (int k : s->cluster_large)
     HIP_TRY(s, LaunchDenseCholesky(s->d_Cmat + s->cluster_host.mat_off[k], s->cluster_host.cl_off[k + 1] - s->cluster_host.cl_off[k], s->d_fail_flag, st));
   return 0;
 }
-int op_cluster_jacobi_update(ceres_hip_solver* s, bool* failed) {
+int op_cluster_jacobi_update(ceres_hip_solver* s, SolveCtx& cx, bool* failed) {
   *failed = false;
   s->cluster_valid = false;
   TRY(cluster_jacobi_eliminate(s));
-  TRY(cluster_jacobi_assemble_and_factor(s));
+  TRY(cluster_jacobi_assemble_and_factor(s, cx));
   TRY(check_factorization(s, failed));
   s->cluster_valid = !*failed;
   return 0;
@@ -1677,27 +1692,56 @@ int rec(ceres_hip_solver* s, int i) {
   return 0;
 }
 
-// The two LinearSolver::SolveImpl bodies.  x is a device pointer (num_cols).
-int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x, ceres_hip_summary* summary);
-int solve_loaded(ceres_hip_solver* s, double q_tol, double r_tol, double* x, ceres_hip_summary* summary) {
-  int rc = solve_loaded_impl(s, q_tol, r_tol, x, summary);
+// The LinearSolver::SolveImpl bodies.  x is a device pointer (num_cols).  rq: what the caller asks of this solve (StepRequest() = a plain
+// Solve); *outcome: what it did.  The promises one phase makes a later one live in the context and end with it.
+int solve_loaded_impl(ceres_hip_solver* s, SolveCtx& cx, double q_tol, double r_tol, double* x, ceres_hip_summary* summary);
+int solve_loaded(ceres_hip_solver* s, const StepRequest& rq, double q_tol, double r_tol, double* x, ceres_hip_summary* summary,
+                 StepOutcome* outcome = nullptr) {
+  SolveCtx cx(rq);
+  int rc = solve_loaded_impl(s, cx, q_tol, r_tol, x, summary);
   // a deferred rhs all-reduce nobody took along (an early return between op_schur_init and the preconditioner): pay it now, so that
-  // every rank issues the same collectives and a later op-level call does not find a stale promise
-  if (s->rhs_reduce_pending) {
-    s->rhs_reduce_pending = false;
+  // every rank issues the same collectives
+  if (cx.rhs_reduce_pending) {
+    cx.rhs_reduce_pending = false;
     if (rc == 0) rc = allreduce(s, s->rhs_f, size_t(s->hs.num_cols_f));
   }
   // "the flags were cleared together at the start" holds INSIDE one solve only: paths that never consume the promise (DENSE_SCHUR,
-  // explicit S, IDENTITY, early returns) clear and raise d_fail_flag themselves, and a later op-level call must not skip its memset
-  s->fail_flag_clean = false;
-  s->nonfinite_clean = false;
-  if (s->clear_flags_pending) {   // no fused first pass took the clearing along: cannot happen on the paths that set it — an error, not a silent skip
-    s->clear_flags_pending = false;
+  // explicit S, IDENTITY, early returns) clear and raise d_fail_flag themselves
+  cx.fail_flag_clean = false;
+  cx.nonfinite_clean = false;
+  if (cx.clear_flags_pending) {   // no fused first pass took the clearing along: cannot happen on the paths that set it — an error, not a silent skip
+    cx.clear_flags_pending = false;
     if (rc == 0) rc = fail(s, CERES_HIP_E_INVALID, "internal: the solve's flags were never cleared (no first pass ran)");
   }
+  if (cx.out.route >= 0) s->last_backsub_route = cx.out.route;   // (ceres_hip_debug_last_backsub_route reads it there)
+  if (outcome) *outcome = cx.out;
   return rc;
 }
-int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x, ceres_hip_summary* summary) {
+
+// termination FAILURE with the reference's message; the solve itself returns 0
+int solve_failed(ceres_hip_summary* summary, const char* message) {
+  summary->termination_type = CERES_HIP_FAILURE;
+  snprintf(summary->message, sizeof(summary->message), "%s", message);
+  return 0;
+}
+// CG on the reduced system with a block-diagonal preconditioner over the F blocks (nullptr: IDENTITY)
+void f_space_block_jacobi(const ceres_hip_solver* s, const double* blocks, CgSpec* spec) {
+  const HostStructure& h = s->hs;
+  spec->n = h.num_cols_f;
+  spec->n_local = 0;  // camera space is replicated: no inner product crosses ranks
+  spec->first_block = h.nelim;
+  spec->nblocks = h.ncb - h.nelim;
+  spec->col_begin = h.num_cols_e;
+  spec->diag_off = s->G.diag_off_f;
+  spec->blocks = blocks;
+}
+int solve_dense_schur(ceres_hip_solver* s, SolveCtx& cx, double* x, ceres_hip_summary* summary);
+int solve_explicit_schur(ceres_hip_solver* s, SolveCtx& cx, double q_tol, double r_tol, double* x, ceres_hip_summary* summary);
+int solve_implicit_schur(ceres_hip_solver* s, SolveCtx& cx, double q_tol, double r_tol, double* x, ceres_hip_summary* summary);
+int solve_cgnr(ceres_hip_solver* s, SolveCtx& cx, double q_tol, double r_tol, double* x, ceres_hip_summary* summary);
+
+// What every solve starts with: the flags, ImplicitSchurComplement::Init for the Schur solvers, then the solver's own function.
+int solve_loaded_impl(ceres_hip_solver* s, SolveCtx& cx, double q_tol, double r_tol, double* x, ceres_hip_summary* summary) {
   const HostStructure& h = s->hs;
   hipStream_t st = s->stream;
   memset(summary, 0, sizeof(*summary));
@@ -1711,358 +1755,298 @@ int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x
   s->cluster_valid = false;
   // finite-step flag + factorization flag, adjacent.  Fused path: the solve's first pass clears them itself (BalArgs::clear_flags:
   // op_schur_init / op_cgnr_setup_bal, which every fused solve starts with) — no fill command in front of it
-  s->clear_flags_pending = s->path == CERES_HIP_PATH_BAL && s->ops != nullptr;
-  if (!s->clear_flags_pending) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, 2 * sizeof(int), st));
-  s->fail_flag_clean = true;
-  s->nonfinite_clean = true;
+  cx.clear_flags_pending = s->path == CERES_HIP_PATH_BAL && s->ops != nullptr;
+  if (!cx.clear_flags_pending) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, 2 * sizeof(int), st));
+  cx.fail_flag_clean = true;
+  cx.nonfinite_clean = true;
   TRY(rec(s, 2));
-  if (is_schur(s)) {
-    // IterativeSchurComplementSolver::SolveImpl, I/iterative_schur_complement_solver.cc:64-157
-    const int pre = s->opt.preconditioner_type;
-    // sharded fused path, block-diagonal preconditioner from the camera-major pass: rhs, the blocks and the camera column norms go
-    // through ONE all-reduce, issued by op_preconditioner
-    // (armed only where the code below REACHES that op_preconditioner call: the implicit iterative branch with F blocks — a direct or
-    // explicit-S solve, or the no-F-blocks shortcut, would otherwise factor / iterate on this rank's raw rhs)
-    const bool implicit_iterative = !is_dense_schur(s) && !s->sparse_S && !s->opt.use_explicit_schur_complement && h.ncb - h.nelim > 0;
-    // (round 6: not when the camera-major pass exchanges its blocks itself — a verdict all ranks share —: rhs is then summed over ranks by
-    // the first pass's own reduction, or by the stand-alone all-reduce on a rank whose reduction cannot: the same slots either way)
-    s->merge_step_reduce = s->world > 1 && s->path == CERES_HIP_PATH_BAL && (pre == CERES_HIP_SCHUR_JACOBI || pre == CERES_HIP_JACOBI) &&
-                           !s->opt.use_spse_initialization && implicit_iterative && !camera_blocks_exchange(s);
-    const int rc_init = op_schur_init(s, pre == CERES_HIP_SCHUR_JACOBI);
-    s->merge_step_reduce = false;
-    TRY(rc_init);
-    bool bad = false;
-    if (s->path != CERES_HIP_PATH_BAL) TRY(check_factorization(s, &bad));
-    if (bad) {
-      summary->termination_type = CERES_HIP_FAILURE;
-      snprintf(summary->message, sizeof(summary->message), "E^T E + D^2 is not positive definite.");
-      return 0;
-    }
-    TRY(rec(s, 3));
-    const int nf_blocks = h.ncb - h.nelim;
-    if (nf_blocks == 0) {  // :88-95
-      summary->termination_type = CERES_HIP_SUCCESS;
-      summary->num_iterations = 0;
-      TRY(op_back_substitute(s, nullptr, x));
-      TRY(rec(s, 4));
-      TRY(rec(s, 5));
-      TRY(rec(s, 6));
-      return 0;
-    }
-    if (is_dense_schur(s)) {
-      // DenseSchurComplementSolver (I/schur_complement_solver.cc:163-222): S dense by elimination, Cholesky of its upper
-      // triangle (DenseCholesky::FactorAndSolve), back-substitution on SUCCESS.
-      const int64_t nf = h.num_cols_f;
-      if (s->dense_from_blocks) {
-        const double* ei = s->etei;
-        if (s->path == CERES_HIP_PATH_BAL) {  // packed 6-per-point inverses (internal point order) -> the dense E-block store
-          HIP_TRY(s, LaunchExpandSym(s->etei, s->ops->ne, s->ops->etei_pitch, s->etei_dense, s->d_pt_eoff, s->plan.n_points, st));
-          ei = s->etei_dense;
-        }
-        HIP_TRY(s, LaunchSchurSparseEliminate(s->G, s->schur_pairs, s->values, ei, s->D, s->d_Sblk, st));
-        HIP_TRY(s, hipMemsetAsync(s->d_S, 0, sizeof(double) * size_t(nf) * size_t(nf), st));
-        HIP_TRY(s, LaunchSchurBlocksToDense(s->G, s->schur_pairs, s->d_Sblk, s->schur_storage.num_values(), s->d_S, st));
-      } else {
-        HIP_TRY(s, LaunchGenSchurDense(s->G, s->values, s->etei, (s->world > 1 && s->rank != 0) ? nullptr : s->D, s->d_S, st));
-        if (s->world > 1) TRY(allreduce(s, s->d_S, size_t(nf * nf)));
-      }
-      TRY(rec(s, 4));
-      HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
-      HIP_TRY(s, LaunchDenseCholesky(s->d_S, int(nf), s->d_fail_flag, st));
-      TRY(check_factorization(s, &bad));
-      summary->num_iterations = 1;
-      if (bad) {  // EigenDenseCholesky::Factorize, I/dense_cholesky.cc
-        summary->termination_type = CERES_HIP_FAILURE;
-        snprintf(summary->message, sizeof(summary->message), "Eigen failure. Unable to perform dense Cholesky factorization.");
-        return 0;
-      }
-      HIP_TRY(s, hipMemcpyAsync(s->cg.x, s->rhs_f, sizeof(double) * nf, hipMemcpyDeviceToDevice, st));
-      HIP_TRY(s, LaunchDenseCholeskySolve(s->d_S, int(nf), s->cg.x, st));
-      TRY(rec(s, 5));
-      summary->termination_type = CERES_HIP_SUCCESS;
-      snprintf(summary->message, sizeof(summary->message), "Success.");
-      TRY(op_back_substitute(s, s->cg.x, x));
-      TRY(rec(s, 6));
-      return 0;
-    }
-    if (s->sparse_S) {
-      // SparseSchurComplementSolver with use_explicit_schur_complement: S in BlockRandomAccessSparseMatrix storage
-      // (InitStorage's block pairs), SchurEliminator::Eliminate as a gather per stored block, SCHUR_JACOBI = inverted
-      // diagonal blocks OF S, CG with SymmetricRightMultiplyAndAccumulate, back-substitution only on SUCCESS
-      // (I/schur_complement_solver.cc:100-158, 224-290, 337-408).
-      const int64_t nf = h.num_cols_f;
-      HIP_TRY(s, LaunchSchurSparseEliminate(s->G, s->schur_pairs, s->values, s->etei, s->D, s->d_S, st));
-      HIP_TRY(s, LaunchSchurSparseDiag(s->G, s->schur_pairs, s->d_S, s->G.diag_off_f, s->precond, h.diag_off_f.back(), st));
-      HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
-      HIP_TRY(s, LaunchGenInvertBlocks(s->G, h.nelim, h.ncb - h.nelim, s->G.diag_off_f, s->precond, s->d_fail_flag, st));
-      TRY(check_factorization(s, &bad));
-      if (bad) {
-        summary->termination_type = CERES_HIP_FAILURE;
-        snprintf(summary->message, sizeof(summary->message), "Preconditioner update failed.");
-        return 0;
-      }
-      s->precond_valid = true;
-      TRY(rec(s, 4));
-      CgSpec spec;
-      spec.rhs = s->rhs_f;
-      spec.n = nf;
-      spec.n_local = 0;
-      const int* status = &s->cg.S->status;
-      spec.apply = [s, status](const double* in, double* out) -> int {
-        HIP_TRY(s, LaunchSchurSparseSymv(s->G, s->schur_pairs, s->d_S, in, out, status, 0, s->stream));
-        return 0;
-      };
-      spec.first_block = h.nelim;
-      spec.nblocks = h.ncb - h.nelim;
-      spec.col_begin = h.num_cols_e;
-      spec.diag_off = s->G.diag_off_f;
-      spec.blocks = s->precond;
-      TRY(run_cg(s, spec, q_tol, r_tol, summary));
-      TRY(rec(s, 5));
-      if (summary->termination_type == CERES_HIP_SUCCESS) {
-        TRY(op_back_substitute(s, s->cg.x, x));
-      } else {  // x was zero-filled (:135), the reduced solution sits in its tail
-        HIP_TRY(s, hipMemsetAsync(x, 0, sizeof(double) * h.num_cols_e, st));
-        HIP_TRY(s, hipMemcpyAsync(x + h.num_cols_e, s->cg.x, sizeof(double) * nf, hipMemcpyDeviceToDevice, st));
-      }
-      TRY(rec(s, 6));
-      return 0;
-    }
-    if (s->opt.use_explicit_schur_complement) {
-      // sharded runs keep S DENSE (one all-reduce of the ranks' contributions):
-      // SchurComplementSolver::SolveImpl (I/schur_complement_solver.cc:100-158) with
-      // SolveReducedLinearSystemUsingConjugateGradients (:337-408): S and rhs by elimination,
-      // SCHUR_JACOBI = inverted diagonal blocks OF S, CG on S, back-substitution only on SUCCESS.
-      const int64_t nf = h.num_cols_f;
-      // D_f^2 joins the diagonal once: on rank 0 when the elimination is sharded by point
-      HIP_TRY(s, LaunchGenSchurDense(s->G, s->values, s->etei, (s->world > 1 && s->rank != 0) ? nullptr : s->D, s->d_S, st));
-      if (s->world > 1) TRY(allreduce(s, s->d_S, size_t(nf * nf)));  // "reduced-system contributions combined via all-reduce"
-      HIP_TRY(s, LaunchGenSymmetrizeDense(s->G, s->d_S, st));
-      HIP_TRY(s, LaunchGenExtractDiagBlocks(s->G, s->d_S, s->G.diag_off_f, s->precond, st));
-      HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
-      HIP_TRY(s, LaunchGenInvertBlocks(s->G, h.nelim, h.ncb - h.nelim, s->G.diag_off_f, s->precond, s->d_fail_flag, st));
-      TRY(check_factorization(s, &bad));
-      if (bad) {
-        summary->termination_type = CERES_HIP_FAILURE;
-        snprintf(summary->message, sizeof(summary->message), "Preconditioner update failed.");
-        return 0;
-      }
-      s->precond_valid = true;
-      TRY(rec(s, 4));
-      HIP_TRY(s, hipMemcpyAsync(s->cg_rhs, s->rhs_f, sizeof(double) * nf, hipMemcpyDeviceToDevice, st));
-      CgSpec spec;
-      spec.n = nf;
-      spec.n_local = 0;
-      const int* status = &s->cg.S->status;
-      spec.apply = [s, status, nf](const double* in, double* out) -> int {
-        HIP_TRY(s, LaunchGenDenseSymv(s->d_S, int(nf), in, out, status, s->stream));
-        return 0;
-      };
-      spec.first_block = h.nelim;
-      spec.nblocks = h.ncb - h.nelim;
-      spec.col_begin = h.num_cols_e;
-      spec.diag_off = s->G.diag_off_f;
-      spec.blocks = s->precond;
-      TRY(run_cg(s, spec, q_tol, r_tol, summary));
-      TRY(rec(s, 5));
-      if (summary->termination_type == CERES_HIP_SUCCESS) {
-        TRY(op_back_substitute(s, s->cg.x, x));
-      } else {  // x was zero-filled (:135), the reduced solution sits in its tail
-        HIP_TRY(s, hipMemsetAsync(x, 0, sizeof(double) * h.num_cols_e, st));
-        HIP_TRY(s, hipMemcpyAsync(x + h.num_cols_e, s->cg.x, sizeof(double) * nf, hipMemcpyDeviceToDevice, st));
-      }
-      TRY(rec(s, 6));
-      return 0;
-    }
-    const bool spse_pre = pre == CERES_HIP_SCHUR_POWER_SERIES_EXPANSION;
-    const int spse_iters = s->opt.max_num_spse_iterations > 0 ? s->opt.max_num_spse_iterations : 5;
-    if (spse_pre || s->opt.use_spse_initialization) {
-      TRY(ensure_ftf_inverse(s));
-      TRY(check_factorization(s, &bad));
-      if (bad) {
-        summary->termination_type = CERES_HIP_FAILURE;
-        snprintf(summary->message, sizeof(summary->message), "F^T F + D^2 is not positive definite.");
-        return 0;
-      }
-    }
-    // On the fused path the factorization flag of the preconditioner blocks is not read back here
-    // (a host round trip in front of CG): the CG init kernel looks at it and starts in kCgSetupFailed.
-    const bool defer_check = s->path == CERES_HIP_PATH_BAL;
-    const bool cluster_pre = pre == CERES_HIP_CLUSTER_JACOBI;
-    if (cluster_pre) {
-      TRY(op_cluster_jacobi_update(s, &bad));
-      if (bad) {  // Preconditioner::Update returned false, :113-121
-        summary->termination_type = CERES_HIP_FAILURE;
-        snprintf(summary->message, sizeof(summary->message), "Preconditioner update failed.");
-        return 0;
-      }
-    } else if (pre != CERES_HIP_IDENTITY && !spse_pre) {
-      TRY(op_preconditioner(s, pre, s->precond, true));
-      if (!defer_check) {
-        TRY(check_factorization(s, &bad));
-        if (bad) {  // Preconditioner::Update returned false, :113-121
-          summary->termination_type = CERES_HIP_FAILURE;
-          snprintf(summary->message, sizeof(summary->message), "Preconditioner update failed.");
-          return 0;
-        }
-      }
-      s->precond_valid = true;
-    }
-    if (s->rhs_reduce_pending) {  // nobody took the deferred all-reduce along (cannot happen on the paths that set the flag; kept as a guard)
-      TRY(allreduce(s, s->rhs_f, size_t(h.num_cols_f)));
-      s->rhs_reduce_pending = false;
-    }
+  if (!is_schur(s)) return solve_cgnr(s, cx, q_tol, r_tol, x, summary);
+  // IterativeSchurComplementSolver::SolveImpl, I/iterative_schur_complement_solver.cc:64-157
+  const int pre = s->opt.preconditioner_type;
+  const bool explicit_S = s->sparse_S || s->opt.use_explicit_schur_complement;
+  // sharded fused path, block-diagonal preconditioner from the camera-major pass: rhs, the blocks and the camera column norms go
+  // through ONE all-reduce, issued by op_preconditioner
+  // (armed only where the solve REACHES that op_preconditioner call: solve_implicit_schur, with F blocks — a direct or
+  // explicit-S solve, or the no-F-blocks shortcut, would otherwise factor / iterate on this rank's raw rhs)
+  const bool implicit_iterative = !is_dense_schur(s) && !explicit_S && h.ncb - h.nelim > 0;
+  // (round 6: not when the camera-major pass exchanges its blocks itself — a verdict all ranks share —: rhs is then summed over ranks by
+  // the first pass's own reduction, or by the stand-alone all-reduce on a rank whose reduction cannot: the same slots either way)
+  const bool merge_step_reduce = s->world > 1 && s->path == CERES_HIP_PATH_BAL && (pre == CERES_HIP_SCHUR_JACOBI || pre == CERES_HIP_JACOBI) &&
+                                 !s->opt.use_spse_initialization && implicit_iterative && !camera_blocks_exchange(s);
+  TRY(op_schur_init(s, cx, pre == CERES_HIP_SCHUR_JACOBI, merge_step_reduce));
+  bool bad = false;
+  if (s->path != CERES_HIP_PATH_BAL) TRY(check_factorization(s, &bad));
+  if (bad) return solve_failed(summary, "E^T E + D^2 is not positive definite.");
+  TRY(rec(s, 3));
+  if (h.ncb - h.nelim == 0) {  // no F blocks, :88-95
+    summary->termination_type = CERES_HIP_SUCCESS;
+    summary->num_iterations = 0;
+    TRY(op_back_substitute(s, cx, nullptr, x));
     TRY(rec(s, 4));
-    CgSpec spec;
-    spec.rhs = s->rhs_f;  // CG only reads it: no copy into cg_rhs
-    spec.n = h.num_cols_f;
-    spec.n_local = 0;  // camera space is replicated: no inner product crosses ranks
-    const int* status = &s->cg.S->status;
-    spec.apply = [s, status](const double* in, double* out) { return op_sx(s, in, out, status); };
-    if (s->path == CERES_HIP_PATH_BAL)
-      spec.apply_dot = [s, status](const double* in, double* out, double* pq, int* n_pq, const double** extra) {
-        *extra = nullptr;
-        return op_sx(s, in, out, status, pq, n_pq);
-      };
-    spec.first_block = h.nelim;
-    spec.nblocks = h.ncb - h.nelim;
-    spec.col_begin = h.num_cols_e;
-    spec.diag_off = s->G.diag_off_f;
-    spec.blocks = (pre == CERES_HIP_IDENTITY || spse_pre || cluster_pre) ? nullptr : s->precond;
-    if (cg_tail_possible(s) && spec.blocks) {
-      // a camera space this small: the S.x pass finishes the CG iteration itself (one launch instead of four)
-      spec.iteration = [s, status](int it) -> int {
-        if (ensure_packed(s)) return -1;
-        BalArgs A = bal_args(s);
-        if (!s->ops->sx_runs_pipelined(A)) return 0;
-        CgBuffers& B = s->cg;
-        A.x_f = B.p;
-        A.u_out = point_tail_capture(s, B.p);
-        A.status = status;
-        A.tail.enabled = 1; A.tail.it = it; A.tail.ticket = s->d_cg_ticket;
-        A.tail.x = B.x; A.tail.r = B.r; A.tail.p = B.p; A.tail.z = B.z; A.tail.rhs = B.rhs;
-        A.tail.blocks = s->precond; A.tail.D_f = s->D ? s->D + s->hs.num_cols_e : nullptr; A.tail.S = B.S;
-        if (hipError_t e = s->ops->fused(kBalSx, A, true, s->fused_grid, s->stream); e != hipSuccess) {
-          fail(s, CERES_HIP_E_HIP, "S.x + CG iteration launch: %s", hipGetErrorString(e));
-          return -1;
-        }
-        return 1;
-      };
-    }
-    if (defer_check && spec.blocks) spec.setup_fail = s->d_fail_flag;
-    if (spse_pre)  // tolerance 0: the preconditioner must stay fixed during CG (:178-186)
-      spec.precondition = [s, spse_iters, status](const double* in, double* out) { return op_spse_apply(s, in, out, spse_iters, 0.0, status); };
-    if (cluster_pre)   // not block diagonal over the F blocks: CG takes it as an operator (the five-kernel iteration, no one-launch tail)
-      spec.precondition = [s, status](const double* in, double* out) { return op_cluster_jacobi_apply(s, in, out, status); };
-    if (s->opt.use_spse_initialization) {  // :97-111
-      TRY(op_spse_apply(s, s->rhs_f, s->cg.x, spse_iters, s->opt.spse_tolerance, nullptr));
-      spec.x0_nonzero = true;
-    }
-    s->spec_tail_done = false;
-    // point tail: this solve captures if the handle is eligible, CG starts from x = 0 and runs the fused iteration (run_cg has the last word)
-    s->pt_tail_armed = s->point_tail_eligible && s->have_b && !spec.x0_nonzero && !spec.precondition && h.num_cols_f > 0;
-    s->pt_tail_enqueued = s->backsub_enqueued = false;
-    s->last_backsub_route = 0;
-    if (s->lm_speculate && s->path == CERES_HIP_PATH_BAL && h.num_cols_f > 0) {
-      spec.before_poll = [s, x]() {
-        // The point tail and the pass over J carry complementary gates (PointTailTakes): the device runs one of them, by the solve's
-        // own outcome.  The pass over J is left out only while the iterations enqueued cannot go past the tail's reach.
-        int rc = 0;
-        s->pt_tail_enqueued = s->pt_tail_armed;
-        s->backsub_enqueued = !s->pt_tail_armed || s->cg_enqueued > kPointTailMaxIterations;
-        if (s->pt_tail_enqueued) {
-          if (s->lm_negate_in_solve) {   // (one clear for the two launches; op_back_substitute then skips its own)
-            if (!s->nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), s->stream));
-            s->nonfinite_clean = s->backsub_enqueued;
-            s->lm_negated = true;
-          }
-          rc = op_point_tail(s, s->cg.x, x);
-          if (rc) return rc;
-        }
-        if (s->backsub_enqueued) {
-          s->gate_on_cg_status = true;
-          s->backsub_skips_for_tail = s->pt_tail_enqueued;
-          rc = op_back_substitute(s, s->cg.x, x);
-          s->gate_on_cg_status = false;
-          s->backsub_skips_for_tail = false;
-        }
-        if (rc) return rc;
-        // sharded: {finite-step flag, this rank's share of the model cost} summed over ranks into the read-back image, in the same tail
-        // (the exchange runs whether CG has ended or not — a handshake per epoch on every rank, p2p.h; its sums only mean something once it has)
-        if (s->world > 1) {
-          if (s->mailbox && s->d_h_pinned) {   // ... and the poll's read-back (the whole image, stamped): one launch for the two
-            s->tail_mailbox_seq = ++s->mailbox_seq;
-            HIP_TRY(s, LaunchCollectScalarsExchange(s->d_nonfinite, s->scalar_partials, s->backsub_cost_parts, s->scalar_partials + kSumsOffset,
-                                                    next_exchange(s), s->stream, s->scalar_partials, kReadbackDoubles, s->d_h_pinned, s->d_stamp,
-                                                    s->tail_mailbox_seq));
-          } else {
-            HIP_TRY(s, LaunchCollectScalarsExchange(s->d_nonfinite, s->scalar_partials, s->backsub_cost_parts, s->scalar_partials + kSumsOffset,
-                                                    next_exchange(s), s->stream));
-          }
-        }
-        s->spec_tail_done = true;   // (the poll that follows copies the partial sums and flags together with the CG scalars)
-        return 0;
-      };
-    }
-    const int rc_cg = run_cg(s, spec, q_tol, r_tol, summary);
-    const bool armed = s->pt_tail_armed;
-    s->pt_tail_armed = false;
-    TRY(rc_cg);
     TRY(rec(s, 5));
-    const bool usable = summary->termination_type != CERES_HIP_FAILURE && summary->termination_type != CERES_HIP_FATAL_ERROR;
-    // what the device decided, or what the host now decides, by the same rule: the solve's own status and update count
-    const bool tail_takes = armed && PointTailTakes(s->h_scalars->status, s->h_scalars->n_updates);
-    if (s->spec_tail_done) {
-      if (s->pt_tail_enqueued && tail_takes) {
-        s->last_backsub_route = 1;
-        s->backsub_cost_parts = s->pt_tail_parts;
-      } else if (!s->backsub_enqueued && usable) {
-        // CG ended inside the tail's reach in a state the tail does not take (a zero right-hand side, an indefinite matrix): nothing
-        // ran behind the poll — back-substitute now, ungated
-        s->spec_tail_done = false;
-        TRY(op_back_substitute(s, s->cg.x, x));
-      }
-    } else if (usable) {
-      if (tail_takes) {
-        if (s->lm_negate_in_solve) {
-          if (!s->nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), s->stream));
-          s->nonfinite_clean = false;
-          s->lm_negated = true;
-        }
-        TRY(op_point_tail(s, s->cg.x, x));
-        s->last_backsub_route = 1;
-        s->backsub_cost_parts = s->pt_tail_parts;
-      } else {
-        TRY(op_back_substitute(s, s->cg.x, x));
-      }
-    }
     TRY(rec(s, 6));
     return 0;
   }
-  // CgnrSolver::SolveImpl, I/cgnr_solver.cc:146-207
+  if (is_dense_schur(s)) return solve_dense_schur(s, cx, x, summary);
+  if (explicit_S) return solve_explicit_schur(s, cx, q_tol, r_tol, x, summary);
+  return solve_implicit_schur(s, cx, q_tol, r_tol, x, summary);
+}
+
+// DenseSchurComplementSolver (I/schur_complement_solver.cc:163-222): S dense by elimination, Cholesky of its upper
+// triangle (DenseCholesky::FactorAndSolve), back-substitution on SUCCESS.
+int solve_dense_schur(ceres_hip_solver* s, SolveCtx& cx, double* x, ceres_hip_summary* summary) {
+  const HostStructure& h = s->hs;
+  hipStream_t st = s->stream;
+  const int64_t nf = h.num_cols_f;
+  bool bad = false;
+  if (s->dense_from_blocks) {
+    const double* ei = s->etei;
+    if (s->path == CERES_HIP_PATH_BAL) {  // packed 6-per-point inverses (internal point order) -> the dense E-block store
+      HIP_TRY(s, LaunchExpandSym(s->etei, s->ops->ne, s->ops->etei_pitch, s->etei_dense, s->d_pt_eoff, s->plan.n_points, st));
+      ei = s->etei_dense;
+    }
+    HIP_TRY(s, LaunchSchurSparseEliminate(s->G, s->schur_pairs, s->values, ei, s->D, s->d_Sblk, st));
+    HIP_TRY(s, hipMemsetAsync(s->d_S, 0, sizeof(double) * size_t(nf) * size_t(nf), st));
+    HIP_TRY(s, LaunchSchurBlocksToDense(s->G, s->schur_pairs, s->d_Sblk, s->schur_storage.num_values(), s->d_S, st));
+  } else {
+    HIP_TRY(s, LaunchGenSchurDense(s->G, s->values, s->etei, (s->world > 1 && s->rank != 0) ? nullptr : s->D, s->d_S, st));
+    if (s->world > 1) TRY(allreduce(s, s->d_S, size_t(nf * nf)));
+  }
+  TRY(rec(s, 4));
+  HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
+  HIP_TRY(s, LaunchDenseCholesky(s->d_S, int(nf), s->d_fail_flag, st));
+  TRY(check_factorization(s, &bad));
+  summary->num_iterations = 1;
+  // EigenDenseCholesky::Factorize, I/dense_cholesky.cc
+  if (bad) return solve_failed(summary, "Eigen failure. Unable to perform dense Cholesky factorization.");
+  HIP_TRY(s, hipMemcpyAsync(s->cg.x, s->rhs_f, sizeof(double) * nf, hipMemcpyDeviceToDevice, st));
+  HIP_TRY(s, LaunchDenseCholeskySolve(s->d_S, int(nf), s->cg.x, st));
+  TRY(rec(s, 5));
+  summary->termination_type = CERES_HIP_SUCCESS;
+  snprintf(summary->message, sizeof(summary->message), "Success.");
+  TRY(op_back_substitute(s, cx, s->cg.x, x));
+  TRY(rec(s, 6));
+  return 0;
+}
+
+// use_explicit_schur_complement: SchurComplementSolver::SolveImpl (I/schur_complement_solver.cc:100-158) with
+// SolveReducedLinearSystemUsingConjugateGradients (:337-408): S and rhs by elimination, SCHUR_JACOBI = inverted diagonal blocks
+// OF S, CG on S, back-substitution only on SUCCESS.  The two storages differ in how S and its diagonal blocks are formed and in the symv.
+int solve_explicit_schur(ceres_hip_solver* s, SolveCtx& cx, double q_tol, double r_tol, double* x, ceres_hip_summary* summary) {
+  const HostStructure& h = s->hs;
+  hipStream_t st = s->stream;
+  const int64_t nf = h.num_cols_f;
+  if (s->sparse_S) {
+    // SparseSchurComplementSolver (one rank): S in BlockRandomAccessSparseMatrix storage (InitStorage's block pairs),
+    // SchurEliminator::Eliminate as a gather per stored block, CG with SymmetricRightMultiplyAndAccumulate (:224-290)
+    HIP_TRY(s, LaunchSchurSparseEliminate(s->G, s->schur_pairs, s->values, s->etei, s->D, s->d_S, st));
+    HIP_TRY(s, LaunchSchurSparseDiag(s->G, s->schur_pairs, s->d_S, s->G.diag_off_f, s->precond, h.diag_off_f.back(), st));
+  } else {
+    // sharded runs keep S DENSE (one all-reduce of the ranks' contributions)
+    // D_f^2 joins the diagonal once: on rank 0 when the elimination is sharded by point
+    HIP_TRY(s, LaunchGenSchurDense(s->G, s->values, s->etei, (s->world > 1 && s->rank != 0) ? nullptr : s->D, s->d_S, st));
+    if (s->world > 1) TRY(allreduce(s, s->d_S, size_t(nf * nf)));  // "reduced-system contributions combined via all-reduce"
+    HIP_TRY(s, LaunchGenSymmetrizeDense(s->G, s->d_S, st));
+    HIP_TRY(s, LaunchGenExtractDiagBlocks(s->G, s->d_S, s->G.diag_off_f, s->precond, st));
+  }
+  HIP_TRY(s, hipMemsetAsync(s->d_fail_flag, 0, sizeof(int), st));
+  HIP_TRY(s, LaunchGenInvertBlocks(s->G, h.nelim, h.ncb - h.nelim, s->G.diag_off_f, s->precond, s->d_fail_flag, st));
+  bool bad = false;
+  TRY(check_factorization(s, &bad));
+  if (bad) return solve_failed(summary, "Preconditioner update failed.");
+  s->precond_valid = true;
+  TRY(rec(s, 4));
+  CgSpec spec;
+  f_space_block_jacobi(s, s->precond, &spec);
+  const int* status = &s->cg.S->status;
+  if (s->sparse_S) {
+    spec.rhs = s->rhs_f;
+    spec.apply = [s, status](const double* in, double* out) -> int {
+      HIP_TRY(s, LaunchSchurSparseSymv(s->G, s->schur_pairs, s->d_S, in, out, status, 0, s->stream));
+      return 0;
+    };
+  } else {
+    HIP_TRY(s, hipMemcpyAsync(s->cg_rhs, s->rhs_f, sizeof(double) * nf, hipMemcpyDeviceToDevice, st));
+    spec.apply = [s, status, nf](const double* in, double* out) -> int {
+      HIP_TRY(s, LaunchGenDenseSymv(s->d_S, int(nf), in, out, status, s->stream));
+      return 0;
+    };
+  }
+  TRY(run_cg(s, spec, q_tol, r_tol, summary));
+  TRY(rec(s, 5));
+  if (summary->termination_type == CERES_HIP_SUCCESS) {
+    TRY(op_back_substitute(s, cx, s->cg.x, x));
+  } else {  // x was zero-filled (:135), the reduced solution sits in its tail
+    HIP_TRY(s, hipMemsetAsync(x, 0, sizeof(double) * h.num_cols_e, st));
+    HIP_TRY(s, hipMemcpyAsync(x + h.num_cols_e, s->cg.x, sizeof(double) * nf, hipMemcpyDeviceToDevice, st));
+  }
+  TRY(rec(s, 6));
+  return 0;
+}
+
+// ImplicitSchurComplement + CG (I/iterative_schur_complement_solver.cc:97-157), after Init
+int solve_implicit_schur(ceres_hip_solver* s, SolveCtx& cx, double q_tol, double r_tol, double* x, ceres_hip_summary* summary) {
+  const HostStructure& h = s->hs;
+  const int pre = s->opt.preconditioner_type;
+  bool bad = false;
+  const bool spse_pre = pre == CERES_HIP_SCHUR_POWER_SERIES_EXPANSION;
+  const int spse_iters = s->opt.max_num_spse_iterations > 0 ? s->opt.max_num_spse_iterations : 5;
+  if (spse_pre || s->opt.use_spse_initialization) {
+    TRY(ensure_ftf_inverse(s, cx));
+    TRY(check_factorization(s, &bad));
+    if (bad) return solve_failed(summary, "F^T F + D^2 is not positive definite.");
+  }
+  // On the fused path the factorization flag of the preconditioner blocks is not read back here
+  // (a host round trip in front of CG): the CG init kernel looks at it and starts in kCgSetupFailed.
+  const bool defer_check = s->path == CERES_HIP_PATH_BAL;
+  const bool cluster_pre = pre == CERES_HIP_CLUSTER_JACOBI;
+  if (cluster_pre) {
+    TRY(op_cluster_jacobi_update(s, cx, &bad));
+    if (bad) return solve_failed(summary, "Preconditioner update failed.");  // Preconditioner::Update returned false, :113-121
+  } else if (pre != CERES_HIP_IDENTITY && !spse_pre) {
+    TRY(op_preconditioner(s, cx, pre, s->precond, true));
+    if (!defer_check) {
+      TRY(check_factorization(s, &bad));
+      if (bad) return solve_failed(summary, "Preconditioner update failed.");  // Preconditioner::Update returned false, :113-121
+    }
+    s->precond_valid = true;
+  }
+  if (cx.rhs_reduce_pending) {  // nobody took the deferred all-reduce along (cannot happen on the paths that set the flag; kept as a guard)
+    TRY(allreduce(s, s->rhs_f, size_t(h.num_cols_f)));
+    cx.rhs_reduce_pending = false;
+  }
+  TRY(rec(s, 4));
+  CgSpec spec;
+  f_space_block_jacobi(s, (pre == CERES_HIP_IDENTITY || spse_pre || cluster_pre) ? nullptr : s->precond, &spec);
+  spec.rhs = s->rhs_f;  // CG only reads it: no copy into cg_rhs
+  const int* status = &s->cg.S->status;
+  spec.apply = [s, status](const double* in, double* out) { return op_sx(s, in, out, status); };
+  if (s->path == CERES_HIP_PATH_BAL)
+    spec.apply_dot = [s, status](const double* in, double* out, double* pq, int* n_pq, const double** extra, double* u_out) {
+      *extra = nullptr;
+      return op_sx(s, in, out, status, pq, n_pq, u_out);
+    };
+  if (cg_tail_possible(s) && spec.blocks) {
+    // a camera space this small: the S.x pass finishes the CG iteration itself (one launch instead of four)
+    spec.iteration = [s, status](int it, double* u_out) -> int {
+      if (ensure_packed(s)) return -1;
+      BalArgs A = bal_args(s);
+      if (!s->ops->sx_runs_pipelined(A)) return 0;
+      CgBuffers& B = s->cg;
+      A.x_f = B.p;
+      A.u_out = u_out;
+      A.status = status;
+      A.tail.enabled = 1; A.tail.it = it; A.tail.ticket = s->d_cg_ticket;
+      A.tail.x = B.x; A.tail.r = B.r; A.tail.p = B.p; A.tail.z = B.z; A.tail.rhs = B.rhs;
+      A.tail.blocks = s->precond; A.tail.D_f = s->D ? s->D + s->hs.num_cols_e : nullptr; A.tail.S = B.S;
+      if (hipError_t e = s->ops->fused(kBalSx, A, true, s->fused_grid, s->stream); e != hipSuccess) {
+        fail(s, CERES_HIP_E_HIP, "S.x + CG iteration launch: %s", hipGetErrorString(e));
+        return -1;
+      }
+      return 1;
+    };
+  }
+  if (defer_check && spec.blocks) spec.setup_fail = s->d_fail_flag;
+  if (spse_pre)  // tolerance 0: the preconditioner must stay fixed during CG (:178-186)
+    spec.precondition = [s, &cx, spse_iters, status](const double* in, double* out) { return op_spse_apply(s, cx, in, out, spse_iters, 0.0, status); };
+  if (cluster_pre)   // not block diagonal over the F blocks: CG takes it as an operator (the five-kernel iteration, no one-launch tail)
+    spec.precondition = [s, status](const double* in, double* out) { return op_cluster_jacobi_apply(s, in, out, status); };
+  if (s->opt.use_spse_initialization) {  // :97-111
+    TRY(op_spse_apply(s, cx, s->rhs_f, s->cg.x, spse_iters, s->opt.spse_tolerance, nullptr));
+    spec.x0_nonzero = true;
+  }
+  // point tail: this solve captures if the handle is eligible, CG starts from x = 0 and runs the fused iteration (run_cg has the last word)
+  spec.capture_if_fused_start = s->point_tail_eligible && s->have_b && !spec.x0_nonzero && !spec.precondition && h.num_cols_f > 0;
+  const StepRequest& rq = cx.rq;
+  StepOutcome& out = cx.out;
+  out.route = 0;
+  bool captured = false;   // run_cg's word, there before the first poll
+  // The speculative tail, in front of every poll of the status word (a named lambda handed over by reference: nothing is copied).
+  auto enqueue_tail = [&](int enqueued) -> int {
+    // The point tail and the pass over J carry complementary gates (PointTailTakes): the device runs one of them, by the solve's
+    // own outcome.  The pass over J is left out only while the iterations enqueued cannot go past the tail's reach.
+    out.pt_tail_enqueued = captured;
+    out.backsub_enqueued = !captured || enqueued > kPointTailMaxIterations;
+    if (out.pt_tail_enqueued) {
+      if (rq.negate_in_solve) {   // (one clear for the two launches; op_back_substitute then skips its own)
+        if (!cx.nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), s->stream));
+        cx.nonfinite_clean = out.backsub_enqueued;
+        out.negated = true;
+      }
+      TRY(op_point_tail(s, cx, s->cg.x, x));
+    }
+    if (out.backsub_enqueued)
+      TRY(op_back_substitute(s, cx, s->cg.x, x, out.pt_tail_enqueued ? BacksubGate::kOnCgStatusBehindTail : BacksubGate::kOnCgStatus));
+    // sharded: {finite-step flag, this rank's share of the model cost} summed over ranks into the read-back image, in the same tail
+    // (the exchange runs whether CG has ended or not — a handshake per epoch on every rank, p2p.h; its sums only mean something once it has)
+    if (s->world > 1) {
+      if (s->mailbox && s->d_h_pinned) {   // ... and the poll's read-back (the whole image, stamped): one launch for the two
+        s->tail_mailbox_seq = ++s->mailbox_seq;
+        HIP_TRY(s, LaunchCollectScalarsExchange(s->d_nonfinite, s->scalar_partials, out.backsub_cost_parts, s->scalar_partials + kSumsOffset,
+                                                next_exchange(s), s->stream, s->scalar_partials, kReadbackDoubles, s->d_h_pinned, s->d_stamp,
+                                                s->tail_mailbox_seq));
+      } else {
+        HIP_TRY(s, LaunchCollectScalarsExchange(s->d_nonfinite, s->scalar_partials, out.backsub_cost_parts, s->scalar_partials + kSumsOffset,
+                                                next_exchange(s), s->stream));
+      }
+    }
+    out.spec_tail_done = true;   // (the poll that follows copies the partial sums and flags together with the CG scalars)
+    return 0;
+  };
+  if (rq.speculate && s->path == CERES_HIP_PATH_BAL && h.num_cols_f > 0) spec.before_poll = std::ref(enqueue_tail);
+  TRY(run_cg(s, spec, q_tol, r_tol, summary, &captured));
+  TRY(rec(s, 5));
+  const bool usable = summary->termination_type != CERES_HIP_FAILURE && summary->termination_type != CERES_HIP_FATAL_ERROR;
+  // what the device decided, or what the host now decides, by the same rule: the solve's own status and update count
+  const bool tail_takes = captured && PointTailTakes(s->h_scalars->status, s->h_scalars->n_updates);
+  if (out.spec_tail_done) {
+    if (out.pt_tail_enqueued && tail_takes) {
+      out.route = 1;
+      out.backsub_cost_parts = out.pt_tail_parts;
+    } else if (!out.backsub_enqueued && usable) {
+      // CG ended inside the tail's reach in a state the tail does not take (a zero right-hand side, an indefinite matrix): nothing
+      // ran behind the poll — back-substitute now, ungated
+      out.spec_tail_done = false;
+      TRY(op_back_substitute(s, cx, s->cg.x, x));
+    }
+  } else if (usable) {
+    if (tail_takes) {
+      if (rq.negate_in_solve) {
+        if (!cx.nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), s->stream));
+        cx.nonfinite_clean = false;
+        out.negated = true;
+      }
+      TRY(op_point_tail(s, cx, s->cg.x, x));
+      out.route = 1;
+      out.backsub_cost_parts = out.pt_tail_parts;
+    } else {
+      TRY(op_back_substitute(s, cx, s->cg.x, x));
+    }
+  }
+  TRY(rec(s, 6));
+  return 0;
+}
+
+// CgnrSolver::SolveImpl, I/cgnr_solver.cc:146-207
+int solve_cgnr(ceres_hip_solver* s, SolveCtx& cx, double q_tol, double r_tol, double* x, ceres_hip_summary* summary) {
+  const HostStructure& h = s->hs;
   const int pre = s->opt.preconditioner_type;
   TRY(rec(s, 3));
   if (s->path == CERES_HIP_PATH_BAL) {
-    s->merge_step_reduce = s->world > 1 && !camera_blocks_exchange(s);   // (a choice every rank makes alike: the verdict was agreed on)
     s->D_int_valid = false;
-    const int rc_setup = op_cgnr_setup_bal(s, pre == CERES_HIP_JACOBI, s->cg_rhs, s->precond);
-    s->merge_step_reduce = false;
-    TRY(rc_setup);
+    // (sharded: the deferred all-reduce is a choice every rank makes alike: the verdict was agreed on)
+    TRY(op_cgnr_setup_bal(s, cx, pre == CERES_HIP_JACOBI, s->cg_rhs, s->precond, s->world > 1 && !camera_blocks_exchange(s)));
     TRY(ensure_D_int(s));  // (IDENTITY: the set-up kernel forms no point blocks and leaves D where it is)
   } else {
-    if (pre == CERES_HIP_JACOBI) TRY(op_preconditioner(s, pre, s->precond, true));
+    if (pre == CERES_HIP_JACOBI) TRY(op_preconditioner(s, cx, pre, s->precond, true));
     TRY(op_jtb(s, s->cg_rhs));
   }
-  const bool defer_check = s->path == CERES_HIP_PATH_BAL;  // see the ITERATIVE_SCHUR branch
+  const bool defer_check = s->path == CERES_HIP_PATH_BAL;  // see solve_implicit_schur
   if (pre == CERES_HIP_JACOBI) {
     if (!defer_check) {
       bool bad = false;
       TRY(check_factorization(s, &bad));
-      if (bad) {
-        summary->termination_type = CERES_HIP_FAILURE;
-        snprintf(summary->message, sizeof(summary->message), "Preconditioner update failed.");
-        return 0;
-      }
+      if (bad) return solve_failed(summary, "Preconditioner update failed.");
     }
     s->precond_valid = true;
   }
@@ -2073,7 +2057,7 @@ int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x
   const int* status = &s->cg.S->status;
   spec.apply = [s, status](const double* in, double* out) { return op_jtjx(s, in, out, status, nullptr, nullptr, nullptr, true); };
   if (s->path == CERES_HIP_PATH_BAL) {
-    spec.apply_dot = [s, status](const double* in, double* out, double* pq, int* n_pq, const double** extra) {
+    spec.apply_dot = [s, status](const double* in, double* out, double* pq, int* n_pq, const double** extra, double*) {
       return op_jtjx(s, in, out, status, pq, n_pq, extra, true);
     };
     // sharded: the fused iteration needs the shard to be exactly the blocks in front of the 9-wide camera blocks (it is, on this
@@ -2087,22 +2071,20 @@ int solve_loaded_impl(ceres_hip_solver* s, double q_tol, double r_tol, double* x
   spec.diag_off = s->G.diag_off_all;
   spec.blocks = pre == CERES_HIP_JACOBI ? s->precond : nullptr;
   if (defer_check && spec.blocks) spec.setup_fail = s->d_fail_flag;
-  s->spec_tail_done = false;
-  if (s->lm_speculate && s->lm_negate_in_solve && s->path == CERES_HIP_PATH_BAL) {
-    spec.before_poll = [s, x]() {
-      const HostStructure& hh = s->hs;
-      if (!s->nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), s->stream));
-      s->nonfinite_clean = false;
-      HIP_TRY(s, LaunchCgnrModelCost(s->cg.x, s->cg_rhs, s->cg.r, s->D, 0, hh.num_cols, s->scalar_partials, &s->spec_cgnr_parts, s->stream,
-                                     x, s->d_nonfinite, &s->cg.S->status, point_perm(s)));
-      s->spec_tail_done = true;   // (the poll that follows copies the partial sums and flags together with the CG scalars)
-      return 0;
-    };
-  }
+  // The speculative tail: the model-cost kernel, gated on the status word, in front of every poll.
+  auto enqueue_tail = [&](int) -> int {
+    if (!cx.nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), s->stream));
+    cx.nonfinite_clean = false;
+    HIP_TRY(s, LaunchCgnrModelCost(s->cg.x, s->cg_rhs, s->cg.r, s->D, 0, h.num_cols, s->scalar_partials, &cx.out.spec_cgnr_parts, s->stream,
+                                   x, s->d_nonfinite, &s->cg.S->status, point_perm(s)));
+    cx.out.spec_tail_done = true;   // (the poll that follows copies the partial sums and flags together with the CG scalars)
+    return 0;
+  };
+  if (cx.rq.speculate && cx.rq.negate_in_solve && s->path == CERES_HIP_PATH_BAL) spec.before_poll = std::ref(enqueue_tail);
   TRY(run_cg(s, spec, q_tol, r_tol, summary));
   TRY(rec(s, 5));
   // LM step: the model-cost kernel reads the solution anyway and writes the negated step (no copy-out, no separate negation pass)
-  if (s->lm_negate_in_solve) s->lm_cgnr_copy_pending = true;
+  if (cx.rq.negate_in_solve) cx.out.cgnr_copy_pending = true;
   else TRY(copy_out_cgnr_solution(s, x));
   TRY(rec(s, 6));
   return 0;
@@ -2786,7 +2768,7 @@ int ceres_hip_solve(ceres_hip_solver* s, const double* hv, const double* hb, con
   (void)rec(s, 1);
   int rc = load_device(s, s->own_values, s->own_b, hD ? s->own_D : nullptr);
   if (rc) return fatal(rc);
-  rc = solve_loaded(s, q_tol, r_tol, s->own_x, summary);
+  rc = solve_loaded(s, StepRequest(), q_tol, r_tol, s->own_x, summary);
   if (rc) return fatal(rc);
   if (summary->termination_type != CERES_HIP_FAILURE && summary->termination_type != CERES_HIP_FATAL_ERROR) {
     if (hipMemcpyAsync(hx, s->own_x, sizeof(double) * h.num_cols, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
@@ -2817,7 +2799,7 @@ int ceres_hip_solve_unchanged_values(ceres_hip_solver* s, const double* hD, doub
   s->D = hD ? s->own_D : nullptr;
   s->have_D = hD != nullptr;
   keep_loaded_values(s);
-  int rc = solve_loaded(s, q_tol, r_tol, s->own_x, summary);
+  int rc = solve_loaded(s, StepRequest(), q_tol, r_tol, s->own_x, summary);
   if (rc) return fatal(rc);
   if (summary->termination_type != CERES_HIP_FAILURE && summary->termination_type != CERES_HIP_FATAL_ERROR) {
     if (hipMemcpyAsync(hx, s->own_x, sizeof(double) * h.num_cols, hipMemcpyDeviceToHost, s->stream) != hipSuccess)
@@ -2843,7 +2825,7 @@ int ceres_hip_solve_device(ceres_hip_solver* s, const double* dv, const double* 
   (void)rec(s, 1);
   int rc = load_device(s, dv, db, dD);
   if (rc) return fatal(rc);
-  rc = solve_loaded(s, q_tol, r_tol, dx, summary);
+  rc = solve_loaded(s, StepRequest(), q_tol, r_tol, dx, summary);
   if (rc) return fatal(rc);
   (void)rec(s, 7);
   if (hipStreamSynchronize(s->stream) != hipSuccess) return fatal(fail(s, CERES_HIP_E_HIP, "stream synchronisation failed: %s", hipGetErrorString(hipGetLastError())));
@@ -2852,7 +2834,8 @@ int ceres_hip_solve_device(ceres_hip_solver* s, const double* dv, const double* 
 }
 
 namespace {
-int lm_step_loaded(ceres_hip_solver* s, const ceres_hip_lm_options* o, double* dx, ceres_hip_lm_result* res) {
+// no_model_cost: Schur solvers form no model cost change (the dogleg strategy gets every step's from its own Gram pass)
+int lm_step_loaded(ceres_hip_solver* s, const ceres_hip_lm_options* o, double* dx, ceres_hip_lm_result* res, bool no_model_cost = false) {
   const HostStructure& h = s->hs;
   hipStream_t st = s->stream;
   memset(res, 0, sizeof(*res));
@@ -2866,36 +2849,28 @@ int lm_step_loaded(ceres_hip_solver* s, const ceres_hip_lm_options* o, double* d
   const bool fresh = !o->reuse_diagonal || !s->have_lm_diag;
   // (DENSE_SCHUR forms no preconditioner blocks: nobody would form the camera part of a fused diagonal)
   // (a shared strip's column norms are not formed by the set-up kernels: such shapes take the separate column-norm pass)
-  s->lm_fuse_active = fresh && s->path == CERES_HIP_PATH_BAL && s->opt.preconditioner_type != CERES_HIP_IDENTITY && !is_dense_schur(s) && s->plan.ns == 0 &&
-                      !is_cluster_jacobi(s);   // (the cluster factor is formed by the gather elimination, which reads a finished D)
-  s->lm_opts = *o;
-  if (fresh && !s->lm_fuse_active) TRY(op_squared_column_norm(s, s->lm_diag));
-  if (!s->lm_fuse_active)
+  const bool fuse = fresh && s->path == CERES_HIP_PATH_BAL && s->opt.preconditioner_type != CERES_HIP_IDENTITY && !is_dense_schur(s) && s->plan.ns == 0 &&
+                    !is_cluster_jacobi(s);   // (the cluster factor is formed by the gather elimination, which reads a finished D)
+  StepRequest rq;
+  if (fuse) rq.fuse = o;
+  if (fresh && !fuse) TRY(op_squared_column_norm(s, s->lm_diag));
+  if (!fuse)
     HIP_TRY(s, LaunchLmDiagonal(s->lm_diag, o->min_diagonal, o->max_diagonal, o->radius, s->lm_D, h.num_cols, st));
   s->have_lm_diag = true;
   s->D = s->lm_D;
   s->have_D = true;
-  s->lm_want_model_cost = !s->lm_skip_model_cost && is_schur(s) && s->path == CERES_HIP_PATH_BAL && s->fused_grid < 2 * kMaxVecGrid;  // (< : room for the remainder rows' partial)
-  s->backsub_cost_parts = 0;
+  rq.skip_model_cost = no_model_cost;
+  rq.want_model_cost = !no_model_cost && is_schur(s) && s->path == CERES_HIP_PATH_BAL && s->fused_grid < 2 * kMaxVecGrid;  // (< : room for the remainder rows' partial)
   // fused <2,3,9> path, implicit solvers: negation + finite check ride in the last kernel that touches the solution
-  s->lm_negate_in_solve = s->path == CERES_HIP_PATH_BAL && !s->opt.use_explicit_schur_complement && !is_dense_schur(s);
-  s->lm_negated = false;
-  s->lm_cgnr_copy_pending = false;
+  rq.negate_in_solve = s->path == CERES_HIP_PATH_BAL && !s->opt.use_explicit_schur_complement && !is_dense_schur(s);
   // (rows outside the tiles add ungated generic launches to the ITERATIVE_SCHUR tail: no speculation then)
   // (sharded: ITERATIVE_SCHUR where every rank can — the tail then holds one exchange per poll, which all ranks must issue alike)
-  s->lm_speculate = s->speculate && s->lm_negate_in_solve && !is_cluster_jacobi(s) &&
-                    (s->world <= 1 ? (!is_schur(s) || (s->lm_want_model_cost && !has_remainder(s))) : (is_schur(s) && s->spec_agreed && s->p2p && s->lm_want_model_cost));
-  s->spec_tail_done = false;
-  const int rc = solve_loaded(s, o->eta, -1.0, dx, &res->linear_solver);
-  const bool spec_done = s->spec_tail_done;
-  s->spec_tail_done = false;
-  s->lm_speculate = false;
-  s->lm_fuse_active = false;
-  s->lm_want_model_cost = false;
-  s->lm_negate_in_solve = false;
-  const bool cgnr_deferred = s->lm_cgnr_copy_pending;
-  s->lm_cgnr_copy_pending = false;
-  if (rc) return rc;
+  rq.speculate = s->speculate && rq.negate_in_solve && !is_cluster_jacobi(s) &&
+                 (s->world <= 1 ? (!is_schur(s) || (rq.want_model_cost && !has_remainder(s))) : (is_schur(s) && s->spec_agreed && s->p2p && rq.want_model_cost));
+  StepOutcome out;
+  TRY(solve_loaded(s, rq, o->eta, -1.0, dx, &res->linear_solver, &out));
+  const bool spec_done = out.spec_tail_done;
+  const bool cgnr_deferred = out.cgnr_copy_pending;
   res->step_is_finite = 0;
   const int term = res->linear_solver.termination_type;
   if (term == CERES_HIP_FAILURE || term == CERES_HIP_FATAL_ERROR) {
@@ -2905,9 +2880,8 @@ int lm_step_loaded(ceres_hip_solver* s, const ceres_hip_lm_options* o, double* d
   // Finite check + negation and the model cost change are enqueued together and read back with ONE
   // synchronisation (and, sharded, one all-reduce of {flag, cost}); a non-finite step makes the
   // cost meaningless, it is then ignored.
-  if (!s->lm_negated && !spec_done) {
-    if (!s->nonfinite_clean) HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), st));
-    s->nonfinite_clean = false;
+  if (!out.negated && !spec_done) {
+    HIP_TRY(s, hipMemsetAsync(s->d_nonfinite, 0, sizeof(int), st));
     if (!cgnr_deferred) HIP_TRY(s, LaunchNegateAndCheck(dx, h.num_cols, s->d_nonfinite, st));
   }
   double* const neg = cgnr_deferred ? dx : nullptr;  // CGNR: the model-cost kernel writes dx = -y and checks it
@@ -2925,15 +2899,15 @@ int lm_step_loaded(ceres_hip_solver* s, const ceres_hip_lm_options* o, double* d
       parts_local = s->scalar_partials;
       parts_shared = s->scalar_partials + kMaxVecGrid;
     } else {
-      if (spec_done) n_shared = s->spec_cgnr_parts;  // the gated kernel in front of the last poll already did all of it
+      if (spec_done) n_shared = out.spec_cgnr_parts;  // the gated kernel in front of the last poll already did all of it
       else HIP_TRY(s, LaunchCgnrModelCost(s->cg.x, s->cg_rhs, s->cg.r, s->D, 0, h.num_cols, s->scalar_partials, &n_shared, st, neg, s->d_nonfinite, nullptr, point_perm(s)));
       if (h.num_cols <= 0) n_shared = 0;
       parts_shared = s->scalar_partials;
     }
-  } else if (s->backsub_cost_parts > 0) {  // the back-substitution kernel already formed it
+  } else if (out.backsub_cost_parts > 0) {  // the back-substitution kernel (or the point tail) already formed it
     parts_local = s->scalar_partials;
-    n_local = s->backsub_cost_parts;
-  } else if (!s->lm_skip_model_cost) {
+    n_local = out.backsub_cost_parts;
+  } else if (!rq.skip_model_cost) {
     TRY(enqueue_model_cost_change(s, dx, &parts_local, &n_local));  // rows are sharded: every rank holds a share
   }
   double* hp = s->h_pinned;
@@ -3085,6 +3059,7 @@ int ceres_hip_time_op(ceres_hip_solver* s, int32_t op, int32_t iters, double* av
   hipStream_t st = s->stream;
   const int64_t n = is_schur(s) ? h.num_cols_f : h.num_cols;
   std::function<int()> body;
+  SolveCtx plain;   // operator-level calls: a plain request, nothing promised
   struct DeviceScratch {   // (operands of the two probes that need vectors of their own)
     double* p = nullptr;
     ~DeviceScratch() { if (p) (void)hipFree(p); }
@@ -3122,30 +3097,30 @@ int ceres_hip_time_op(ceres_hip_solver* s, int32_t op, int32_t iters, double* av
       break;
     case CERES_HIP_TIMED_SX:
       if (!is_schur(s)) return fail(s, CERES_HIP_E_INVALID, "Sx needs an ITERATIVE_SCHUR instance");
-      TRY(op_schur_init(s, true));
+      TRY(op_schur_init(s, plain, true));
       body = [&] { return op_sx(s, s->cg.p, s->cg.z, nullptr); };
       break;
     case CERES_HIP_TIMED_SCHUR_INIT:  // as a solve runs it: fused with the re-layout of the step's values
       if (!is_schur(s)) return fail(s, CERES_HIP_E_INVALID, "needs an ITERATIVE_SCHUR instance");
-      body = [&] { s->packed = false; return op_schur_init(s, true); };
+      body = [&] { s->packed = false; return op_schur_init(s, plain, true); };
       break;
     case CERES_HIP_TIMED_CGNR_SETUP:
       if (is_schur(s) || s->path != CERES_HIP_PATH_BAL) return fail(s, CERES_HIP_E_INVALID, "needs a CGNR instance on the <2,3,9> path");
-      body = [&] { s->packed = false; return op_cgnr_setup_bal(s, s->opt.preconditioner_type == CERES_HIP_JACOBI, s->cg_rhs, s->precond); };
+      body = [&] { s->packed = false; return op_cgnr_setup_bal(s, plain, s->opt.preconditioner_type == CERES_HIP_JACOBI, s->cg_rhs, s->precond); };
       break;
     case CERES_HIP_TIMED_SCHUR_JACOBI:
       if (!is_schur(s)) return fail(s, CERES_HIP_E_INVALID, "needs an ITERATIVE_SCHUR instance");
-      TRY(op_schur_init(s, true));
-      body = [&] { return op_preconditioner(s, CERES_HIP_SCHUR_JACOBI, s->precond, true); };
+      TRY(op_schur_init(s, plain, true));
+      body = [&] { return op_preconditioner(s, plain, CERES_HIP_SCHUR_JACOBI, s->precond, true); };
       break;
     case CERES_HIP_TIMED_BLOCK_JACOBI:
-      if (is_schur(s)) TRY(op_schur_init(s, false));
-      body = [&] { return op_preconditioner(s, CERES_HIP_JACOBI, s->precond, true); };
+      if (is_schur(s)) TRY(op_schur_init(s, plain, false));
+      body = [&] { return op_preconditioner(s, plain, CERES_HIP_JACOBI, s->precond, true); };
       break;
     case CERES_HIP_TIMED_BACK_SUBSTITUTE:
       if (!is_schur(s)) return fail(s, CERES_HIP_E_INVALID, "needs an ITERATIVE_SCHUR instance");
-      TRY(op_schur_init(s, false));
-      body = [&] { return op_back_substitute(s, s->cg.p, s->own_x); };
+      TRY(op_schur_init(s, plain, false));
+      body = [&] { return op_back_substitute(s, plain, s->cg.p, s->own_x); };
       break;
     case CERES_HIP_TIMED_PACK:
       if (s->path != CERES_HIP_PATH_BAL) return fail(s, CERES_HIP_E_INVALID, "pack exists on the <2,3,9> path only");
@@ -3168,12 +3143,12 @@ int ceres_hip_time_op(ceres_hip_solver* s, int32_t op, int32_t iters, double* av
     case CERES_HIP_TIMED_CLUSTER_FACTOR:
     case CERES_HIP_TIMED_CLUSTER_APPLY: {
       if (!is_cluster_jacobi(s) || h.ncb - h.nelim <= 0) return fail(s, CERES_HIP_E_INVALID, "needs an ITERATIVE_SCHUR instance with CLUSTER_JACOBI");
-      TRY(op_schur_init(s, false));
+      TRY(op_schur_init(s, plain, false));
       bool failed = false;
-      TRY(op_cluster_jacobi_update(s, &failed));
+      TRY(op_cluster_jacobi_update(s, plain, &failed));
       if (failed) return fail(s, CERES_HIP_E_INVALID, "Preconditioner update failed.");
       if (op == CERES_HIP_TIMED_CLUSTER_ELIMINATE) body = [&] { return cluster_jacobi_eliminate(s); };
-      else if (op == CERES_HIP_TIMED_CLUSTER_FACTOR) body = [&] { return cluster_jacobi_assemble_and_factor(s); };   // (re-assembled from the blocks every time)
+      else if (op == CERES_HIP_TIMED_CLUSTER_FACTOR) body = [&] { return cluster_jacobi_assemble_and_factor(s, plain); };   // (re-assembled from the blocks every time)
       else body = [&] { return op_cluster_jacobi_apply(s, s->cg.p, s->cg.z, nullptr); };
       break;
     }

@@ -139,7 +139,8 @@ int ceres_hip_op_schur_init(ceres_hip_solver* s) {
   TRY(require_loaded(s));
   HIP_TRY(s, hipSetDevice(s->opt.device));
   if (!is_schur(s)) return fail(s, CERES_HIP_E_INVALID, "not an ITERATIVE_SCHUR instance");
-  TRY(op_schur_init(s, true));
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  TRY(op_schur_init(s, op, true));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   return 0;
 }
@@ -181,7 +182,8 @@ int ceres_hip_op_back_substitute(ceres_hip_solver* s, const double* z, double* x
   HIP_TRY(s, hipSetDevice(s->opt.device));
   if (!is_schur(s)) return fail(s, CERES_HIP_E_INVALID, "not an ITERATIVE_SCHUR instance");
   if (s->hs.num_cols_f > 0) TRY(up(s, s->cg.p, z, s->hs.num_cols_f));
-  TRY(op_back_substitute(s, s->hs.num_cols_f > 0 ? s->cg.p : nullptr, s->own_x));
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  TRY(op_back_substitute(s, op, s->hs.num_cols_f > 0 ? s->cg.p : nullptr, s->own_x));
   return down(s, x, s->own_x, s->hs.num_cols);
 }
 
@@ -192,7 +194,8 @@ int ceres_hip_op_power_series_operator(ceres_hip_solver* s, const double* x, dou
   const int n = s->hs.num_cols_f;
   TRY(up(s, s->cg.p, x, n));
   TRY(up(s, s->cg.z, y, n));
-  TRY(op_power_series(s, s->cg.p, s->cg.z, nullptr));
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  TRY(op_power_series(s, op, s->cg.p, s->cg.z, nullptr));
   return down(s, y, s->cg.z, n);
 }
 
@@ -203,19 +206,17 @@ int ceres_hip_op_spse_apply(ceres_hip_solver* s, const double* x, double* y, int
   if (max_iters < 1) return fail(s, CERES_HIP_E_INVALID, "max_num_spse_iterations < 1");
   const int n = s->hs.num_cols_f;
   TRY(up(s, s->cg.p, x, n));
-  TRY(op_spse_apply(s, s->cg.p, s->cg.z, max_iters, tolerance, nullptr));
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  TRY(op_spse_apply(s, op, s->cg.p, s->cg.z, max_iters, tolerance, nullptr));
   return down(s, y, s->cg.z, n);
 }
 
 int ceres_hip_op_block_jacobi_update(ceres_hip_solver* s) {
   TRY(require_loaded(s));
   HIP_TRY(s, hipSetDevice(s->opt.device));
-  if (is_schur(s)) {
-    TRY(op_schur_init(s, false));
-    TRY(op_preconditioner(s, CERES_HIP_JACOBI, s->precond, true));
-  } else {
-    TRY(op_preconditioner(s, CERES_HIP_JACOBI, s->precond, true));
-  }
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  if (is_schur(s)) TRY(op_schur_init(s, op, false));
+  TRY(op_preconditioner(s, op, CERES_HIP_JACOBI, s->precond, true));
   s->precond_valid = true;
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   return 0;
@@ -225,8 +226,9 @@ int ceres_hip_op_schur_jacobi_update(ceres_hip_solver* s) {
   TRY(require_loaded(s));
   HIP_TRY(s, hipSetDevice(s->opt.device));
   if (!is_schur(s)) return fail(s, CERES_HIP_E_INVALID, "not an ITERATIVE_SCHUR instance");
-  TRY(op_schur_init(s, true));
-  TRY(op_preconditioner(s, CERES_HIP_SCHUR_JACOBI, s->precond, true));
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  TRY(op_schur_init(s, op, true));
+  TRY(op_preconditioner(s, op, CERES_HIP_SCHUR_JACOBI, s->precond, true));
   s->precond_valid = true;
   HIP_TRY(s, hipStreamSynchronize(s->stream));
   return 0;
@@ -237,9 +239,10 @@ int ceres_hip_op_cluster_jacobi_update(ceres_hip_solver* s) {
   HIP_TRY(s, hipSetDevice(s->opt.device));
   if (!is_cluster_jacobi(s)) return fail(s, CERES_HIP_E_INVALID, "the handle was not created with the CLUSTER_JACOBI preconditioner");
   if (s->hs.ncb - s->hs.nelim <= 0) return fail(s, CERES_HIP_E_INVALID, "the structure has no F block");
-  TRY(op_schur_init(s, false));
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  TRY(op_schur_init(s, op, false));
   bool failed = false;
-  TRY(op_cluster_jacobi_update(s, &failed));
+  TRY(op_cluster_jacobi_update(s, op, &failed));
   if (failed) return fail(s, CERES_HIP_E_INVALID, "Preconditioner update failed.");
   return 0;
 }
@@ -273,8 +276,9 @@ int ceres_hip_get_preconditioner_blocks(ceres_hip_solver* s, int32_t not_inverte
   HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&tmp), sizeof(double) * std::max<int64_t>(1, len)));
   int rc = debug_poison(s, tmp, size_t(len)) == hipSuccess ? 0 : fail(s, CERES_HIP_E_HIP, "CERES_HIP_DEBUG_POISON: filling a new buffer failed");
   int type = s->opt.preconditioner_type == CERES_HIP_IDENTITY ? CERES_HIP_JACOBI : s->opt.preconditioner_type;
-  if (!rc && is_schur(s)) rc = op_schur_init(s, true);
-  if (!rc) rc = op_preconditioner(s, type, tmp, false);
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  if (!rc && is_schur(s)) rc = op_schur_init(s, op, true);
+  if (!rc) rc = op_preconditioner(s, op, type, tmp, false);
   if (!rc) rc = down(s, blocks, tmp, size_t(len));
   (void)hipFree(tmp);
   return rc;
@@ -312,7 +316,8 @@ int ceres_hip_op_schur_eliminate_dense(ceres_hip_solver* s, double* lhs, double*
   if (!is_schur(s)) return fail(s, CERES_HIP_E_INVALID, "not an ITERATIVE_SCHUR instance");
   if (s->path != CERES_HIP_PATH_GENERIC) return fail(s, CERES_HIP_E_UNSUPPORTED, "dense elimination runs on the generic path: create the solver with force_generic_path = 1");
   const HostStructure& h = s->hs;
-  TRY(op_schur_init(s, false));
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  TRY(op_schur_init(s, op, false));
   const int64_t n = h.num_cols_f;
   double* d_lhs = nullptr;
   HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&d_lhs), sizeof(double) * std::max<int64_t>(1, n * n)));
@@ -341,7 +346,8 @@ int ceres_hip_op_schur_eliminate_sparse(ceres_hip_solver* s, int32_t* pair_i, in
   const SchurStorage& Q = s->schur_storage;
   const int64_t np = int64_t(Q.pair_i.size());
   if (pair_capacity < np || value_capacity < Q.num_values()) return fail(s, CERES_HIP_E_INVALID, "capacity too small");
-  TRY(op_schur_init(s, false));
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  TRY(op_schur_init(s, op, false));
   HIP_TRY(s, LaunchSchurSparseEliminate(s->G, s->schur_pairs, s->values, s->etei, s->D, s->d_S, s->stream));
   for (int64_t p = 0; p < np; ++p) { pair_i[p] = Q.pair_i[p]; pair_j[p] = Q.pair_j[p]; pair_offset[p] = Q.pair_off[p]; }
   return down(s, values, s->d_S, size_t(Q.num_values()));
@@ -364,7 +370,8 @@ int ceres_hip_op_eliminator_back_substitute(ceres_hip_solver* s, const double* z
   TRY(require_loaded(s));
   HIP_TRY(s, hipSetDevice(s->opt.device));
   if (!is_schur(s)) return fail(s, CERES_HIP_E_INVALID, "not an ITERATIVE_SCHUR instance");
-  TRY(op_schur_init(s, false));
+  SolveCtx op;   // operator-level call: a plain request, nothing promised
+  TRY(op_schur_init(s, op, false));
   return ceres_hip_op_back_substitute(s, z, x);
 }
 
