@@ -62,6 +62,9 @@ struct ceres_hip_bal {
   int64_t* d_free_block = nullptr;             // BalFreeBlocks::block
   int32_t *d_pack_cam = nullptr, *d_pack_scale = nullptr;   // BalEvalTilesArgs' camera records (constant cameras on the tile path)
   double2* d_scrap = nullptr;
+  // ceres_hip_bal_create_with_fixed_intrinsics (SubsetManifold on every camera; kernels_subset.hip): bit k set — coordinate 6 + k of every
+  // camera is constant.  cs stays 9, cw = 9 - bits; 0 on every other handle
+  int intrinsics_mask = 0;
   // ceres_hip_bal_evaluate_gradient / ceres_hip_bal_minimize_line_search (line_search.inc): their lists and vectors, made on first use
   struct BalLineSearch* ls = nullptr;
   // ceres_hip_bal_covariance (covariance.inc): its lists and buffers, made on first use
@@ -96,7 +99,10 @@ int bal_evaluate_device(ceres_hip_bal* p, const double* d_state, bool jacobian, 
   A.state = d_state; A.cam_base = 3 * int64_t(p->np); A.scale = d_scale;
   A.residuals = d_residuals; A.values = jacobian ? p->d_vals : nullptr; A.partials = p->d_parts; A.loss = p->loss;
   int nparts = 0;
-  if (p->has_const && jacobian) {   // a reduced program: the cells of constant blocks are neither scaled nor stored
+  if (p->intrinsics_mask && jacobian) {   // fixed intrinsics: F cells of 2 x cw (the cost alone has no columns to remove)
+    A.row_fpos = p->d_row_fpos; A.row_scam = p->d_row_scam; A.row_spt = p->d_row_spt;   // (uploaded with or without constant blocks)
+    HIP_TRY(s, LaunchBalEvaluateSubset(A, p->intrinsics_mask, &nparts, s->stream));
+  } else if (p->has_const && jacobian) {   // a reduced program: the cells of constant blocks are neither scaled nor stored
     A.row_fpos = p->d_row_fpos; A.row_scam = p->d_row_scam; A.row_spt = p->d_row_spt;
     HIP_TRY(s, LaunchBalEvaluateConst(A, &nparts, s->stream, p->camera_model));
   } else {
@@ -117,6 +123,7 @@ bool bal_writes_tiles(const ceres_hip_bal* p) {
   const ceres_hip_solver* s = p->s;
   // (the tile evaluator computes the angle-axis Jacobian: quaternion cameras keep the two-pass form — the manifold's <2,3,9> included)
   if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) return false;
+  if (p->intrinsics_mask) return false;   // (the tile evaluator writes <2,3,9> tiles)
   // (constant blocks: the tile evaluator's records exist for constant cameras alone — constant points leave remainder rows anyway)
   if (p->has_const && !p->d_pack_cam) return false;
   if (const char* e = getenv("CERES_HIP_EVAL_TILES")) if (atoi(e) == 0) return false;
@@ -132,6 +139,7 @@ bool bal_writes_tiles(const ceres_hip_bal* p) {
 // caller-layout copy of the Jacobian exists then — or read them from p->d_vals (CERES_HIP_EVAL_TILES=2: always; 3: never).
 bool bal_camera_pass_evaluates(const ceres_hip_bal* p) {
   if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) return false;   // (the evaluating pass is angle-axis)
+  if (p->intrinsics_mask) return false;                               // (and nine columns wide)
   if (const char* e = getenv("CERES_HIP_EVAL_TILES")) {
     if (atoi(e) == 2) return false;
     if (atoi(e) == 3) return p->d_cm_obs != nullptr;   // (tests: the evaluating kernel whatever the item length)
@@ -215,7 +223,10 @@ int bal_gradient_max(ceres_hip_bal* p, const double* d_scale, const double* d_x,
 // delta = step .* scale, cand = Plus(x, delta); |x|^2 partials at parts[0 ..), |delta|^2 at parts[*nparts ..)
 int bal_candidate(ceres_hip_bal* p, const double* x, const double* scale, double* cand, double* parts, int* nparts) {
   ceres_hip_solver* s = p->s;
-  if (p->has_const)   // (Plus scattered into the free blocks; cand's constant blocks hold the state's values already: ceres_hip_bal_minimize)
+  if (p->intrinsics_mask)   // (fixed intrinsics: a narrower step scattered into the free coordinates, with or without constant blocks)
+    HIP_TRY(s, LaunchBalCandidateSubset(BalFreeBlocks{p->has_const ? p->d_free_block : nullptr, p->nfp, p->nfc}, p->intrinsics_mask, p->np, x,
+                                        p->d_step, scale, p->d_delta, cand, parts, nparts, s->stream));
+  else if (p->has_const)   // (Plus scattered into the free blocks; cand's constant blocks hold the state's values already: ceres_hip_bal_minimize)
     HIP_TRY(s, LaunchBalCandidateFree(BalFreeBlocks{p->d_free_block, p->nfp, p->nfc}, p->camera_model, x, p->d_step, scale, p->d_delta, cand, parts,
                                       nparts, s->stream));
   else if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD)
@@ -293,12 +304,13 @@ void ceres_hip_bal_destroy(ceres_hip_bal* p) {
 
 namespace {
 
-// ceres_hip_bal_create, ceres_hip_bal_create_with_camera and ceres_hip_bal_create_with_constant_blocks (`fn` names the entry point in
-// the messages).  The masks may be NULL; with none set the reduction below is the identity and the handle is what it always was.
+// ceres_hip_bal_create, ceres_hip_bal_create_with_camera, ceres_hip_bal_create_with_constant_blocks and
+// ceres_hip_bal_create_with_fixed_intrinsics (`fn` names the entry point in the messages).  The masks may be NULL; with none set the
+// reduction below is the identity, the camera keeps its width and the handle is what it always was.
 ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras, int32_t num_points,
                           int64_t num_observations, const int32_t* camera_index, const int32_t* point_index,
                           const double* observations, const uint8_t* camera_is_constant = nullptr,
-                          const uint8_t* point_is_constant = nullptr) try {   // (host vectors sized by the caller's counts: no C++ exception crosses the C boundary)
+                          const uint8_t* point_is_constant = nullptr, const uint8_t* camera_coordinate_is_constant = nullptr) try {   // (host vectors sized by the caller's counts: no C++ exception crosses the C boundary)
   const std::string name(fn);
   static_assert(kCamAngleAxis == CERES_HIP_CAMERA_ANGLE_AXIS && kCamQuaternion == CERES_HIP_CAMERA_QUATERNION &&
                 kCamQuaternionManifold == CERES_HIP_CAMERA_QUATERNION_MANIFOLD, "device camera models are the ABI's");
@@ -312,8 +324,24 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
     return nullptr;
   }
   const int cs = camera_model == CERES_HIP_CAMERA_ANGLE_AXIS ? 9 : 10;       // state doubles per camera
-  const int cw = camera_model == CERES_HIP_CAMERA_QUATERNION ? 10 : 9;       // Jacobian columns per camera (tangent)
-  const int64_t per_obs = 6 + 2 * cw;                                        // Jacobian values per observation: 24, 26 or 24
+  // SubsetManifold on every camera (one mask of cs entries; NULL: none): the intrinsics f, k1, k2 of the angle-axis camera alone
+  int intrinsics_mask = 0;
+  for (int j = 0; camera_coordinate_is_constant && j < cs; ++j) {
+    if (!camera_coordinate_is_constant[j]) continue;
+    if (camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) {
+      g_create_error = name + ": constant camera coordinates are supported for the angle-axis camera only (camera_model " + std::to_string(camera_model) + ")";
+      return nullptr;
+    }
+    if (j >= 6) { intrinsics_mask |= 1 << (j - 6); continue; }
+    bool all = true;
+    for (int k = 0; k < cs; ++k) all = all && camera_coordinate_is_constant[k] != 0;
+    g_create_error = all ? name + ": every camera coordinate is constant: use constant cameras (camera_is_constant)"
+                         : name + ": camera coordinate " + std::to_string(j) + " cannot be constant: only the intrinsics, coordinates 6 .. 8 (f, k1, k2)";
+    return nullptr;
+  }
+  // Jacobian columns per camera (tangent): the free coordinates
+  const int cw = (camera_model == CERES_HIP_CAMERA_QUATERNION ? 10 : 9) - ((intrinsics_mask & 1) + ((intrinsics_mask >> 1) & 1) + ((intrinsics_mask >> 2) & 1));
+  const int64_t per_obs = 6 + 2 * cw;                                        // Jacobian values per observation: 24, 26 or 24 (18 .. 22 with fixed intrinsics)
   if (num_observations * per_obs > int64_t(INT32_MAX)) {  // cell.position is an int in the reference too (I/block_structure.h:64)
     g_create_error = name + ": more than " + std::to_string(int64_t(INT32_MAX) / per_obs / 1000000) +
                      " M observations do not fit 32-bit value positions";
@@ -344,6 +372,10 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
     g_create_error = name + ": more than 2^31 state doubles with constant blocks";
     return nullptr;
   }
+  if (intrinsics_mask && 3 * int64_t(num_points) + cs * int64_t(num_cameras) > int64_t(INT32_MAX)) {   // (row_scam / row_spt are 32-bit)
+    g_create_error = name + ": more than 2^31 state doubles with fixed intrinsics";
+    return nullptr;
+  }
   ceres_hip_options o = *options;
   o.num_eliminate_blocks = nfp;
   ceres_hip_solver* s = ceres_hip_create(&o);
@@ -353,7 +385,7 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
   const int64_t no = int64_t(R.row_obs.size());   // kept rows
   p->nc = num_cameras; p->np = num_points; p->no = no;
   p->nfc = nfc; p->nfp = nfp; p->has_const = has_const;
-  p->camera_model = camera_model; p->cs = cs; p->cw = cw;
+  p->camera_model = camera_model; p->cs = cs; p->cw = cw; p->intrinsics_mask = intrinsics_mask;
   p->n_a = 3 * int64_t(num_points) + cs * int64_t(num_cameras);
   p->n_t = 3 * int64_t(nfp) + cw * int64_t(nfc);
   auto bail = [&](const char* what) -> ceres_hip_bal* {
@@ -425,9 +457,14 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
       p->d_rm_obs = reinterpret_cast<double2*>(md);
     }
   }
+  // fixed intrinsics without constant blocks: the evaluator's per-row positions all the same (kernels_subset.hip has the one form)
+  if (ok && intrinsics_mask && !has_const)
+    ok = dev_upload(s, &p->d_row_fpos, rfpos) == 0 && dev_upload(s, &p->d_row_scam, rscam) == 0 && dev_upload(s, &p->d_row_spt, rspt) == 0;
   // the rows' camera / point / pixel in slot order: the tile evaluator's and the evaluating camera-major pass's records (angle-axis only;
-  // with constant blocks: constant cameras alone — every row then has its E cell, no row is outside the tiles)
-  if (ok && s->path == CERES_HIP_PATH_BAL && !s->plan.slot_bpos.empty() && camera_model == CERES_HIP_CAMERA_ANGLE_AXIS && nfp == num_points) {
+  // with constant blocks: constant cameras alone — every row then has its E cell, no row is outside the tiles; nine columns wide: not
+  // with fixed intrinsics)
+  if (ok && s->path == CERES_HIP_PATH_BAL && !s->plan.slot_bpos.empty() && camera_model == CERES_HIP_CAMERA_ANGLE_AXIS && nfp == num_points &&
+      intrinsics_mask == 0) {
     const size_t ns = s->plan.slot_bpos.size();
     // camera records: the free cameras in the solver's order, the constant ones behind them (the identity without constants)
     std::vector<int32_t> rec_of(num_cameras), pack_cam(num_cameras), pack_scale(num_cameras);
@@ -501,6 +538,23 @@ ceres_hip_bal* ceres_hip_bal_create_with_constant_blocks(const ceres_hip_options
                                                          const uint8_t* camera_is_constant, const uint8_t* point_is_constant) {
   return bal_create("ceres_hip_bal_create_with_constant_blocks", options, camera_model, num_cameras, num_points, num_observations, camera_index,
                     point_index, observations, camera_is_constant, point_is_constant);
+}
+
+ceres_hip_bal* ceres_hip_bal_create_with_fixed_intrinsics(const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras,
+                                                          int32_t num_points, int64_t num_observations, const int32_t* camera_index,
+                                                          const int32_t* point_index, const double* observations,
+                                                          const uint8_t* camera_is_constant, const uint8_t* point_is_constant,
+                                                          const uint8_t* camera_coordinate_is_constant) {
+  // (nothing marked: the handle — and the messages — of ceres_hip_bal_create_with_constant_blocks; an unknown camera model: the mask's
+  // length is unknown too, it is not read)
+  const bool known = camera_model >= CERES_HIP_CAMERA_ANGLE_AXIS && camera_model <= CERES_HIP_CAMERA_QUATERNION_MANIFOLD;
+  bool any = false;
+  for (int j = 0; known && camera_coordinate_is_constant && j < (camera_model == CERES_HIP_CAMERA_ANGLE_AXIS ? 9 : 10); ++j)
+    any = any || camera_coordinate_is_constant[j] != 0;
+  const bool mine = any || (!known && camera_coordinate_is_constant);
+  return bal_create(mine ? "ceres_hip_bal_create_with_fixed_intrinsics" : "ceres_hip_bal_create_with_constant_blocks", options, camera_model, num_cameras,
+                    num_points, num_observations, camera_index, point_index, observations, camera_is_constant, point_is_constant,
+                    any ? camera_coordinate_is_constant : nullptr);
 }
 
 int ceres_hip_bal_reduced_sizes(const ceres_hip_bal* p, int64_t* num_rows, int64_t* num_rows_e, int64_t* num_rows_removed,
@@ -608,6 +662,10 @@ int ceres_hip_debug_bal_evaluate_tiles_timing(ceres_hip_bal* p, const double* st
     p->err = "ceres_hip_debug_bal_evaluate_tiles_timing: the tile evaluator is angle-axis only";
     return CERES_HIP_E_UNSUPPORTED;
   }
+  if (p->intrinsics_mask) {
+    p->err = "ceres_hip_debug_bal_evaluate_tiles_timing: the tile evaluator is not supported on handles with fixed intrinsics";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
   HIP_TRY(s, hipSetDevice(s->opt.device));
   if (!bal_writes_tiles(p)) return fail(s, CERES_HIP_E_UNSUPPORTED, "the evaluator does not write this structure's tiles");
   if (p->has_const && flags != 0) return fail(s, CERES_HIP_E_UNSUPPORTED, "the store experiments are not built for handles with constant cameras");
@@ -659,6 +717,14 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
   }
   if (p->has_const && s->world > 1) {
     p->err = "ceres_hip_bal_minimize: constant parameter blocks are not supported on sharded handles";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
+  if (p->intrinsics_mask && s->world > 1) {
+    p->err = "ceres_hip_bal_minimize: fixed intrinsics are not supported on sharded handles";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
+  if (p->intrinsics_mask && p->inner_blocks != CERES_HIP_INNER_NONE) {   // (unreachable through ceres_hip_bal_set_inner_iterations)
+    p->err = "ceres_hip_bal_minimize: inner iterations are not supported on handles with fixed intrinsics";
     return CERES_HIP_E_UNSUPPORTED;
   }
   const int64_t n = p->n_a;

@@ -730,6 +730,16 @@ hipError_t LaunchBalCandidateFree(const BalFreeBlocks& B, int camera_model, cons
 hipError_t LaunchBalGradientMaxQuatFree(const BalFreeBlocks& B, const double* g, const double* scale, const double* x, double* partials,
                                         int* nparts, hipStream_t stream);
 
+// ---- fixed camera intrinsics (kernels_subset.hip; ceres_hip_bal_create_with_fixed_intrinsics) ----
+// mask: bit k set — coordinate 6 + k of every angle-axis camera is constant (1 .. 7); the tangent width of a camera is cw = 9 - bits.
+// The Jacobian evaluation with the marked columns removed after the Corrector and before the scale: F cells of 2 x cw where
+// BalEvalConstArgs says (always the reduced-program form; nothing constant: the identity reduction); A.scale indexes the tangent vector.
+hipError_t LaunchBalEvaluateSubset(const BalEvalConstArgs& A, int mask, int* nparts, hipStream_t stream);
+// delta = step .* scale (tangent), cand = x + delta on the free coordinates of the free blocks, marked coordinates copied from x;
+// B.block == nullptr: every block is free (B.n_free_points = n_points); partials as LaunchBalCandidateFree's
+hipError_t LaunchBalCandidateSubset(const BalFreeBlocks& B, int mask, int64_t n_points, const double* x, const double* step, const double* scale,
+                                    double* delta, double* cand, double* partials, int* nparts, hipStream_t stream);
+
 // ---- dogleg trust region of the BAL front end (kernels_dogleg.hip; dogleg.inc) ----
 constexpr int kDoglegGrid = 256;   // workgroups (and partial sums per scalar) of the two kernels below
 // partials[5 q + k], q < *nparts: workgroup q's share of |J a|^2, (J a).(J b), |J b|^2, (J a).f, (J b).f (k = 0 .. 4), one walk over

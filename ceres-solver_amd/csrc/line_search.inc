@@ -594,6 +594,10 @@ int ceres_hip_bal_evaluate_gradient(ceres_hip_bal* p, const double* state, doubl
     p->err = "ceres_hip_bal_evaluate_gradient: not supported on sharded handles";
     return CERES_HIP_E_UNSUPPORTED;
   }
+  if (p->intrinsics_mask) {   // (kernels_line_search.hip sums nine columns per camera)
+    p->err = "ceres_hip_bal_evaluate_gradient: not supported on handles with fixed intrinsics";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
   HIP_TRY(s, hipSetDevice(s->opt.device));
   BAL_TRY(p, bal_ls_prepare(p));
   BAL_TRY(p, up(s, p->d_cand, state, size_t(p->n_a)));   // (d_cand, d_delta: scratch of the trust-region loop between its calls)
@@ -624,6 +628,7 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
   if (!p) return refuse(CERES_HIP_E_INVALID, "NULL problem handle");
   ceres_hip_solver* s = p->s;
   if (s->world > 1) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on sharded handles");
+  if (p->intrinsics_mask) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with fixed intrinsics");
   hipStream_t st = s->stream;
   HIP_TRY(s, hipSetDevice(s->opt.device));
   const auto t_start = std::chrono::steady_clock::now();

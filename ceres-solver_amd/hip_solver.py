@@ -203,6 +203,9 @@ ABI += [
                                                     POINTER(c_int32), _DP]),
     ("ceres_hip_bal_create_with_constant_blocks", c_void_p, [POINTER(COptions), c_int32, c_int32, c_int32, c_int64, POINTER(c_int32),
                                                              POINTER(c_int32), _DP, POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8)]),
+    ("ceres_hip_bal_create_with_fixed_intrinsics", c_void_p, [POINTER(COptions), c_int32, c_int32, c_int32, c_int64, POINTER(c_int32),
+                                                              POINTER(c_int32), _DP, POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8),
+                                                              POINTER(ctypes.c_uint8)]),
     ("ceres_hip_bal_reduced_sizes", c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int32),
                                               POINTER(c_int32)]),
     ("ceres_hip_bal_fixed_cost", c_int32, [c_void_p, _DP, _DP]),
@@ -1144,6 +1147,38 @@ def debug_bal_reduce(num_cameras, num_points, camera_index, point_index, constan
     return rows[:nr.value].copy(), ne.value, ccol[:int(num_cameras)], pcol[:int(num_points)]
 
 
+INTRINSIC_NAMES = ("f", "k1", "k2")   # coordinates 6, 7, 8 of the angle-axis camera [angle-axis(3) t(3) f k1 k2]
+
+
+def _intrinsics_mask(spec, camera_state_size):
+    """constant_intrinsics -> a uint8 mask of camera_state_size entries, or None for nothing marked.  spec: names from INTRINSIC_NAMES,
+    coordinate indices, or a boolean mask of camera_state_size entries.  What may be marked is the library's rule (its message)."""
+    if spec is None:
+        return None
+    if isinstance(spec, str):
+        spec = [spec]
+    items = list(spec)
+    if len(items) == 0:
+        return None
+    m = np.zeros(camera_state_size, dtype=np.uint8)
+    if all(isinstance(v, (bool, np.bool_)) for v in items):
+        if len(items) != camera_state_size:
+            raise ValueError(f"constant_intrinsics: a boolean mask has {camera_state_size} entries, got {len(items)}")
+        m[:] = np.asarray(items, dtype=bool)
+    else:
+        for v in items:
+            if isinstance(v, str):
+                if v not in INTRINSIC_NAMES:
+                    raise ValueError(f"constant_intrinsics: unknown name {v!r}: one of {', '.join(INTRINSIC_NAMES)}")
+                m[6 + INTRINSIC_NAMES.index(v)] = 1
+            else:
+                j = int(v)
+                if j < 0 or j >= camera_state_size:
+                    raise ValueError(f"constant_intrinsics: coordinate {j} outside [0, {camera_state_size})")
+                m[j] = 1
+    return m if m.any() else None
+
+
 class BalProblem:
     """Bundle adjustment in BAL form on the device: the Evaluator of the reduced,
     Schur-ordered program (internal/ceres/evaluator.h:98-158) for the Snavely reprojection error
@@ -1161,10 +1196,16 @@ class BalProblem:
     constant_cameras / constant_points (Problem::SetParameterBlockConstant): index arrays or boolean masks of the blocks to hold fixed;
     None or empty takes the entry points above.  The state keeps its full layout (constant blocks are read, never written); the
     gradient, the Jacobian's columns and minimize's step are the reduced program's — free points, then free cameras, ascending — see
-    ceres_hip_bal_create_with_constant_blocks in include/ceres_hip.h, `reduced_sizes` and `fixed_cost`."""
+    ceres_hip_bal_create_with_constant_blocks in include/ceres_hip.h, `reduced_sizes` and `fixed_cost`.
+
+    constant_intrinsics (SubsetManifold on every camera block): names from ("f", "k1", "k2"), coordinate indices 6 .. 8 or a boolean
+    mask of nine — the intrinsics held fixed on all cameras while poses and points move; angle-axis cameras only.  The state stays
+    nine per camera (marked coordinates are read, never written); `camera_tangent_size` = 9 - (number marked) is the width of a
+    camera in the gradient, the step and the Jacobian — see ceres_hip_bal_create_with_fixed_intrinsics in include/ceres_hip.h for what
+    such a handle offers."""
 
     def __init__(self, options: LinearSolverOptions, num_cameras, num_points, camera_index, point_index, observations,
-                 camera_model="angle_axis", constant_cameras=None, constant_points=None):
+                 camera_model="angle_axis", constant_cameras=None, constant_points=None, constant_intrinsics=None):
         self._lib = load_library()
         self.options = options
         if isinstance(camera_model, str):
@@ -1186,7 +1227,13 @@ class BalProblem:
                      int(options.use_explicit_schur_complement), int(options.visibility_clustering_type))
         cm = _constant_mask(constant_cameras, self.num_cameras, "constant_cameras")
         pm = _constant_mask(constant_points, self.num_points, "constant_points")
-        if cm is not None or pm is not None:
+        im = _intrinsics_mask(constant_intrinsics, 9 if self.camera_model == CAMERA_ANGLE_AXIS else 10)
+        if im is not None:
+            self._h = self._lib.ceres_hip_bal_create_with_fixed_intrinsics(byref(c), self.camera_model, self.num_cameras, self.num_points,
+                                                                           self.num_observations, cam.ctypes.data_as(POINTER(c_int32)),
+                                                                           pt.ctypes.data_as(POINTER(c_int32)), _p(obs), _u8p(cm), _u8p(pm),
+                                                                           _u8p(im))
+        elif cm is not None or pm is not None:
             self._h = self._lib.ceres_hip_bal_create_with_constant_blocks(byref(c), self.camera_model, self.num_cameras, self.num_points,
                                                                           self.num_observations, cam.ctypes.data_as(POINTER(c_int32)),
                                                                           pt.ctypes.data_as(POINTER(c_int32)), _p(obs), _u8p(cm), _u8p(pm))
@@ -1206,6 +1253,8 @@ class BalProblem:
         self.num_parameters, self.num_residuals, self.num_jacobian_values = n.value, m.value, v.value
         self.num_effective_parameters = t.value
         self.camera_state_size = 9 if self.camera_model == CAMERA_ANGLE_AXIS else 10
+        # Jacobian columns per camera: the tangent of the manifold, less the coordinates constant_intrinsics marks
+        self.camera_tangent_size = (10 if self.camera_model == CAMERA_QUATERNION else 9) - (int(im.sum()) if im is not None else 0)
         self.num_rows = self.num_residuals // 2   # (= num_observations without constant blocks)
 
     @classmethod

@@ -100,11 +100,21 @@ class HipBalProblem {
   // constant, else one entry per camera / point, non-zero = constant.  With any entry the handle is the reduced program
   // (ceres_hip_bal_create_with_constant_blocks): the state keeps its full layout, the gradient and the Jacobian's columns are the free
   // blocks' (ReducedSizes); without, the entry point this class always used.
+  // camera_coordinate_is_constant (SubsetManifold(9, ...) on every camera block): empty = none, else nine entries, non-zero = constant
+  // on all cameras — only the intrinsics, coordinates 6 .. 8, of the angle-axis camera (ceres_hip_bal_create_with_fixed_intrinsics: the
+  // state stays nine per camera, a camera is CameraTangentSize() wide in the gradient and the Jacobian; what such a handle refuses is
+  // listed in include/ceres_hip.h).
   HipBalProblem(const LinearSolver::Options& options, const BalData& d, int camera_model = CERES_HIP_CAMERA_ANGLE_AXIS,
-                const std::vector<uint8_t>& camera_is_constant = {}, const std::vector<uint8_t>& point_is_constant = {}) {
+                const std::vector<uint8_t>& camera_is_constant = {}, const std::vector<uint8_t>& point_is_constant = {},
+                const std::vector<uint8_t>& camera_coordinate_is_constant = {}) {
     if ((!camera_is_constant.empty() && camera_is_constant.size() != size_t(d.num_cameras)) ||
         (!point_is_constant.empty() && point_is_constant.size() != size_t(d.num_points)))
       throw std::invalid_argument("HipBalProblem: a constant-block mask has one entry per block");
+    const size_t cs = camera_model == CERES_HIP_CAMERA_ANGLE_AXIS ? 9 : 10;
+    if (!camera_coordinate_is_constant.empty() && camera_coordinate_is_constant.size() != cs)
+      throw std::invalid_argument("HipBalProblem: the camera coordinate mask has one entry per camera state double");
+    camera_tangent_size_ = camera_model == CERES_HIP_CAMERA_QUATERNION ? 10 : 9;
+    for (uint8_t m : camera_coordinate_is_constant) camera_tangent_size_ -= m != 0;
     ceres_hip_options o{};
     o.solver_type = options.type;
     o.preconditioner_type = options.preconditioner_type;
@@ -112,7 +122,13 @@ class HipBalProblem {
     o.max_num_iterations = options.max_num_iterations;
     o.residual_reset_period = options.residual_reset_period;
     o.device = options.device;
-    if (camera_is_constant.empty() && point_is_constant.empty())
+    if (!camera_coordinate_is_constant.empty())
+      handle_ = ceres_hip_bal_create_with_fixed_intrinsics(&o, camera_model, d.num_cameras, d.num_points, int64_t(d.camera_index.size()),
+                                                           d.camera_index.data(), d.point_index.data(), d.observations.data(),
+                                                           camera_is_constant.empty() ? nullptr : camera_is_constant.data(),
+                                                           point_is_constant.empty() ? nullptr : point_is_constant.data(),
+                                                           camera_coordinate_is_constant.data());
+    else if (camera_is_constant.empty() && point_is_constant.empty())
       handle_ = ceres_hip_bal_create_with_camera(&o, camera_model, d.num_cameras, d.num_points, int64_t(d.camera_index.size()),
                                                  d.camera_index.data(), d.point_index.data(), d.observations.data());
     else
@@ -131,6 +147,7 @@ class HipBalProblem {
   int NumParameters() const { return int(num_parameters_); }   // Evaluator::NumParameters, I/evaluator.h:151
   int NumResiduals() const { return int(num_residuals_); }     // Evaluator::NumResiduals, :158
   int NumEffectiveParameters() const { return int(num_effective_parameters_); }   // Evaluator::NumEffectiveParameters: the gradient's length
+  int CameraTangentSize() const { return camera_tangent_size_; }   // Jacobian columns per free camera (Manifold::TangentSize of the block)
   // What Program::RemoveFixedBlocks left: rows kept, rows with an E cell (they come first), rows removed (both blocks constant), free
   // cameras, free points; any pointer may be null
   bool ReducedSizes(int64_t* num_rows, int64_t* num_rows_e, int64_t* num_rows_removed, int32_t* num_free_cameras, int32_t* num_free_points) const {
@@ -211,6 +228,7 @@ class HipBalProblem {
  private:
   ceres_hip_bal* handle_ = nullptr;
   int64_t num_parameters_ = 0, num_residuals_ = 0, num_jacobian_values_ = 0, num_effective_parameters_ = 0;
+  int camera_tangent_size_ = 9;
 };
 
 }  // namespace ceres_hip

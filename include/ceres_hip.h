@@ -521,6 +521,33 @@ ceres_hip_bal* ceres_hip_bal_create_with_constant_blocks(const ceres_hip_options
                                                          int32_t num_points, int64_t num_observations, const int32_t* camera_index,
                                                          const int32_t* point_index, const double* observations,
                                                          const uint8_t* camera_is_constant, const uint8_t* point_is_constant);
+/* Fixed camera intrinsics: SubsetManifold(9, constant coordinates) on EVERY camera block (include/ceres/manifold.h;
+ * I/residual_block.cc:161-195), together with constant blocks.  camera_coordinate_is_constant: cs entries (9), one mask for all
+ * cameras of the handle; NULL or all zero: exactly the handle ceres_hip_bal_create_with_constant_blocks builds.  Angle-axis cameras
+ * [angle-axis(3) t(3) f k1 k2] only, and only coordinates 6, 7, 8 (f, k1, k2) may be marked, any non-empty subset of them.
+ *   - STATE: ambient and unchanged, 9 doubles per camera (ceres_hip_bal_sizes' first value, 3 n_p + 9 n_c).  A marked coordinate is
+ *     read and never written: after ceres_hip_bal_minimize its doubles are bit-identical to the caller's.
+ *   - TANGENT: cw = 9 - (number marked) = 6, 7 or 8 entries per free camera, its free coordinates in ascending index;
+ *     ceres_hip_bal_num_effective_parameters = 3 free points + cw free cameras.  Plus adds the tangent step to the free coordinates.
+ *   - JACOBIAN: the ambient one with the marked columns removed (PlusJacobian is a selection) — after the Corrector, before the Jacobi
+ *     scale.  F cells are 2 x cw; the values are [E cells, 6 per row | F cells, 2 cw per row], 6 + 2 cw per kept row with both cells.
+ *   - The gradient's max norm is |g_i|_inf over the tangent, the step norm the tangent |delta|; |x| of the parameter-tolerance test
+ *     runs over the ambient doubles of the free blocks, marked coordinates included (the block stays in the program with all nine).
+ *   - camera_is_constant / point_is_constant as above: a constant camera is removed, the coordinate mask applies to the free ones.
+ *   - With an iterative solver, no force_generic_path and no constant point the handle runs the fused <2,3,cw> path.
+ * NULL (message in ceres_hip_bal_last_error(NULL)), before any device call: a quaternion camera model with an entry set, an entry set
+ * outside 6 .. 8, all nine set ("use constant cameras"), and what ceres_hip_bal_create_with_constant_blocks refuses.
+ * On a handle with fixed intrinsics ceres_hip_bal_evaluate, ceres_hip_bal_minimize (LEVENBERG_MARQUARDT and both DOGLEG types, every
+ * linear solver the front end accepts), ceres_hip_bal_set_loss, ceres_hip_bal_fixed_cost, ceres_hip_bal_reduced_sizes and
+ * ceres_hip_bal_get_row_order work as usual.  CERES_HIP_E_UNSUPPORTED, with a message that says so: ceres_hip_bal_set_inner_iterations
+ * with anything but NONE, ceres_hip_bal_inner_iterate, ceres_hip_bal_evaluate_gradient, ceres_hip_bal_minimize_line_search,
+ * ceres_hip_bal_covariance, ceres_hip_debug_bal_evaluate_tiles_timing, and ceres_hip_bal_minimize on a sharded handle.  The loop
+ * evaluates in the caller layout (the tile-order evaluator writes <2,3,9> tiles). */
+ceres_hip_bal* ceres_hip_bal_create_with_fixed_intrinsics(const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras,
+                                                          int32_t num_points, int64_t num_observations, const int32_t* camera_index,
+                                                          const int32_t* point_index, const double* observations,
+                                                          const uint8_t* camera_is_constant, const uint8_t* point_is_constant,
+                                                          const uint8_t* camera_coordinate_is_constant /* cs entries */);
 /* What the reduction made of the problem (all NULL-able): rows kept, rows with an E cell (they come first), rows dropped because both
  * blocks are constant, free cameras, free points. */
 int ceres_hip_bal_reduced_sizes(const ceres_hip_bal* p, int64_t* num_rows, int64_t* num_rows_e, int64_t* num_rows_removed,
@@ -533,7 +560,7 @@ const char* ceres_hip_bal_last_error(const ceres_hip_bal* p);
 /* The linear solver this problem drives (borrowed; operators, timing, info). */
 ceres_hip_solver* ceres_hip_bal_linear_solver(ceres_hip_bal* p);
 /* Evaluator::NumParameters (the ambient state) / NumResiduals, and the number of Jacobian values (6 + 2 x camera Jacobian columns per
- * observation: 24, or 26 for CERES_HIP_CAMERA_QUATERNION). */
+ * observation: 24, or 26 for CERES_HIP_CAMERA_QUATERNION; 18, 20 or 22 with fixed intrinsics). */
 int ceres_hip_bal_sizes(const ceres_hip_bal* p, int64_t* num_parameters, int64_t* num_residuals, int64_t* num_jacobian_values);
 /* Evaluator::NumEffectiveParameters: the tangent length — of the gradient, and the Jacobian's columns (= num_parameters for the
  * angle-axis and the Euclidean quaternion camera). */
@@ -705,14 +732,15 @@ typedef struct ceres_hip_line_search_summary {
 /* Evaluator::Evaluate(state, cost, nullptr, gradient, nullptr): cost = 1/2 sum rho with the handle's loss; gradient (may be NULL: the
  * cost alone) in the tangent space — ceres_hip_bal_num_effective_parameters doubles, free points then free cameras, unscaled; per
  * observation rho' J^T r.  No Jacobian value and no per-observation contribution is written to memory; no floating-point atomics: two
- * calls at one state give the same bits.  Works on every handle (any linear solver, any camera model, constant blocks); the solver's
- * loaded values are not touched.  CERES_HIP_E_UNSUPPORTED on a sharded handle. */
+ * calls at one state give the same bits.  Works on every handle (any linear solver, any camera model, constant blocks) EXCEPT one with
+ * fixed intrinsics (ceres_hip_bal_create_with_fixed_intrinsics): CERES_HIP_E_UNSUPPORTED there and on a sharded handle.  The solver's
+ * loaded values are not touched. */
 int ceres_hip_bal_evaluate_gradient(ceres_hip_bal* p, const double* state, double* cost, double* gradient);
 /* LineSearchMinimizer::Minimize.  state: host, in / out (constant blocks come back bit-identical; the reported costs include the fixed
  * cost).  No Jacobi scaling (the reference applies none here); the handle's inner-iteration and trust-region settings are ignored.
  * The options are validated first (LineSearchOptionsAreValid, internal/ceres/solver.cc, Ceres' wording): CERES_HIP_E_INVALID — also
  * for BISECTION with max_line_search_step_contraction > 0.5 or min_line_search_step_contraction < 0.5, which the reference only warns
- * about; CERES_HIP_E_UNSUPPORTED for CERES_HIP_BFGS and on a sharded handle.  The message is in ceres_hip_bal_last_error(p) — (NULL)
+ * about; CERES_HIP_E_UNSUPPORTED for CERES_HIP_BFGS, on a sharded handle and on a handle with fixed intrinsics.  The message is in ceres_hip_bal_last_error(p) — (NULL)
  * for a NULL handle. */
 int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_search_options* options, double* state,
                                        ceres_hip_line_search_summary* summary);
@@ -724,7 +752,8 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
  * with S dense, factored by the blocked Cholesky of DENSE_SCHUR and inverted from the factor on the matrix pipe.
  * Blocks are in the TANGENT space (3 for a point, 9 for an angle-axis or quaternion-manifold camera, 10 for a Euclidean quaternion
  * camera); a pair that involves a constant block is all zeros (covariance_impl.cc:143-165).  Not offered: lifting to the ambient space of
- * a manifold camera, null_space_rank and the pseudo-inverse, sharded handles, handles whose linear solver is not CERES_HIP_DENSE_SCHUR.
+ * a manifold camera, null_space_rank and the pseudo-inverse, sharded handles, handles whose linear solver is not CERES_HIP_DENSE_SCHUR,
+ * handles with fixed intrinsics (ceres_hip_bal_create_with_fixed_intrinsics: CERES_HIP_E_UNSUPPORTED).
  * RANK.  An unpivoted Cholesky does not notice a lost gauge, so S and every C_p are factored with a unit diagonal (S~ = Lambda S Lambda,
  * Lambda = diag(S)^-1/2; S^-1 = Lambda S~^-1 Lambda) and the call FAILS when a pivot is not above min_scaled_pivot, or when a diagonal
  * entry is not positive (a point all of whose rows a loss switched off).  This guard is a property of the inputs — on bundle-adjustment
@@ -752,7 +781,8 @@ typedef struct ceres_hip_covariance_summary {
  * The second n x n buffer (n = tangent scalars of the free cameras) is allocated on the first call and released with the handle.
  * Returns CERES_HIP_E_INVALID (message in ceres_hip_bal_last_error; of (NULL) for a NULL handle, which answers before any device call)
  * for a NULL handle, state, summary or pair array, num_pairs < 0, a block index out of range, a non-finite or negative
- * min_scaled_pivot; CERES_HIP_E_UNSUPPORTED for a handle whose linear solver is not CERES_HIP_DENSE_SCHUR and for a sharded handle.
+ * min_scaled_pivot; CERES_HIP_E_UNSUPPORTED for a handle whose linear solver is not CERES_HIP_DENSE_SCHUR, for a sharded handle and
+ * for a handle with fixed intrinsics.
  * A rank-deficient problem returns 0 with termination_type = CERES_HIP_FAILURE, the message naming the factorization that failed and
  * the pivot; blocks_out is then not written.  No floating-point atomics: two calls at one state give the same bits. */
 int ceres_hip_bal_covariance(ceres_hip_bal* p, const ceres_hip_covariance_options* options, const double* state,
