@@ -7,6 +7,8 @@
 //                             with LevenbergMarquardtStrategy  I/levenberg_marquardt_strategy.cc:69-157
 //                             or DoglegStrategy                I/dogleg_strategy.cc (dogleg.inc)
 //   ceres_hip_bal_minimize_line_search = LineSearchMinimizer::Minimize   I/line_search_minimizer.cc (line_search.inc)
+//   ceres_hip_bal_set_bounds = Problem::SetParameterLowerBound / SetParameterUpperBound: the projection inside Plus, the projected
+//                             gradient norm and DoLineSearch of the loop below (bounds.inc)
 // The loop below follows the reference statement by statement (the same restatement as
 // oracle/bal_harness.cc, which is what the parity tests compare it with); only the places
 // where vectors live differ: everything of size num_parameters / num_residuals stays in HBM.
@@ -69,14 +71,23 @@ struct ceres_hip_bal {
   struct BalLineSearch* ls = nullptr;
   // ceres_hip_bal_covariance (covariance.inc): its lists and buffers, made on first use
   struct BalCovariance* cov = nullptr;
+  // ceres_hip_bal_set_bounds (bounds.inc, kernels_bounds.hip): some coordinate of a free block has a finite bound — the one field
+  // ceres_hip_bal_minimize tests before anything it does for bounds; the bounds on the device (ambient layout, -inf / +inf: none), made
+  // by the first call that constrains the handle; the host copies, the search's options and the statistics
+  bool is_constrained = false;
+  double *d_lower = nullptr, *d_upper = nullptr;
+  struct BalBoundsState* bounds = nullptr;
 };
 void bal_inner_free(ceres_hip_bal* p);
 void bal_ls_free(ceres_hip_bal* p);
 void bal_cov_free(ceres_hip_bal* p);
+void bal_bounds_free(ceres_hip_bal* p);
 
 namespace {
 
 constexpr int kBalParts = 4096;
+BalBounds bal_bounds_args(const ceres_hip_bal* p);   // (bounds.inc)
+double bal_bounds_step_size(const ceres_hip_bal* p);
 
 int bal_fail(ceres_hip_bal* p, int code) {
   if (p && p->s) p->err = p->s->err;
@@ -197,7 +208,9 @@ int bal_gradient_max(ceres_hip_bal* p, const double* d_scale, const double* d_x,
   ceres_hip_solver* s = p->s;
   int nparts = 0;
   static_assert(kMaxVecGrid <= kBalParts - kBalSecondParts, "room for the second kernel's partials");
-  if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD && p->has_const)
+  if (p->is_constrained)   // |x - clamp(x - g)|_inf over the free blocks (I/trust_region_minimizer.cc:281-302)
+    HIP_TRY(s, LaunchBoundsGradientMax(bal_bounds_args(p), d_x, p->d_grad, d_scale, p->d_parts + kBalSecondParts, &nparts, s->stream));
+  else if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD && p->has_const)
     HIP_TRY(s, LaunchBalGradientMaxQuatFree(BalFreeBlocks{p->d_free_block, p->nfp, p->nfc}, p->d_grad, d_scale, d_x, p->d_parts + kBalSecondParts, &nparts,
                                             s->stream));
   else if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD)
@@ -221,9 +234,14 @@ int bal_gradient_max(ceres_hip_bal* p, const double* d_scale, const double* d_x,
 }
 
 // delta = step .* scale, cand = Plus(x, delta); |x|^2 partials at parts[0 ..), |delta|^2 at parts[*nparts ..)
+// (a constrained handle: delta = a (step .* scale) with the projected search's step size a, cand = clamp(x + delta), and the second
+// sum is |cand - x|^2, Ceres' ambient step norm; two more sets follow, unused here)
 int bal_candidate(ceres_hip_bal* p, const double* x, const double* scale, double* cand, double* parts, int* nparts) {
   ceres_hip_solver* s = p->s;
-  if (p->intrinsics_mask)   // (fixed intrinsics: a narrower step scattered into the free coordinates, with or without constant blocks)
+  if (p->is_constrained)
+    HIP_TRY(s, LaunchBoundsTrialPoint(bal_bounds_args(p), x, p->d_step, scale, nullptr, bal_bounds_step_size(p), true, p->d_delta, cand, parts,
+                                      nparts, s->stream));
+  else if (p->intrinsics_mask)   // (fixed intrinsics: a narrower step scattered into the free coordinates, with or without constant blocks)
     HIP_TRY(s, LaunchBalCandidateSubset(BalFreeBlocks{p->has_const ? p->d_free_block : nullptr, p->nfp, p->nfc}, p->intrinsics_mask, p->np, x,
                                         p->d_step, scale, p->d_delta, cand, parts, nparts, s->stream));
   else if (p->has_const)   // (Plus scattered into the free blocks; cand's constant blocks hold the state's values already: ceres_hip_bal_minimize)
@@ -265,6 +283,7 @@ double seconds_since(std::chrono::steady_clock::time_point t0) {
 #include "inner_iterations.inc"
 #include "dogleg.inc"
 #include "line_search.inc"
+#include "bounds.inc"
 #include "covariance.inc"
 
 extern "C" {
@@ -296,6 +315,7 @@ void ceres_hip_bal_destroy(ceres_hip_bal* p) {
   bal_inner_free(p);
   bal_ls_free(p);
   bal_cov_free(p);
+  bal_bounds_free(p);
   if (p->s) ceres_hip_destroy(p->s);  // frees every device allocation made through dev_alloc
   delete p;
 }
@@ -708,6 +728,17 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
   if (!p || !o || !state || !S) return CERES_HIP_E_INVALID;
   ceres_hip_solver* s = p->s;
   hipStream_t st = s->stream;
+  if (p->is_constrained) {   // Program::IsFeasible for the constant blocks (I/program.cc:240-289), before any device call
+    const std::string why = bal_bounds_constant_infeasible(p, state);
+    if (!why.empty()) {
+      p->err = "ceres_hip_bal_minimize: " + why;
+      return CERES_HIP_E_INVALID;
+    }
+    if (p->inner_blocks != CERES_HIP_INNER_NONE) {
+      p->err = "ceres_hip_bal_minimize: inner iterations are not supported on handles with bounds";
+      return CERES_HIP_E_UNSUPPORTED;
+    }
+  }
   HIP_TRY(s, hipSetDevice(s->opt.device));
   const auto t_start = std::chrono::steady_clock::now();
   memset(S, 0, sizeof(*S));
@@ -731,6 +762,11 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
   BAL_TRY(p, up(s, p->d_x, state, size_t(n)));
   double* x = p->d_x;
   double* cand = p->d_cand;
+  if (p->is_constrained) {   // iteration zero: x = Plus(x, 0), the projection onto the box (I/trust_region_minimizer.cc:210-220)
+    p->bounds->reset_stats();
+    p->bounds->ran_constrained = 1;
+    BAL_TRY(p, bal_bounds_project_device(p, x, &p->bounds->num_projected));
+  }
   // Constant blocks: the candidate buffer starts as a copy of the state — Plus and the inner passes write free blocks only, so the
   // constant blocks of both buffers stay the caller's doubles through every swap — and the removed rows' cost is taken once, here
   // (TrustRegionMinimizer adds solver_summary_->fixed_cost to every cost it reports: I/trust_region_minimizer.cc:127, 228, 261, 490)
@@ -766,6 +802,7 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
   }
 
   auto log_iter = [&](const ceres_hip_iteration_summary& it) {
+    if (p->is_constrained) bal_bounds_log(p, S->num_iterations_logged);   // (the projected search of the iteration being logged)
     if (S->num_iterations_logged < CERES_HIP_MAX_LOGGED_ITERATIONS) {
       S->iterations[S->num_iterations_logged] = it;
       S->iterations[S->num_iterations_logged++].cost += fixed_cost;   // (0.0 without constant blocks)
@@ -871,6 +908,9 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
       return d;
     };
     {
+      // DoLineSearch (I/trust_region_minimizer.cc:103-108): the projected Armijo search scales delta; the candidate below is
+      // clamp(x + a delta), its cost the loop's own evaluator's
+      if (p->is_constrained) BAL_TRY(p, bal_bounds_line_search(p, x, scale, cand, x_cost));
       const auto te = std::chrono::steady_clock::now();
       static_assert(2 * kMaxVecGrid <= kBalParts - kBalSecondParts, "room for |x|^2 and |delta|^2 partials");
       BAL_TRY(p, bal_candidate(p, x, scale, cand, p->d_parts + kBalSecondParts, &nparts));

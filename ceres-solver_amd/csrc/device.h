@@ -740,6 +740,29 @@ hipError_t LaunchBalEvaluateSubset(const BalEvalConstArgs& A, int mask, int* npa
 hipError_t LaunchBalCandidateSubset(const BalFreeBlocks& B, int mask, int64_t n_points, const double* x, const double* step, const double* scale,
                                     double* delta, double* cand, double* partials, int* nparts, hipStream_t stream);
 
+// ---- bound constraints (kernels_bounds.hip; bounds.inc: ceres_hip_bal_set_bounds) ----
+// Problem::SetParameterLowerBound / SetParameterUpperBound: lower / upper in the state's (ambient) layout, no bound = -inf / +inf.  Plus
+// is x + delta on every handle that takes bounds (angle-axis and Euclidean quaternion cameras), so a coordinate's ambient and tangent
+// offsets inside its block coincide.  Two forms of every kernel: B.block == nullptr — every block is free, ambient index = tangent
+// index, n = B.n_free_points (the whole state's length then); otherwise one work item per free block of `camera_width` (9 | 10) or 3
+// doubles.  Constant blocks are neither read nor written.  No floating-point atomics: per-workgroup partials, *nparts of each.
+struct BalBounds {
+  const double* lower = nullptr;
+  const double* upper = nullptr;
+  BalFreeBlocks B;         // block == nullptr: the plain form, n_free_points = the state's length
+  int camera_width = 9;
+};
+// Program::Plus(x, 0) in place: x = clamp(x) on the free blocks; counts[b], b < *nparts: the coordinates workgroup b moved
+hipError_t LaunchBoundsProject(const BalBounds& K, double* x, unsigned long long* counts, int* nparts, hipStream_t stream);
+// delta = step .* scale (fold: t (step .* scale)), out = clamp(x + t delta) (fold: clamp(x + delta)) on the free blocks; partials[k g + b],
+// g = *nparts: workgroup b's share of |x|^2 (k = 0), |out - x|^2 (1), max |delta| (2) and (grad ./ scale) . delta (3; grad == nullptr: 0).
+// scale may be nullptr (ones).  Products and sums are rounded one by one (no contraction), as the restatement's.
+hipError_t LaunchBoundsTrialPoint(const BalBounds& K, const double* x, const double* step, const double* scale, const double* grad, double t,
+                                  bool fold, double* delta, double* out, double* partials, int* nparts, hipStream_t stream);
+// partial maxima of |x - clamp(x - g ./ scale)| over the free blocks (I/trust_region_minimizer.cc:281-302)
+hipError_t LaunchBoundsGradientMax(const BalBounds& K, const double* x, const double* g, const double* scale, double* partials, int* nparts,
+                                   hipStream_t stream);
+
 // ---- dogleg trust region of the BAL front end (kernels_dogleg.hip; dogleg.inc) ----
 constexpr int kDoglegGrid = 256;   // workgroups (and partial sums per scalar) of the two kernels below
 // partials[5 q + k], q < *nparts: workgroup q's share of |J a|^2, (J a).(J b), |J b|^2, (J a).f, (J b).f (k = 0 .. 4), one walk over

@@ -338,6 +338,7 @@ int ceres_hip_bal_inner_iterate(ceres_hip_bal* p, double* state, double* cost_be
   if (!state || !cost_before || !cost_after) return refuse(CERES_HIP_E_INVALID, "NULL state or cost");
   if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported with quaternion cameras");
   if (p->intrinsics_mask) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with fixed intrinsics");
+  if (p->is_constrained) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with bounds");   // (the passes do not project)
   if (p->inner_blocks == CERES_HIP_INNER_NONE) return refuse(CERES_HIP_E_INVALID, "no inner iterations set (ceres_hip_bal_set_inner_iterations)");
   if (s->world > 1) return refuse(CERES_HIP_E_UNSUPPORTED, "not on sharded handles");
   HIP_TRY(s, hipSetDevice(s->opt.device));

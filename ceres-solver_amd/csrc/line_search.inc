@@ -629,6 +629,7 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
   ceres_hip_solver* s = p->s;
   if (s->world > 1) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on sharded handles");
   if (p->intrinsics_mask) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with fixed intrinsics");
+  if (p->is_constrained) return refuse(CERES_HIP_E_INVALID, "LINE_SEARCH Minimizer does not support bounds.");   // I/line_search_preprocessor.cc:47-51
   hipStream_t st = s->stream;
   HIP_TRY(s, hipSetDevice(s->opt.device));
   const auto t_start = std::chrono::steady_clock::now();

@@ -304,6 +304,16 @@ ABI += [
 ]
 
 
+# ---- bound constraints (include/ceres_hip.h: ceres_hip_bal_set_bounds; design/23_bounds.md) ----
+ABI += [
+    ("ceres_hip_bal_set_bounds", c_int32, [c_void_p, _DP, _DP, POINTER(CLineSearchOptions)]),
+    ("ceres_hip_bal_project", c_int32, [c_void_p, _DP, POINTER(c_int64)]),
+    ("ceres_hip_bal_bounds_stats", c_int32, [c_void_p, POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), _DP,
+                                             POINTER(c_int64), POINTER(c_int32), POINTER(c_int32), _DP]),
+    ("ceres_hip_debug_bal_bounded_step", c_int32, [c_void_p, _DP, _DP, c_double, _DP, _DP, _DP, _DP]),
+]
+
+
 def load_library():
     """dlopen csrc/libceres_hip.so and bind every ABI symbol; raises if anything is missing."""
     global _lib
@@ -1416,6 +1426,47 @@ class BalProblem:
         S = CMinimizerSummary()
         self._check(self._lib.ceres_hip_bal_minimize(self._h, byref(o), _p(x), byref(S)))
         return x, S
+
+    def set_bounds(self, lower=None, upper=None, **line_search_options_):
+        """Problem::SetParameterLowerBound / SetParameterUpperBound for every coordinate of the state at once (num_parameters doubles
+        each; None: no bound on that side, both None: clears).  The keyword arguments are the line-search fields of the projected search
+        (line_search_interpolation_type, min_line_search_step_size, line_search_sufficient_function_decrease,
+        max/min_line_search_step_contraction, max_num_line_search_step_size_iterations).  In force until set again."""
+        lo = None if lower is None else _f64(lower, self.num_parameters)
+        hi = None if upper is None else _f64(upper, self.num_parameters)
+        o = line_search_options(**line_search_options_) if line_search_options_ else None
+        self._check(self._lib.ceres_hip_bal_set_bounds(self._h, _p(lo), _p(hi), byref(o) if o is not None else None))
+
+    def project(self, state):
+        """Program::Plus(state, 0): (the state clamped to the bounds on the free blocks, the number of coordinates moved)."""
+        x = _f64(state, self.num_parameters).copy()
+        n = c_int64()
+        self._check(self._lib.ceres_hip_bal_project(self._h, _p(x), byref(n)))
+        return x, n.value
+
+    def bounds_stats(self):
+        """Of the last minimize: dict(is_constrained, num_line_search_steps, num_function_evaluations, num_gradient_evaluations,
+        line_search_seconds, num_projected, and per logged iteration line_search_iterations (-1: none ran), line_search_success,
+        step_size)."""
+        c, n, f, g, m = c_int32(), c_int32(), c_int32(), c_int32(), c_int64()
+        t = np.zeros(1)
+        its, ok = np.empty(MAX_LOGGED_ITERATIONS, dtype=np.int32), np.empty(MAX_LOGGED_ITERATIONS, dtype=np.int32)
+        step = np.empty(MAX_LOGGED_ITERATIONS)
+        self._check(self._lib.ceres_hip_bal_bounds_stats(self._h, byref(c), byref(n), byref(f), byref(g), _p(t), byref(m),
+                                                         its.ctypes.data_as(POINTER(c_int32)), ok.ctypes.data_as(POINTER(c_int32)), _p(step)))
+        return dict(is_constrained=c.value, num_line_search_steps=n.value, num_function_evaluations=f.value,
+                    num_gradient_evaluations=g.value, line_search_seconds=float(t[0]), num_projected=m.value,
+                    line_search_iterations=its, line_search_success=ok, step_size=step)
+
+    def bounded_step(self, state, v, t):
+        """Debug: the bounded loop's vector kernels at a state.  v: tangent (num_effective_parameters).  Returns (clamp(state + t v) on
+        the free blocks, |state| and |trial - state| over the free blocks, max |state - clamp(state - v)|)."""
+        x = _f64(state, self.num_parameters)
+        d = _f64(v, self.num_effective_parameters)
+        out = np.empty(self.num_parameters)
+        xn, sn, pm = np.zeros(1), np.zeros(1), np.zeros(1)
+        self._check(self._lib.ceres_hip_debug_bal_bounded_step(self._h, _p(x), _p(d), float(t), _p(out), _p(xn), _p(sn), _p(pm)))
+        return out, float(xn[0]), float(sn[0]), float(pm[0])
 
     def evaluate_gradient(self, state, gradient=True):
         """Evaluator::Evaluate(state, cost, nullptr, gradient, nullptr) without a Jacobian in memory: (cost, tangent gradient | None)."""

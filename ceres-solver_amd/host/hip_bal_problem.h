@@ -224,6 +224,29 @@ class HipBalProblem {
       throw std::runtime_error(std::string(ceres_hip_bal_last_error(handle_)));
     return s;
   }
+  // Problem::SetParameterLowerBound / SetParameterUpperBound for every coordinate of the state at once (NumParameters() doubles each,
+  // an empty vector: no bound on that side, both empty: clears).  line_search_options: the fields of the projected search Minimize then
+  // runs (Solver::Options::line_search_interpolation_type, min_line_search_step_size, ...), null: the defaults.  A refused call throws
+  // with Ceres' message (an infeasible bound, an option out of range).  Applies to the later Minimize calls.
+  void SetBounds(const std::vector<double>& lower, const std::vector<double>& upper,
+                 const ceres_hip_line_search_options* line_search_options = nullptr) {
+    if ((!lower.empty() && int64_t(lower.size()) != num_parameters_) || (!upper.empty() && int64_t(upper.size()) != num_parameters_))
+      throw std::invalid_argument("HipBalProblem::SetBounds: a bounds vector must have NumParameters() entries or none");
+    if (ceres_hip_bal_set_bounds(handle_, lower.empty() ? nullptr : lower.data(), upper.empty() ? nullptr : upper.data(), line_search_options) !=
+        CERES_HIP_OK)
+      throw std::invalid_argument(std::string(ceres_hip_bal_last_error(handle_)));
+  }
+  // Program::Plus(state, 0): state clamped to the bounds on the free blocks, in / out; *num_moved: the coordinates changed
+  bool Project(double* state, int64_t* num_moved) { return ceres_hip_bal_project(handle_, state, num_moved) == CERES_HIP_OK; }
+  // Of the last Minimize: Solver::Summary::is_constrained, num_line_search_steps, the searches' evaluations and seconds, the
+  // coordinates the initial projection moved; per logged iteration (arrays of CERES_HIP_MAX_LOGGED_ITERATIONS, may be null) the
+  // search's iterations (-1: none ran), success and step size.  Any pointer may be null.
+  bool BoundsStats(int32_t* is_constrained, int32_t* num_line_search_steps, int32_t* num_function_evaluations, int32_t* num_gradient_evaluations,
+                   double* line_search_seconds, int64_t* num_projected, int32_t* line_search_iterations = nullptr,
+                   int32_t* line_search_success = nullptr, double* step_size = nullptr) const {
+    return ceres_hip_bal_bounds_stats(handle_, is_constrained, num_line_search_steps, num_function_evaluations, num_gradient_evaluations,
+                                      line_search_seconds, num_projected, line_search_iterations, line_search_success, step_size) == CERES_HIP_OK;
+  }
 
  private:
   ceres_hip_bal* handle_ = nullptr;

@@ -744,6 +744,54 @@ int ceres_hip_bal_evaluate_gradient(ceres_hip_bal* p, const double* state, doubl
  * for a NULL handle. */
 int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_search_options* options, double* state,
                                        ceres_hip_line_search_summary* summary);
+/* ---- bound constraints (Problem::SetParameterLowerBound / SetParameterUpperBound; design/23_bounds.md) ----
+ * internal/ceres/parameter_block.h:227-255 (Plus clamps every coordinate of x_plus_delta to [lower, upper]), program.cc:215-289
+ * (IsBoundsConstrained, IsFeasible), trust_region_minimizer.cc:103-108, 210-220, 281-302, 596-641, 726-748 (the projected line search,
+ * the initial projection, the projected gradient norm, DoLineSearch, the ambient step norm), line_search.cc:103-145, 281-366
+ * (LineSearchFunction, ArmijoLineSearch), line_search_preprocessor.cc:47-51 (the line search minimizer refuses bounds).
+ * Bounds are per coordinate of the AMBIENT state, in the state's layout [3 per point | cs per camera].  A value <= -DBL_MAX (or -inf)
+ * is no lower bound, a value >= DBL_MAX (or +inf) no upper bound.  A handle is CONSTRAINED when some coordinate of a FREE block has a
+ * finite bound; bounds on constant blocks are kept but never applied.  A handle that is not constrained behaves in every call exactly
+ * as if bounds had never been set, bit for bit.  On a constrained handle ceres_hip_bal_minimize
+ *   - projects the state onto the box before the first evaluation (Plus(x, 0));
+ *   - reports gradient_max_norm = max |x - clamp(x - g)| over the free blocks;
+ *   - after every valid step runs a projected ARMIJO search on phi(a) = cost(clamp(x + a delta)), first sample a = 1, phi'(0) =
+ *     g . delta (unprojected, as Ceres passes it), direction max norm |delta|_inf; CUBIC interpolation evaluates the gradient at every
+ *     sample (phi'(a) = g(x_a) . delta), QUADRATIC and BISECTION the cost alone; success: delta *= a, failure (the iteration limit, or a
+ *     step below min_line_search_step_size): delta unchanged; model_cost_change stays the full step's;
+ *   - takes candidate = clamp(x + delta), its cost from the loop's own cost-only evaluation, and step_norm = |x - candidate| in the
+ *     ambient space (not the tangent |delta| of the unbounded loop).  The rest of the iteration is unchanged (it stays monotonic).
+ * Of the line-search options only line_search_interpolation_type, min_line_search_step_size, line_search_sufficient_function_decrease,
+ * max_line_search_step_contraction, min_line_search_step_contraction and max_num_line_search_step_size_iterations are read, and only
+ * they are validated (LineSearchOptionsAreValid's rules and wording); NULL: the defaults.
+ * ceres_hip_bal_evaluate, ceres_hip_bal_evaluate_gradient and ceres_hip_bal_covariance ignore bounds (the Evaluator and Covariance do).
+ * On a constrained handle ceres_hip_bal_minimize with inner iterations set and ceres_hip_bal_inner_iterate return
+ * CERES_HIP_E_UNSUPPORTED; ceres_hip_bal_minimize_line_search returns CERES_HIP_E_INVALID, "LINE_SEARCH Minimizer does not support
+ * bounds."; ceres_hip_bal_minimize returns CERES_HIP_E_INVALID before any device call when a constant block's value lies outside its
+ * bounds (Program::IsFeasible; the message names the block, the index and the three numbers; the state is untouched). */
+/* Problem::SetParameterLowerBound / SetParameterUpperBound for every coordinate at once. lower / upper: n_a doubles each
+ * (ceres_hip_bal_sizes' first value), copied; either NULL: no bound on that side; both NULL: clears. In force until set again.
+ * CERES_HIP_E_INVALID: a NULL handle, a NaN bound, lower >= upper on a coordinate of a free block (Ceres' "infeasible bound": the
+ * message gives the block, the index and both values), a line-search field out of range.  CERES_HIP_E_UNSUPPORTED with a non-NULL
+ * array: a CERES_HIP_CAMERA_QUATERNION_MANIFOLD handle, a handle with fixed intrinsics, a sharded handle.  A refused call changes
+ * nothing.  The device buffers of the feature are allocated by the first call that constrains the handle and freed with the handle. */
+int ceres_hip_bal_set_bounds(ceres_hip_bal* p, const double* lower, const double* upper,
+                             const ceres_hip_line_search_options* line_search_options);
+/* Program::Plus(state, 0): state (host, in/out) clamped on the free blocks; *num_moved = coordinates changed. Not constrained: untouched, 0. */
+int ceres_hip_bal_project(ceres_hip_bal* p, double* state, int64_t* num_moved);
+/* Of the last ceres_hip_bal_minimize: Summary::is_constrained, num_line_search_steps (sum of the searches' iterations), the searches'
+ * function / gradient evaluations and seconds, the coordinates the initial projection moved; and per LOGGED iteration i (index of
+ * summary.iterations[i]; arrays of CERES_HIP_MAX_LOGGED_ITERATIONS, NULL-able): the search's iterations (-1: none ran — iteration 0,
+ * an invalid step, an unconstrained handle), whether it succeeded, and the step size applied (1 where it failed or did not run). */
+int ceres_hip_bal_bounds_stats(const ceres_hip_bal* p, int32_t* is_constrained, int32_t* num_line_search_steps,
+                               int32_t* num_function_evaluations, int32_t* num_gradient_evaluations, double* line_search_seconds,
+                               int64_t* num_projected, int32_t* line_search_iterations, int32_t* line_search_success, double* step_size);
+/* Debug: the bounded loop's vector kernels at a host state, as the loop launches them. v: n_t (tangent).
+ * trial_out (n_a) = clamp(Plus(state, t v)) on the free blocks, the rest copied; *x_norm = |state| and *step_norm = |trial_out - state|
+ * over the free blocks; *projected_max_norm = max |state - clamp(Plus(state, -v))|.  CERES_HIP_E_INVALID on a handle that is not
+ * constrained (the kernels need the bounds on the device). */
+int ceres_hip_debug_bal_bounded_step(ceres_hip_bal* p, const double* state, const double* v, double t, double* trial_out,
+                                     double* x_norm, double* step_norm, double* projected_max_norm);
 /* ---- covariance (ceres::Covariance: include/ceres/covariance.h, internal/ceres/covariance_impl.cc; design/17_covariance.md) ----
  * Cov = (J^T J)^-1 with J the Evaluator's Jacobian of the reduced program at `state`: unscaled, no LM diagonal, loss-corrected when
  * apply_loss_function is set (CovarianceImpl evaluates it so, covariance_impl.cc:71); columns [free points | free cameras].  Computed in
