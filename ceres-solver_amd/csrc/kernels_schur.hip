@@ -240,6 +240,9 @@ __global__ __launch_bounds__(256) void dense_potrf_panel_kernel(double* __restri
       // The pivot chain is 16 dependent steps per sub-block, 128 per panel: sqrt and divide (long software sequences in fp64) are
       // replaced by ONE reciprocal square root per pivot — v_rsq_f64 refined by two Newton steps — and multiplications by it
       // (L_jj = d y, column j *= y, and the inverse below multiplies by the same y = 1 / L_jj): a few ulps from the divided form.
+      // L_jj itself takes one correction step from its exact residual, L += (d - L^2) y / 2 (two FMAs, off the chain: only lane j's
+      // diagonal entry waits for them): d y alone was up to 1.3 u off (measured at n = 1: |d - L^2| = 2.6 u d), which the two divisions by L_jj
+      // in the triangular solves double — at n = 1 the solve's residual stood at 1.56 n u (tests/test_gpu_dense_cholesky.py).
       bool ok = true;
       double ri[kSub];   // 1 / L[j][j]
 #pragma unroll
@@ -250,7 +253,7 @@ __global__ __launch_bounds__(256) void dense_potrf_panel_kernel(double* __restri
         y = y * (1.5 - 0.5 * d * y * y);
         y = y * (1.5 - 0.5 * d * y * y);
         ri[j] = y;
-        if (lane == j) row[j] = d * y;
+        if (lane == j) { const double l = d * y; row[j] = fma(fma(-l, l, d), 0.5 * y, l); }
         else if (lane > j) row[j] *= y;
 #pragma unroll
         for (int c = j + 1; c < kSub; ++c) {

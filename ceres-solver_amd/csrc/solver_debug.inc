@@ -128,6 +128,80 @@ int ceres_hip_op_dense_cholesky_solve(ceres_hip_solver* s, int32_t n, const doub
   return rc;
 }
 
+// The same factorisation with the factor itself returned and the memory around the matrix and the vector watched: both sit in the middle
+// of larger allocations whose guard bands (2 * 128 rows of n doubles on either side of the matrix, 256 doubles on either side of the
+// vector) are filled with the byte 0x5A (a finite double) before the first run and compared word by word after the last.
+int ceres_hip_op_dense_cholesky_factor(ceres_hip_solver* s, int32_t n, const double* A, const double* b, double* factor, double* x,
+                                       int32_t repeats, int32_t* failed, int64_t* guard_words_changed, int32_t* repeatable) {
+  if (!s || !A || !factor || (b && !x) || n < 1 || repeats < 1) return CERES_HIP_E_INVALID;
+  try {
+  HIP_TRY(s, hipSetDevice(s->opt.device));
+  hipStream_t st = s->stream;
+  const size_t nn = size_t(n) * size_t(n);
+  const size_t mat_guard = size_t(2) * 128 * size_t(n), vec_guard = 256;
+  const size_t mat_words = nn + 2 * mat_guard, vec_words = size_t(n) + 2 * vec_guard;
+  constexpr int kGuardByte = 0x5A;
+  double *dA0 = nullptr, *dbuf = nullptr, *dvec = nullptr;
+  int* dflag = nullptr;
+  auto cleanup = [&] {
+    if (dA0) (void)hipFree(dA0); if (dbuf) (void)hipFree(dbuf); if (dvec) (void)hipFree(dvec); if (dflag) (void)hipFree(dflag);
+  };
+  std::vector<double> previous;
+  if (repeats > 1) previous.resize(nn);
+  std::vector<uint64_t> guard(std::max(mat_guard, vec_guard));
+  int64_t changed = 0;
+  int same = 1, flag = 0;
+  auto run = [&]() -> int {
+    HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&dA0), nn * sizeof(double)));
+    HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&dbuf), mat_words * sizeof(double)));
+    HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&dvec), vec_words * sizeof(double)));
+    HIP_TRY(s, hipMalloc(reinterpret_cast<void**>(&dflag), sizeof(int)));
+    double* dA = dbuf + mat_guard;
+    double* dx = dvec + vec_guard;
+    HIP_TRY(s, hipMemsetAsync(dbuf, kGuardByte, mat_words * sizeof(double), st));
+    HIP_TRY(s, hipMemsetAsync(dvec, kGuardByte, vec_words * sizeof(double), st));
+    HIP_TRY(s, hipMemcpyAsync(dA0, A, nn * sizeof(double), hipMemcpyHostToDevice, st));
+    for (int r = 0; r < repeats; ++r) {   // in place: every repeat starts from a fresh copy of the matrix and of b
+      HIP_TRY(s, hipMemcpyAsync(dA, dA0, nn * sizeof(double), hipMemcpyDeviceToDevice, st));
+      if (b) HIP_TRY(s, hipMemcpyAsync(dx, b, size_t(n) * sizeof(double), hipMemcpyHostToDevice, st));
+      HIP_TRY(s, hipMemsetAsync(dflag, 0, sizeof(int), st));
+      HIP_TRY(s, LaunchDenseCholesky(dA, n, dflag, st));
+      int this_flag = 0;
+      HIP_TRY(s, hipMemcpyAsync(&this_flag, dflag, sizeof(int), hipMemcpyDeviceToHost, st));
+      HIP_TRY(s, hipStreamSynchronize(st));
+      if (b && !this_flag) HIP_TRY(s, LaunchDenseCholeskySolve(dA, n, dx, st));
+      if (r > 0) std::memcpy(previous.data(), factor, nn * sizeof(double));
+      HIP_TRY(s, hipMemcpyAsync(factor, dA, nn * sizeof(double), hipMemcpyDeviceToHost, st));
+      if (b) HIP_TRY(s, hipMemcpyAsync(x, dx, size_t(n) * sizeof(double), hipMemcpyDeviceToHost, st));
+      HIP_TRY(s, hipStreamSynchronize(st));
+      if (r > 0) {
+        if (this_flag != flag) same = 0;
+        for (size_t i = 0; i < size_t(n) && same; ++i)
+          if (std::memcmp(previous.data() + i * size_t(n), factor + i * size_t(n), (i + 1) * sizeof(double)) != 0) same = 0;
+      }
+      flag = this_flag;
+    }
+    uint64_t pattern;
+    std::memset(&pattern, kGuardByte, sizeof(pattern));
+    const double* bands[4] = {dbuf, dbuf + mat_guard + nn, dvec, dvec + vec_guard + size_t(n)};
+    const size_t words[4] = {mat_guard, mat_guard, vec_guard, vec_guard};
+    for (int k = 0; k < 4; ++k) {
+      HIP_TRY(s, hipMemcpyAsync(guard.data(), bands[k], words[k] * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+      HIP_TRY(s, hipStreamSynchronize(st));
+      for (size_t i = 0; i < words[k]; ++i) changed += guard[i] != pattern;
+    }
+    return 0;
+  };
+  const int rc = run();
+  cleanup();
+  if (rc != 0) return rc;
+  if (failed) *failed = flag;
+  if (guard_words_changed) *guard_words_changed = changed;
+  if (repeatable) *repeatable = same;
+  return 0;
+  } catch (...) { return CERES_HIP_E_INVALID; }   // (host buffers sized by the caller's n: no C++ exception crosses the C boundary)
+}
+
 int ceres_hip_debug_hybrid_plan(const ceres_hip_block_structure* bs, int32_t num_eliminate_blocks, int32_t groups, int32_t rows,
                                 int64_t counts[8], int32_t* slot_word, int32_t* slot_row, int32_t* tile_zbase, int32_t* grp_tile_ptr,
                                 int32_t* entry_row, int32_t* unit_cam, int32_t* unit_begin, int32_t* unit_end,

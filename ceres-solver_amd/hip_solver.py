@@ -162,6 +162,8 @@ ABI = [
                                        POINTER(c_int32), POINTER(c_int32), POINTER(c_int32), POINTER(c_uint32),
                                        POINTER(c_int32), POINTER(c_int32), c_int64, c_char_p, c_int32]),
     ("ceres_hip_op_dense_cholesky_solve", c_int32, [c_void_p, c_int32, _DP, _DP, _DP, c_int32, POINTER(c_double), POINTER(c_int32)]),
+    ("ceres_hip_op_dense_cholesky_factor", c_int32, [c_void_p, c_int32, _DP, _DP, _DP, _DP, c_int32, POINTER(c_int32), POINTER(c_int64),
+                                                     POINTER(c_int32)]),
     ("ceres_hip_debug_hybrid_plan", c_int32, [POINTER(CBlockStructure), c_int32, c_int32, c_int32, POINTER(c_int64)] + [POINTER(c_int32)] * 8 +
      [c_int64, c_int64, c_int64]),
     ("ceres_hip_debug_staged_x_plan", c_int32, [POINTER(CBlockStructure), c_int32, POINTER(c_int64), POINTER(c_int32), POINTER(c_int32), c_int64, c_int64]),
@@ -828,6 +830,25 @@ class HipLinearSolver:
         ms, failed = c_double(0.0), c_int32(0)
         self._check(self._lib.ceres_hip_op_dense_cholesky_solve(self._h, n, _p(A), _p(b), _p(x), repeats, byref(ms), byref(failed)))
         return x, float(ms.value), bool(failed.value)
+
+    def dense_cholesky_factor(self, A: np.ndarray, b: Optional[np.ndarray] = None, repeats: int = 1):
+        """The same factorisation, debug form (ceres_hip_op_dense_cholesky_factor): the matrix and the vector lie between guard bands
+        on the device.  Returns (the whole n x n array as the device left it: L in its lower triangle; x or None; failed; the number
+        of guard words that changed; whether every repeat left the same bits in the lower triangle)."""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        n = A.shape[0]
+        assert A.shape == (n, n)
+        factor = np.zeros((n, n))
+        x = None
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.float64)
+            assert b.shape == (n,)
+            x = np.zeros(n)
+        failed, changed, same = c_int32(0), c_int64(-1), c_int32(0)
+        self._check(self._lib.ceres_hip_op_dense_cholesky_factor(self._h, n, _p(A), _p(b) if b is not None else None, _p(factor),
+                                                                 _p(x) if x is not None else None, repeats, byref(failed), byref(changed),
+                                                                 byref(same)))
+        return factor, x, bool(failed.value), int(changed.value), bool(same.value)
 
     def time_op(self, op: int, iters: int = 20) -> float:
         """Average milliseconds per application (HIP events on the solver's stream)."""

@@ -941,6 +941,16 @@ int ceres_hip_debug_dogleg_subspace_minimum(const double* B, const double* g, do
  * its average duration (HIP events), *failed = 1 if a pivot was not positive (x is then b).  Needs only a created handle.          */
 int ceres_hip_op_dense_cholesky_solve(ceres_hip_solver* s, int32_t n, const double* A, const double* b, double* x, int32_t repeats,
                                       double* factor_ms, int32_t* failed);
+/* Debug: the same factorisation with the factor returned and the memory around it watched.  A as above; b (n doubles) may be NULL.
+ * The matrix and the vector sit in the middle of larger device allocations: a guard band of 2 * 128 * n doubles on either side of the
+ * matrix and of 256 doubles on either side of the vector, filled with the byte 0x5A before the first run.  Each of `repeats` runs
+ * starts from a fresh copy, factors on the handle's stream and, with b given and no pivot refused, solves.  factor (n * n doubles):
+ * the whole array as the last run left it (L in the lower triangle; above the diagonal whatever the kernels keep there); x (n doubles,
+ * required with b): the last run's solution, b itself if a pivot was refused; *failed: the last run's flag; *guard_words_changed: the
+ * guard words whose bits differ from the fill after the last run; *repeatable: 1 if every run left the same bits in the lower triangle
+ * (and the same flag).  The last three may be NULL.  Needs only a created handle. */
+int ceres_hip_op_dense_cholesky_factor(ceres_hip_solver* s, int32_t n, const double* A, const double* b, double* factor, double* x,
+                                       int32_t repeats, int32_t* failed, int64_t* guard_words_changed, int32_t* repeatable);
 
 /* Debug: the camera-accumulation plan for more cameras than LDS rows (csrc/plan.cc; pure host code).  With groups >= 2 and
  * num_eliminate_blocks > 0 this is the HYBRID plan a Schur solver builds for `groups` workgroups of `rows` LDS accumulator rows;

@@ -3,7 +3,7 @@
 With J = [E | F] (E: the first num_eliminate_blocks column blocks, each row holding at most one E cell) and M_e = E^T E + D_e^2, which is
 block diagonal with one block per eliminated column block:
 
-    S        = F^T F + D_f^2 - F^T E M_e^-1 E^T F                       (applied implicitly; dense only for num_cols_f <= 3000)
+    S        = F^T F + D_f^2 - F^T E M_e^-1 E^T F                       (applied implicitly; dense only for num_cols_f <= 3100)
     rhs      = F^T (b - E M_e^-1 E^T b)                                 (ImplicitSchurComplement::UpdateRhs)
     back-sub = [M_e^-1 E^T (b - F z) ; z]                               (ImplicitSchurComplement::BackSubstitute)
     B        = blockdiag(F^T F + D_f^2)                                 (JACOBI for ITERATIVE_SCHUR)
@@ -16,7 +16,7 @@ other two agree.
 """
 import numpy as np
 
-SCHUR_DENSE_MAX_COLS_F = 3000
+SCHUR_DENSE_MAX_COLS_F = 3100   # (343 cameras 9 wide, the smallest DENSE_SCHUR system with look-ahead: tests/test_gpu_dense_cholesky.py)
 IDENTITY, JACOBI, SCHUR_JACOBI, SCHUR_POWER_SERIES_EXPANSION = 0, 1, 2, 3
 SUCCESS, NO_CONVERGENCE, FAILURE = 0, 1, 2
 
