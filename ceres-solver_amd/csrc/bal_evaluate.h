@@ -8,18 +8,13 @@
 #include <type_traits>
 
 #include "device.h"
+#include "reduce.h"
 #include "robust_loss.h"
 #include "snavely.h"
 
 namespace chip {
 
 namespace {
-
-__device__ __forceinline__ double bal_eval_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // ROBUST: A.loss applies (robust_loss.h) — cost rho / 2, the Jacobian corrected with the uncorrected residual, then the residual; the
 // Jacobi column scaling comes after the correction.  !ROBUST: the squared loss, as this kernel was before losses existed.
@@ -101,10 +96,10 @@ __global__ __launch_bounds__(kVecBlock) void bal_evaluate_kernel(typename std::c
       for (int j = 0; j < CW; ++j) fo[j] = make_double2(jc[2 * j], jc[2 * j + 1]);
     }
   }
-  cost = bal_eval_wave_sum(cost);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = cost;
+  cost = wave_sum(cost);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = cost;   // (inline: wave_to_lds here renumbers the blocks of kernels_quaternion.hip)
   __syncthreads();
-  if (threadIdx.x == 0) A.partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  if (threadIdx.x == 0) A.partials[blockIdx.x] = lds_sum4(sh);
 }
 
 }  // namespace

@@ -34,9 +34,8 @@ struct ceres_hip_bal {
   int32_t* d_cm_pt = nullptr;
   double2* d_cm_obs = nullptr;
   double *d_x = nullptr, *d_cand = nullptr, *d_res = nullptr, *d_vals = nullptr, *d_step = nullptr, *d_delta = nullptr,
-         *d_scale = nullptr, *d_grad = nullptr, *d_parts = nullptr;
-  double* h_parts = nullptr;  // pinned, kBalParts doubles
-  int deferred_cost_parts = 0;  // an evaluation whose cost partials (d_parts[0 ..)) the next synchronising call collects
+         *d_scale = nullptr, *d_grad = nullptr;
+  PartialSums parts;            // every per-workgroup partial sum this file and its .inc files read back (partial_sums.h)
   LossParams loss;              // ceres_hip_bal_set_loss: applies to every observation (kLossNone: the squared loss)
   // ceres_hip_bal_set_inner_iterations (inner_iterations.inc): CERES_HIP_INNER_*, in force until set again; the lists it runs on; and
   // what the last ceres_hip_bal_minimize did with them (ceres_hip_bal_inner_iteration_stats)
@@ -46,9 +45,9 @@ struct ceres_hip_bal {
   int32_t inner_steps = 0, inner_groups_used = 0;
   double inner_seconds = 0.0;
   // ceres_hip_bal_set_trust_region_strategy (dogleg.inc): CERES_HIP_LEVENBERG_MARQUARDT / CERES_HIP_DOGLEG, in force until set again;
-  // the dogleg strategy's device vectors (a = gradient / diagonal, b = gn / diagonal) and partial sums, made on first use
+  // the dogleg strategy's device vectors (a = gradient / diagonal, b = gn / diagonal), made on first use
   int32_t tr_strategy = CERES_HIP_LEVENBERG_MARQUARDT, dogleg_type = CERES_HIP_TRADITIONAL_DOGLEG;
-  double *d_dl_a = nullptr, *d_dl_b = nullptr, *d_dl_parts = nullptr;
+  double *d_dl_a = nullptr, *d_dl_b = nullptr;
   // ceres_hip_bal_create_with_constant_blocks (constant_blocks.inc): nc, np and n_a stay the caller's (the state is full), `no` is the
   // number of KEPT rows, n_t the reduced tangent length.  Everything below is unset on a handle without constant blocks.
   bool has_const = false;
@@ -85,7 +84,8 @@ void bal_bounds_free(ceres_hip_bal* p);
 
 namespace {
 
-constexpr int kBalParts = 4096;
+// the stage's capacity, the largest round trip: an evaluator's cost set + seven vector sets (trial point 2 | 4, norms 2 | 0, dots 3)
+constexpr int kPartialSumsCapacity = kMaxEvalGrid + 7 * kMaxVecGrid;
 BalBounds bal_bounds_args(const ceres_hip_bal* p);   // (bounds.inc)
 double bal_bounds_step_size(const ceres_hip_bal* p);
 
@@ -99,16 +99,28 @@ int bal_fail(ceres_hip_bal* p, int code) {
     if (_rc != 0) return bal_fail(p, _rc);  \
   } while (0)
 
-// cost (and residuals / Jacobian values in the solver's layout) at a device state vector
-// defer: enqueue only — the cost partials stay in d_parts[0 .. deferred_cost_parts) and the next synchronising call of this file
-// (bal_gradient_max, bal_collect) copies them with its own: one host round trip instead of two
-int bal_evaluate_device(ceres_hip_bal* p, const double* d_state, bool jacobian, const double* d_scale, double* d_residuals,
-                        double* cost, bool defer = false) {
+// The handle's stage of partial sums (partial_sums.h).  A refusal is an error of the call, which abandons its round trip.
+int bal_parts_refused(ceres_hip_bal* p) { return fail(p->s, CERES_HIP_E_HIP, "%s", p->parts.refusal().c_str()); }
+int bal_parts_room(ceres_hip_bal* p, int max_doubles, double** at) {
+  *at = p->parts.room(max_doubles);
+  return *at ? 0 : bal_parts_refused(p);
+}
+int bal_parts_collect(ceres_hip_bal* p) {
+  if (!p->parts.error.empty()) return bal_parts_refused(p);
+  HIP_TRY(p->s, p->parts.collect(p->s->stream));
+  return 0;
+}
+// cost (and residuals / Jacobian values in the solver's layout) at a device state vector, enqueued: *cost is the set of its partial sums
+// (removed_rows: over the rows whose blocks are both constant instead — the fixed cost)
+int bal_evaluate_enqueue(ceres_hip_bal* p, const double* d_state, bool jacobian, const double* d_scale, double* d_residuals, PartialSet* cost,
+                         bool removed_rows = false) {
   ceres_hip_solver* s = p->s;
   BalEvalConstArgs A;
+  TRY(bal_parts_room(p, kMaxEvalGrid, &A.partials));
   A.n_rows = p->no; A.row_cam = p->d_row_cam; A.row_pt = p->d_row_pt; A.row_obs = p->d_row_obs;
+  if (removed_rows) { A.n_rows = p->n_removed; A.row_cam = p->d_rm_cam; A.row_pt = p->d_rm_pt; A.row_obs = p->d_rm_obs; }
   A.state = d_state; A.cam_base = 3 * int64_t(p->np); A.scale = d_scale;
-  A.residuals = d_residuals; A.values = jacobian ? p->d_vals : nullptr; A.partials = p->d_parts; A.loss = p->loss;
+  A.residuals = d_residuals; A.values = jacobian ? p->d_vals : nullptr; A.loss = p->loss;
   int nparts = 0;
   if (p->intrinsics_mask && jacobian) {   // fixed intrinsics: F cells of 2 x cw (the cost alone has no columns to remove)
     A.row_fpos = p->d_row_fpos; A.row_scam = p->d_row_scam; A.row_spt = p->d_row_spt;   // (uploaded with or without constant blocks)
@@ -119,12 +131,15 @@ int bal_evaluate_device(ceres_hip_bal* p, const double* d_state, bool jacobian, 
   } else {
     HIP_TRY(s, LaunchBalEvaluate(A, jacobian, &nparts, s->stream, p->camera_model));
   }
-  if (defer) { p->deferred_cost_parts = nparts; return 0; }
-  HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nparts, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  double c = 0;
-  for (int i = 0; i < nparts; ++i) c += p->h_parts[i];  // fixed order: deterministic
-  *cost = c;
+  *cost = p->parts.take(nparts);
+  return 0;
+}
+int bal_evaluate_device(ceres_hip_bal* p, const double* d_state, bool jacobian, const double* d_scale, double* d_residuals, double* cost,
+                        bool removed_rows = false) {
+  PartialSet c;
+  TRY(bal_evaluate_enqueue(p, d_state, jacobian, d_scale, d_residuals, &c, removed_rows));
+  TRY(bal_parts_collect(p));
+  *cost = p->parts.sum(c);
   return 0;
 }
 
@@ -170,15 +185,16 @@ void bal_set_camera_eval(ceres_hip_bal* p, bool on) {
 
 // Cost, residuals and the (scaled) Jacobian at a device state vector, the Jacobian written STRAIGHT INTO THE TILES (kernels_evaluator.hip):
 // afterwards the solver holds loaded, packed values — its first pass over J gathers nothing.  Of the caller layout only the F cells
-// exist (p->d_vals; the camera-major preconditioner pass reads them there).
-int bal_evaluate_into_tiles(ceres_hip_bal* p, const double* d_state, const double* d_scale, double* cost, int debug_flags = 0, bool defer = false) {
+// exist (p->d_vals; the camera-major preconditioner pass reads them there).  Enqueued, as bal_evaluate_enqueue.
+int bal_evaluate_into_tiles(ceres_hip_bal* p, const double* d_state, const double* d_scale, PartialSet* cost, int debug_flags = 0) {
   ceres_hip_solver* s = p->s;
   BalEvalTilesConstArgs T;
+  TRY(bal_parts_room(p, kMaxEvalGrid, &T.e.partials));
   T.debug_flags = debug_flags;
   T.e.n_rows = p->no; T.e.row_cam = p->d_row_cam; T.e.row_pt = p->d_row_pt; T.e.row_obs = p->d_row_obs;
   T.e.state = d_state; T.e.cam_base = 3 * int64_t(p->np); T.e.scale = d_scale;
   const bool cam_eval = debug_flags == 0 && bal_camera_pass_evaluates(p);
-  T.e.residuals = p->d_res; T.e.values = cam_eval ? nullptr : p->d_vals; T.e.partials = p->d_parts; T.e.loss = p->loss;
+  T.e.residuals = p->d_res; T.e.values = cam_eval ? nullptr : p->d_vals; T.e.loss = p->loss;
   T.n_tiles = s->plan.n_tiles; T.slot_bpos = s->d_slot_bpos; T.slot_fpos = s->d_slot_fpos;
   T.J_out = s->d_J; T.tile_pitch = s->ops->tile_pitch; T.b_out = s->d_bt;
   T.slot_cam = p->d_slot_cam; T.slot_pt = p->d_slot_pt; T.slot_obs = p->d_slot_obs; T.pt_pack = p->d_pt_pack; T.cam_pack = p->d_cam_pack;
@@ -190,87 +206,57 @@ int bal_evaluate_into_tiles(ceres_hip_bal* p, const double* d_state, const doubl
   else HIP_TRY(s, LaunchBalEvaluateTiles(T, p->np, p->nc, &nparts, s->stream));
   s->packed = true;
   s->tiles_only = true;   // (E cells are never written; F cells only for the camera-major pass that reads them)
-  if (defer) { p->deferred_cost_parts = nparts; return 0; }
-  HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nparts, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  double c = 0;
-  for (int i = 0; i < nparts; ++i) c += p->h_parts[i];  // fixed order: deterministic
-  *cost = c;
+  *cost = p->parts.take(nparts);
   return 0;
 }
 
-constexpr int kBalSecondParts = 2048;   // d_parts / h_parts: an evaluation's cost partials in [0, 2048), a second kernel's from here on
-static_assert(kMaxEvalGrid <= kBalSecondParts, "one cost partial per workgroup of the evaluators");
-
-// max |g_i / scale_i| — with quaternion-manifold cameras |x - Plus(x, -g)|_inf at the state d_x; deferred_cost != nullptr: also the cost of
-// the evaluation enqueued before (bal_evaluate_*(…, defer = true))
-int bal_gradient_max(ceres_hip_bal* p, const double* d_scale, const double* d_x, double* out, double* deferred_cost = nullptr) {
+// max |g_i / scale_i| — with quaternion-manifold cameras |x - Plus(x, -g)|_inf at the state d_x — enqueued: *out is the set of maxima
+int bal_gradient_max(ceres_hip_bal* p, const double* d_scale, const double* d_x, PartialSet* out) {
   ceres_hip_solver* s = p->s;
-  int nparts = 0;
-  static_assert(kMaxVecGrid <= kBalParts - kBalSecondParts, "room for the second kernel's partials");
+  int nparts = 0; double* parts = nullptr;
+  TRY(bal_parts_room(p, kMaxVecGrid, &parts));
   if (p->is_constrained)   // |x - clamp(x - g)|_inf over the free blocks (I/trust_region_minimizer.cc:281-302)
-    HIP_TRY(s, LaunchBoundsGradientMax(bal_bounds_args(p), d_x, p->d_grad, d_scale, p->d_parts + kBalSecondParts, &nparts, s->stream));
+    HIP_TRY(s, LaunchBoundsGradientMax(bal_bounds_args(p), d_x, p->d_grad, d_scale, parts, &nparts, s->stream));
   else if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD && p->has_const)
-    HIP_TRY(s, LaunchBalGradientMaxQuatFree(BalFreeBlocks{p->d_free_block, p->nfp, p->nfc}, p->d_grad, d_scale, d_x, p->d_parts + kBalSecondParts, &nparts,
-                                            s->stream));
+    HIP_TRY(s, LaunchBalGradientMaxQuatFree(BalFreeBlocks{p->d_free_block, p->nfp, p->nfc}, p->d_grad, d_scale, d_x, parts, &nparts, s->stream));
   else if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD)
-    HIP_TRY(s, LaunchBalGradientMaxQuat(p->d_grad, d_scale, d_x, p->np, p->nc, p->d_parts + kBalSecondParts, &nparts, s->stream));
+    HIP_TRY(s, LaunchBalGradientMaxQuat(p->d_grad, d_scale, d_x, p->np, p->nc, parts, &nparts, s->stream));
   else
-    HIP_TRY(s, LaunchBalGradientMax(p->d_grad, d_scale, p->n_t, p->d_parts + kBalSecondParts, &nparts, s->stream));
-  const int nc = deferred_cost ? p->deferred_cost_parts : 0;
-  if (nc > 0) HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nc, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipMemcpyAsync(p->h_parts + kBalSecondParts, p->d_parts + kBalSecondParts, sizeof(double) * nparts, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  double m = 0;
-  for (int i = 0; i < nparts; ++i) m = std::max(m, p->h_parts[kBalSecondParts + i]);
-  *out = m;
-  if (deferred_cost) {
-    double c = 0;
-    for (int i = 0; i < nc; ++i) c += p->h_parts[i];  // fixed order: deterministic
-    *deferred_cost = c;
-    p->deferred_cost_parts = 0;
-  }
+    HIP_TRY(s, LaunchBalGradientMax(p->d_grad, d_scale, p->n_t, parts, &nparts, s->stream));
+  *out = p->parts.take(nparts);
   return 0;
 }
 
-// delta = step .* scale, cand = Plus(x, delta); |x|^2 partials at parts[0 ..), |delta|^2 at parts[*nparts ..)
+// delta = step .* scale, cand = Plus(x, delta), enqueued; the sets of |x|^2 and |delta|^2
 // (a constrained handle: delta = a (step .* scale) with the projected search's step size a, cand = clamp(x + delta), and the second
-// sum is |cand - x|^2, Ceres' ambient step norm; two more sets follow, unused here)
-int bal_candidate(ceres_hip_bal* p, const double* x, const double* scale, double* cand, double* parts, int* nparts) {
+// sum is |cand - x|^2, Ceres' ambient step norm; the kernel's two further sets are taken and not read)
+int bal_candidate(ceres_hip_bal* p, const double* x, const double* scale, double* cand, PartialSet* x_norm2, PartialSet* delta_norm2) {
   ceres_hip_solver* s = p->s;
+  int n = 0; double* parts = nullptr;
+  TRY(bal_parts_room(p, (p->is_constrained ? 4 : 2) * kMaxVecGrid, &parts));
   if (p->is_constrained)
     HIP_TRY(s, LaunchBoundsTrialPoint(bal_bounds_args(p), x, p->d_step, scale, nullptr, bal_bounds_step_size(p), true, p->d_delta, cand, parts,
-                                      nparts, s->stream));
+                                      &n, s->stream));
   else if (p->intrinsics_mask)   // (fixed intrinsics: a narrower step scattered into the free coordinates, with or without constant blocks)
     HIP_TRY(s, LaunchBalCandidateSubset(BalFreeBlocks{p->has_const ? p->d_free_block : nullptr, p->nfp, p->nfc}, p->intrinsics_mask, p->np, x,
-                                        p->d_step, scale, p->d_delta, cand, parts, nparts, s->stream));
+                                        p->d_step, scale, p->d_delta, cand, parts, &n, s->stream));
   else if (p->has_const)   // (Plus scattered into the free blocks; cand's constant blocks hold the state's values already: ceres_hip_bal_minimize)
     HIP_TRY(s, LaunchBalCandidateFree(BalFreeBlocks{p->d_free_block, p->nfp, p->nfc}, p->camera_model, x, p->d_step, scale, p->d_delta, cand, parts,
-                                      nparts, s->stream));
+                                      &n, s->stream));
   else if (p->camera_model == CERES_HIP_CAMERA_QUATERNION_MANIFOLD)
-    HIP_TRY(s, LaunchBalCandidateQuat(x, p->d_step, scale, p->d_delta, cand, p->np, p->nc, parts, nparts, s->stream));
+    HIP_TRY(s, LaunchBalCandidateQuat(x, p->d_step, scale, p->d_delta, cand, p->np, p->nc, parts, &n, s->stream));
   else   // (the angle-axis and the Euclidean quaternion camera: Plus is x + delta)
-    HIP_TRY(s, LaunchBalCandidate(x, p->d_step, scale, p->d_delta, cand, p->n_a, parts, nparts, s->stream));
+    HIP_TRY(s, LaunchBalCandidate(x, p->d_step, scale, p->d_delta, cand, p->n_a, parts, &n, s->stream));
+  *x_norm2 = p->parts.take(n); *delta_norm2 = p->parts.take(n);
+  if (p->is_constrained) { p->parts.take(n); p->parts.take(n); }
   return 0;
 }
 
 // Solver::Summary::fixed_cost at a device state vector: the cost-only evaluator over the removed rows (both blocks constant), its
 // partial sums added in their fixed order
 int bal_fixed_cost_device(ceres_hip_bal* p, const double* d_state, double* cost) {
-  ceres_hip_solver* s = p->s;
   *cost = 0.0;
-  if (p->n_removed == 0) return 0;
-  BalEvalArgs A;
-  A.n_rows = p->n_removed; A.row_cam = p->d_rm_cam; A.row_pt = p->d_rm_pt; A.row_obs = p->d_rm_obs;
-  A.state = d_state; A.cam_base = 3 * int64_t(p->np); A.partials = p->d_parts; A.loss = p->loss;
-  int nparts = 0;
-  HIP_TRY(s, LaunchBalEvaluate(A, false, &nparts, s->stream, p->camera_model));
-  HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nparts, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  double c = 0;
-  for (int i = 0; i < nparts; ++i) c += p->h_parts[i];
-  *cost = c;
-  return 0;
+  return p->n_removed == 0 ? 0 : bal_evaluate_device(p, d_state, false, nullptr, nullptr, cost, true);
 }
 
 double seconds_since(std::chrono::steady_clock::time_point t0) {
@@ -311,7 +297,7 @@ ceres_hip_solver* ceres_hip_bal_linear_solver(ceres_hip_bal* p) { return p ? p->
 
 void ceres_hip_bal_destroy(ceres_hip_bal* p) {
   if (!p) return;
-  if (p->h_parts) (void)hipHostFree(p->h_parts);
+  if (p->parts.pinned) (void)hipHostFree(p->parts.pinned);
   bal_inner_free(p);
   bal_ls_free(p);
   bal_cov_free(p);
@@ -452,7 +438,7 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
        dev_alloc(s, &p->d_step, size_t(p->n_t)) == 0 && dev_alloc(s, &p->d_delta, size_t(p->n_t)) == 0 &&
        dev_alloc(s, &p->d_scale, size_t(p->n_t)) == 0 && dev_alloc(s, &p->d_grad, size_t(p->n_t)) == 0 &&
        dev_alloc(s, &p->d_res, size_t(2 * no)) == 0 && dev_alloc(s, &p->d_vals, size_t(nvals)) == 0 &&
-       dev_alloc(s, &p->d_parts, size_t(kBalParts)) == 0;
+       dev_alloc(s, &p->parts.device, size_t(kPartialSumsCapacity)) == 0;
   if (ok && has_const) {   // the reduced program's maps, the removed rows, the caller's observations (the inner iterations' lists)
     p->cam_col = R.camera_column; p->pt_col = R.point_column;
     p->all_cam.assign(camera_index, camera_index + num_observations);
@@ -526,8 +512,9 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
     }
   }
   if (!ok) return bail((name + ": device allocation").c_str());
-  if (hipHostMalloc(reinterpret_cast<void**>(&p->h_parts), sizeof(double) * kBalParts) != hipSuccess)
+  if (hipHostMalloc(reinterpret_cast<void**>(&p->parts.pinned), sizeof(double) * kPartialSumsCapacity) != hipSuccess)
     return bail((name + ": pinned allocation").c_str());
+  p->parts.capacity = kPartialSumsCapacity;
   return p;
 } catch (const std::exception& ex) {
   g_create_error = std::string(fn) + ": " + ex.what();
@@ -690,17 +677,19 @@ int ceres_hip_debug_bal_evaluate_tiles_timing(ceres_hip_bal* p, const double* st
   if (!bal_writes_tiles(p)) return fail(s, CERES_HIP_E_UNSUPPORTED, "the evaluator does not write this structure's tiles");
   if (p->has_const && flags != 0) return fail(s, CERES_HIP_E_UNSUPPORTED, "the store experiments are not built for handles with constant cameras");
   BAL_TRY(p, up(s, p->d_x, state, size_t(p->n_a)));
-  double cost = 0;
+  PartialSet cost;
   hipEvent_t e0, e1;
   HIP_TRY(s, hipEventCreate(&e0));
   HIP_TRY(s, hipEventCreate(&e1));
   int rc = 0;
-  for (int w = 0; w < 2 && !rc; ++w) rc = bal_evaluate_into_tiles(p, p->d_x, nullptr, &cost, flags);
+  for (int w = 0; w < 2 && !rc; ++w)
+    if ((rc = bal_evaluate_into_tiles(p, p->d_x, nullptr, &cost, flags)) == 0) rc = bal_parts_collect(p);
   float ms = 0;
+  BalEvalTilesConstArgs T;   // (the launches alone: every one writes the same partial sums, which nobody takes; no synchronisation in between)
+  if (!rc) rc = bal_parts_room(p, kMaxEvalGrid, &T.e.partials);
   if (!rc) {
-    BalEvalTilesConstArgs T;   // (the launches alone: no copy of the partial sums, no synchronisation in between)
     T.debug_flags = flags;
-    T.e.n_rows = p->no; T.e.state = p->d_x; T.e.cam_base = 3 * int64_t(p->np); T.e.residuals = p->d_res; T.e.values = p->d_vals; T.e.partials = p->d_parts;
+    T.e.n_rows = p->no; T.e.state = p->d_x; T.e.cam_base = 3 * int64_t(p->np); T.e.residuals = p->d_res; T.e.values = p->d_vals;
     T.e.loss = p->loss;   // (what ceres_hip_bal_minimize runs)
     T.n_tiles = s->plan.n_tiles; T.slot_bpos = s->d_slot_bpos; T.slot_fpos = s->d_slot_fpos;
     T.J_out = s->d_J; T.tile_pitch = s->ops->tile_pitch; T.b_out = s->d_bt;
@@ -811,13 +800,13 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
   // EvaluateGradientAndJacobian, I/trust_region_minimizer.cc:246-314.  The Jacobian is written
   // already scaled; the gradient of the unscaled problem is recovered from (J S)^T f = S J^T f.
   const bool into_tiles = bal_writes_tiles(p);
+  PartialSet x_cost_parts;
   auto eval_values = [&](const double* sc, bool for_column_norms = false) -> int {   // J (scaled by sc) and f at x, loaded into the solver
     // (with the cameras' sums outside LDS the column norms come from the generic kernel, which reads the caller layout: that one
     // evaluation — the first of a run — keeps the two-pass form)
-    // (the cost is collected with the gradient's maximum, one host round trip for both: defer; the cost of the unscaled evaluation
-    // that only feeds the column norms is never collected)
-    if (into_tiles && !(for_column_norms && !s->lds_mode)) return bal_evaluate_into_tiles(p, x, sc, &x_cost, 0, true);
-    TRY(bal_evaluate_device(p, x, true, sc, p->d_res, &x_cost, true));
+    // (enqueued only: the cost is collected with the gradient's maximum, one host round trip for both)
+    if (into_tiles && !(for_column_norms && !s->lds_mode)) return bal_evaluate_into_tiles(p, x, sc, &x_cost_parts);
+    TRY(bal_evaluate_enqueue(p, x, true, sc, p->d_res, &x_cost_parts));
     bal_set_camera_eval(p, false);
     return load_device(s, p->d_vals, p->d_res, nullptr);
   };
@@ -825,12 +814,16 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
     const auto t0 = std::chrono::steady_clock::now();
     if (o->jacobi_scaling && iteration == 0) {  // scale = 1 / (1 + sqrt(SquaredColumnNorm(J))) of the first Jacobian
       TRY(eval_values(nullptr, true));
+      p->parts.drop();   // (the cost of the unscaled evaluation that only feeds the column norms is never read)
       TRY(op_squared_column_norm(s, p->d_grad));
       HIP_TRY(s, LaunchBalJacobiScale(p->d_grad, p->d_scale, p->n_t, st));
     }
     TRY(eval_values(scale));
     TRY(op_jtb(s, p->d_grad));
-    TRY(bal_gradient_max(p, scale, x, &grad_max, &x_cost));
+    PartialSet grad_max_parts;
+    TRY(bal_gradient_max(p, scale, x, &grad_max_parts));
+    TRY(bal_parts_collect(p));
+    grad_max = p->parts.max(grad_max_parts); x_cost = p->parts.sum(x_cost_parts);
     S->evaluation_seconds += seconds_since(t0);
     return 0;
   };
@@ -898,33 +891,26 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
     // delta = step .* scale; candidate = Plus(x, delta); |x|, |delta|; the candidate's cost — two kernels, ONE host round trip
     // (inner iterations set: |x - candidate| too, a third kernel in the same round trip — Ceres' step norm, whether or not an inner
     // pass follows: ParameterToleranceReached, I/trust_region_minimizer.cc:726-748)
-    int nparts = 0, ndiff = 0;
     double xn = 0, dn = 0, cand_cost = 0;
-    constexpr int kDiffParts = kBalSecondParts + 2 * kMaxVecGrid;
-    static_assert(kDiffParts + kMaxVecGrid <= kBalParts, "room for the |x - candidate|^2 partials");
-    auto collect_diff = [&](int nd) {
-      double d = 0;
-      for (int i = 0; i < nd; ++i) d += p->h_parts[kDiffParts + i];
-      return d;
+    PartialSet xn_parts, dn_parts, diff_parts, cost_parts;
+    auto diff_norm = [&](PartialSet* out) -> int {   // |x - candidate|^2, enqueued
+      int nd = 0; double* parts = nullptr;
+      TRY(bal_parts_room(p, kMaxVecGrid, &parts));
+      HIP_TRY(s, LaunchBalDiffNorm(x, cand, n, parts, &nd, st));
+      *out = p->parts.take(nd);
+      return 0;
     };
     {
       // DoLineSearch (I/trust_region_minimizer.cc:103-108): the projected Armijo search scales delta; the candidate below is
       // clamp(x + a delta), its cost the loop's own evaluator's
       if (p->is_constrained) BAL_TRY(p, bal_bounds_line_search(p, x, scale, cand, x_cost));
       const auto te = std::chrono::steady_clock::now();
-      static_assert(2 * kMaxVecGrid <= kBalParts - kBalSecondParts, "room for |x|^2 and |delta|^2 partials");
-      BAL_TRY(p, bal_candidate(p, x, scale, cand, p->d_parts + kBalSecondParts, &nparts));
-      if (inner_set) HIP_TRY(s, LaunchBalDiffNorm(x, cand, n, p->d_parts + kDiffParts, &ndiff, st));
-      BAL_TRY(p, bal_evaluate_device(p, cand, false, nullptr, nullptr, &cand_cost, true));
-      const int nc = p->deferred_cost_parts;
-      HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
-      HIP_TRY(s, hipMemcpyAsync(p->h_parts + kBalSecondParts, p->d_parts + kBalSecondParts, sizeof(double) * 2 * nparts, hipMemcpyDeviceToHost, st));
-      if (inner_set) HIP_TRY(s, hipMemcpyAsync(p->h_parts + kDiffParts, p->d_parts + kDiffParts, sizeof(double) * ndiff, hipMemcpyDeviceToHost, st));
-      HIP_TRY(s, hipStreamSynchronize(st));
-      for (int i = 0; i < nparts; ++i) { xn += p->h_parts[kBalSecondParts + i]; dn += p->h_parts[kBalSecondParts + nparts + i]; }
-      for (int i = 0; i < nc; ++i) cand_cost += p->h_parts[i];
-      if (inner_set) dn = collect_diff(ndiff);
-      p->deferred_cost_parts = 0;
+      BAL_TRY(p, bal_candidate(p, x, scale, cand, &xn_parts, &dn_parts));
+      if (inner_set) BAL_TRY(p, diff_norm(&diff_parts));
+      BAL_TRY(p, bal_evaluate_enqueue(p, cand, false, nullptr, nullptr, &cost_parts));
+      BAL_TRY(p, bal_parts_collect(p));
+      xn = p->parts.sum(xn_parts); dn = p->parts.sum(inner_set ? diff_parts : dn_parts);
+      cand_cost = p->parts.sum(cost_parts);
       S->evaluation_seconds += seconds_since(te);
     }
     // DoInnerIterationsIfNeeded, I/trust_region_minimizer.cc:509-587: one coordinate-descent pass from the candidate, which always
@@ -936,22 +922,19 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
       ++p->inner_steps;
       double inner_cost = 0;
       BAL_TRY(p, bal_inner_pass(p, cand));
-      HIP_TRY(s, LaunchBalDiffNorm(x, cand, n, p->d_parts + kDiffParts, &ndiff, st));
-      BAL_TRY(p, bal_evaluate_device(p, cand, false, nullptr, nullptr, &inner_cost, true));
-      const int nc = p->deferred_cost_parts;
-      HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
-      HIP_TRY(s, hipMemcpyAsync(p->h_parts + kDiffParts, p->d_parts + kDiffParts, sizeof(double) * ndiff, hipMemcpyDeviceToHost, st));
-      HIP_TRY(s, hipStreamSynchronize(st));
-      for (int i = 0; i < nc; ++i) inner_cost += p->h_parts[i];
-      p->deferred_cost_parts = 0;
+      BAL_TRY(p, diff_norm(&diff_parts));
+      BAL_TRY(p, bal_evaluate_enqueue(p, cand, false, nullptr, nullptr, &cost_parts));
+      BAL_TRY(p, bal_parts_collect(p));
+      inner_cost = p->parts.sum(cost_parts);
       if (std::isfinite(inner_cost)) {
-        dn = collect_diff(ndiff);
+        dn = p->parts.sum(diff_parts);
         model_cost_change += cand_cost - inner_cost;
         inner_useful = inner_cost < std::min(x_cost, cand_cost);
         inner_enabled = 1.0 - inner_cost / cand_cost > p->inner_tolerance;
         cand_cost = inner_cost;
       } else {   // (the evaluation failed: Ceres keeps the candidate as it was — rebuilt here from x and the step)
-        BAL_TRY(p, bal_candidate(p, x, scale, cand, p->d_parts + kBalSecondParts, &nparts));
+        BAL_TRY(p, bal_candidate(p, x, scale, cand, &xn_parts, &dn_parts));
+        p->parts.drop();   // (its sums were read above)
       }
       p->inner_seconds += seconds_since(ti);
     }

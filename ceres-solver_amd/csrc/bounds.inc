@@ -45,9 +45,6 @@ void bal_bounds_free(ceres_hip_bal* p) {
 
 namespace {
 
-constexpr int kBoundsTrial = kLsCostParts, kBoundsDots = kLsCostParts + 4 * kMaxVecGrid;   // in BalLineSearch::d_parts / h_parts
-static_assert(kBoundsDots + 3 * kMaxVecGrid <= kLsParts, "room for the trial point's four sets and ls_dots_kernel's three");
-
 // the kernels' view of the bounds: the plain form where every block is free, else the loop's free-block list
 BalBounds bal_bounds_args(const ceres_hip_bal* p) {
   BalBounds K;
@@ -111,10 +108,9 @@ int bal_bounds_line_search(ceres_hip_bal* p, const double* x, const double* scal
   ceres_hip_solver* s = p->s;
   hipStream_t st = s->stream;
   BalBoundsState* b = p->bounds;
-  BalLineSearch* ls = p->ls;
+  PartialSums& P = p->parts;
   const auto t0 = std::chrono::steady_clock::now();
   const BalBounds K = bal_bounds_args(p);
-  double *hp = ls->h_parts, *dp = ls->d_parts;
   LsSearchOptions so = b->search;
   const bool cubic = so.interpolation_type == CERES_HIP_CUBIC;
   bool first = true;
@@ -125,29 +121,25 @@ int bal_bounds_line_search(ceres_hip_bal* p, const double* x, const double* scal
   auto sample = [&](double a, bool want_gradient, LsSample* out) -> int {
     *out = LsSample();
     out->x = a;
-    int ntp = 0, nc = 0, nd = 0;
-    HIP_TRY(s, LaunchBoundsTrialPoint(K, x, p->d_step, scale, first ? p->d_grad : nullptr, a, false, p->d_delta, cand, dp + kBoundsTrial, &ntp, st));
-    TRY(bal_ls_evaluate_enqueue(p, cand, want_gradient ? b->d_ls_grad : nullptr, &nc));
-    if (want_gradient) HIP_TRY(s, LaunchLsDots(p->d_delta, b->d_ls_grad, nullptr, p->n_t, dp + kBoundsDots, &nd, st));
-    HIP_TRY(s, hipMemcpyAsync(hp, dp, sizeof(double) * nc, hipMemcpyDeviceToHost, st));
-    if (first) HIP_TRY(s, hipMemcpyAsync(hp + kBoundsTrial, dp + kBoundsTrial, sizeof(double) * 4 * ntp, hipMemcpyDeviceToHost, st));
-    if (want_gradient) HIP_TRY(s, hipMemcpyAsync(hp + kBoundsDots, dp + kBoundsDots, sizeof(double) * nd, hipMemcpyDeviceToHost, st));
-    HIP_TRY(s, hipStreamSynchronize(st));
-    double v = 0;
-    for (int i = 0; i < nc; ++i) v += hp[i];   // fixed order
-    out->value = v;
-    out->value_is_valid = std::isfinite(v);
+    int ntp = 0; double* parts = nullptr;
+    PartialSet cost, delta_max, grad_delta, dg, unused;
+    TRY(bal_parts_room(p, 4 * kMaxVecGrid, &parts));
+    HIP_TRY(s, LaunchBoundsTrialPoint(K, x, p->d_step, scale, first ? p->d_grad : nullptr, a, false, p->d_delta, cand, parts, &ntp, st));
+    P.take(ntp); P.take(ntp);   // (|x|^2 and |cand - x|^2: the loop reads its own candidate's)
+    delta_max = P.take(ntp); grad_delta = P.take(ntp);
+    TRY(bal_ls_evaluate_enqueue(p, cand, want_gradient ? b->d_ls_grad : nullptr, &cost));
+    if (want_gradient) TRY(bal_ls_dots_enqueue(p, p->d_delta, b->d_ls_grad, nullptr, &dg, &unused, &unused));
+    TRY(bal_parts_collect(p));
+    out->value = P.sum(cost);
+    out->value_is_valid = std::isfinite(out->value);
     out->vector_x_is_valid = true;
     if (first) {
-      double gd = 0, dm = 0;
-      for (int i = 0; i < ntp; ++i) { dm = std::max(dm, hp[kBoundsTrial + 2 * ntp + i]); gd += hp[kBoundsTrial + 3 * ntp + i]; }
-      initial.gradient = gd;
-      so.direction_max_norm = dm;
+      initial.gradient = P.sum(grad_delta);
+      so.direction_max_norm = P.max(delta_max);
       first = false;
     }
     if (!out->value_is_valid || !want_gradient) return 0;
-    double g = 0;
-    for (int i = 0; i < nd; ++i) g += hp[kBoundsDots + i];
+    const double g = P.sum(dg);
     out->gradient = g;
     if (std::isfinite(g)) { out->gradient_is_valid = true; out->vector_gradient_is_valid = true; }
     return 0;
@@ -238,7 +230,7 @@ int ceres_hip_bal_set_bounds(ceres_hip_bal* p, const double* lower, const double
   }
   if (constrained) {
     HIP_TRY(s, hipSetDevice(s->opt.device));
-    BAL_TRY(p, bal_ls_prepare(p));   // the samples' evaluator (bal_ls_evaluate_enqueue) and its partial sums
+    BAL_TRY(p, bal_ls_prepare(p));   // the samples' evaluator (bal_ls_evaluate_enqueue)
     if (!p->bounds) {
       std::unique_ptr<BalBoundsState> b(new BalBoundsState);
       b->reset_stats();
@@ -330,16 +322,18 @@ int ceres_hip_debug_bal_bounded_step(ceres_hip_bal* p, const double* state, cons
   BAL_TRY(p, up(s, p->d_step, v, size_t(p->n_t)));
   HIP_TRY(s, hipMemcpyAsync(p->d_cand, p->d_x, sizeof(double) * p->n_a, hipMemcpyDeviceToDevice, st));   // (constant blocks: copied)
   const BalBounds K = bal_bounds_args(p);
-  int nt = 0, ng = 0;
-  static_assert(5 * kMaxVecGrid <= kBalParts, "room for the trial point's four sets and the projected gradient's one");
-  HIP_TRY(s, LaunchBoundsTrialPoint(K, p->d_x, p->d_step, nullptr, nullptr, t, false, p->d_delta, p->d_cand, p->d_parts, &nt, st));
-  HIP_TRY(s, LaunchBoundsGradientMax(K, p->d_x, p->d_step, nullptr, p->d_parts + 4 * kMaxVecGrid, &ng, st));
-  HIP_TRY(s, hipMemcpyAsync(p->h_parts, p->d_parts, sizeof(double) * 5 * kMaxVecGrid, hipMemcpyDeviceToHost, st));
-  BAL_TRY(p, down(s, trial_out, p->d_cand, size_t(p->n_a)));
-  double xn = 0, sn = 0, m = 0;
-  for (int i = 0; i < nt; ++i) { xn += p->h_parts[i]; sn += p->h_parts[nt + i]; }
-  for (int i = 0; i < ng; ++i) m = std::max(m, p->h_parts[4 * kMaxVecGrid + i]);
-  *x_norm = std::sqrt(xn); *step_norm = std::sqrt(sn); *projected_max_norm = m;
+  PartialSums& P = p->parts;
+  int nt = 0, ng = 0; double* parts = nullptr;
+  BAL_TRY(p, bal_parts_room(p, 4 * kMaxVecGrid, &parts));
+  HIP_TRY(s, LaunchBoundsTrialPoint(K, p->d_x, p->d_step, nullptr, nullptr, t, false, p->d_delta, p->d_cand, parts, &nt, st));
+  const PartialSet xn = P.take(nt), sn = P.take(nt);
+  P.take(nt); P.take(nt);   // (max |delta| and g . delta: not asked for)
+  BAL_TRY(p, bal_parts_room(p, kMaxVecGrid, &parts));
+  HIP_TRY(s, LaunchBoundsGradientMax(K, p->d_x, p->d_step, nullptr, parts, &ng, st));
+  const PartialSet m = P.take(ng);
+  HIP_TRY(s, hipMemcpyAsync(trial_out, p->d_cand, sizeof(double) * p->n_a, hipMemcpyDeviceToHost, st));   // (waited for by the collect)
+  BAL_TRY(p, bal_parts_collect(p));
+  *x_norm = std::sqrt(P.sum(xn)); *step_norm = std::sqrt(P.sum(sn)); *projected_max_norm = P.max(m);
   return 0;
 }
 

@@ -243,15 +243,18 @@ int dogleg_step(ceres_hip_bal* p, DoglegState& st, const ceres_hip_minimizer_opt
     if (lr->linear_solver.termination_type == CERES_HIP_FAILURE) return 0;
     // the strategy's vectors and the pass over J; s->lm_diag holds the clamped column norms lm_step_loaded formed
     int n3 = 0, n5 = 0;
-    double* parts = p->d_dl_parts;
+    double* parts = nullptr;   // (both kernels interleave their scalars: three, then five to a workgroup)
+    TRY(bal_parts_room(p, 3 * kDoglegGrid, &parts));
     HIP_TRY(s, LaunchDoglegPrep(s->lm_diag, p->d_grad, p->d_dl_b, p->d_dl_a, p->n_t, parts, &n3, stream));
-    HIP_TRY(s, LaunchJacobianGram(s->G, s->values, p->d_dl_a, p->d_dl_b, s->b, parts + 3 * kDoglegGrid, &n5, stream));
-    HIP_TRY(s, hipMemcpyAsync(p->h_parts, parts, sizeof(double) * 3 * n3, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(s, hipMemcpyAsync(p->h_parts + 3 * kDoglegGrid, parts + 3 * kDoglegGrid, sizeof(double) * 5 * n5, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(s, hipStreamSynchronize(stream));
+    const PartialSet set3 = p->parts.take(3 * n3);
+    TRY(bal_parts_room(p, 5 * kDoglegGrid, &parts));
+    HIP_TRY(s, LaunchJacobianGram(s->G, s->values, p->d_dl_a, p->d_dl_b, s->b, parts, &n5, stream));
+    const PartialSet set5 = p->parts.take(5 * n5);
+    TRY(bal_parts_collect(p));
+    const double *h3 = p->parts.host(set3), *h5 = p->parts.host(set5);
     double v3[3] = {0, 0, 0}, v5[5] = {0, 0, 0, 0, 0};
-    for (int q = 0; q < n3; ++q) for (int k = 0; k < 3; ++k) v3[k] += p->h_parts[3 * q + k];   // fixed order: deterministic
-    for (int q = 0; q < n5; ++q) for (int k = 0; k < 5; ++k) v5[k] += p->h_parts[3 * kDoglegGrid + 5 * q + k];
+    for (int q = 0; q < n3; ++q) for (int k = 0; k < 3; ++k) v3[k] += h3[3 * q + k];   // fixed order: deterministic
+    for (int q = 0; q < n5; ++q) for (int k = 0; k < 5; ++k) v5[k] += h5[5 * q + k];
     st.gg = v3[0]; st.ggn = v3[1]; st.nn = v3[2];
     st.jaa = v5[0]; st.jab = v5[1]; st.jbb = v5[2]; st.jaf = v5[3]; st.jbf = v5[4];
     st.alpha = st.gg / st.jaa;   // ComputeCauchyPoint, :185-199
@@ -275,7 +278,7 @@ int dogleg_step(ceres_hip_bal* p, DoglegState& st, const ceres_hip_minimizer_opt
 int dogleg_alloc(ceres_hip_bal* p) {
   if (p->d_dl_a) return 0;
   ceres_hip_solver* s = p->s;
-  if (dev_alloc(s, &p->d_dl_a, size_t(p->n_t)) || dev_alloc(s, &p->d_dl_b, size_t(p->n_t)) || dev_alloc(s, &p->d_dl_parts, size_t(8) * kDoglegGrid)) {
+  if (dev_alloc(s, &p->d_dl_a, size_t(p->n_t)) || dev_alloc(s, &p->d_dl_b, size_t(p->n_t))) {
     p->d_dl_a = nullptr;
     return CERES_HIP_E_HIP;
   }
@@ -283,8 +286,6 @@ int dogleg_alloc(ceres_hip_bal* p) {
 }
 
 }  // namespace
-
-static_assert(8 * kDoglegGrid <= kBalParts, "the dogleg pass's partial sums come back through h_parts");
 
 extern "C" {
 

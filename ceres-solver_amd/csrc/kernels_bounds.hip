@@ -13,28 +13,13 @@
 #include <hip/hip_runtime.h>
 
 #include "device.h"
+#include "reduce.h"
 
 #pragma clang fp contract(off)
 
 namespace chip {
 
 namespace {
-
-__device__ __forceinline__ double wave_sum_b(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max_b(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-  return v;
-}
-__device__ __forceinline__ unsigned wave_sum_u(unsigned v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // std::max(v, lower) then std::min(., upper), as ParameterBlock::Plus writes them (a NaN passes through; no bound: -inf / +inf)
 __device__ __forceinline__ double clamp_b(double v, double lo, double hi) {
@@ -74,8 +59,8 @@ __global__ __launch_bounds__(kVecBlock) void bounds_project_kernel(BalFreeBlocks
     const double v = x[a], c = clamp_b(v, lower[a], upper[a]);
     if (c != v) { x[a] = c; ++moved; }
   });
-  moved = wave_sum_u(moved);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = moved;
+  moved = wave_sum(moved);
+  wave_to_lds(moved, sh);
   __syncthreads();
   if (threadIdx.x == 0) counts[blockIdx.x] = (unsigned long long)(sh[0]) + sh[1] + sh[2] + sh[3];
 }
@@ -101,7 +86,7 @@ __global__ __launch_bounds__(kVecBlock) void bounds_trial_kernel(BalFreeBlocks B
     dm = fmax(dm, fabs(d));
     if (grad) gd += (scale ? grad[k] / sc : grad[k]) * d;
   });
-  xn = wave_sum_b(xn); sn = wave_sum_b(sn); dm = wave_max_b(dm); gd = wave_sum_b(gd);
+  xn = wave_sum(xn); sn = wave_sum(sn); dm = wave_max(dm); gd = wave_sum(gd);
   if ((threadIdx.x & 63) == 0) {
     const int w = threadIdx.x >> 6;
     sh[w] = xn; sh[4 + w] = sn; sh[8 + w] = dm; sh[12 + w] = gd;
@@ -109,10 +94,10 @@ __global__ __launch_bounds__(kVecBlock) void bounds_trial_kernel(BalFreeBlocks B
   __syncthreads();
   if (threadIdx.x == 0) {
     const int g = gridDim.x;
-    partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    partials[g + blockIdx.x] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
-    partials[2 * g + blockIdx.x] = fmax(fmax(sh[8], sh[9]), fmax(sh[10], sh[11]));
-    partials[3 * g + blockIdx.x] = (sh[12] + sh[13]) + (sh[14] + sh[15]);
+    partials[blockIdx.x] = lds_sum4(sh);
+    partials[g + blockIdx.x] = lds_sum4(sh + 4);
+    partials[2 * g + blockIdx.x] = lds_max4(sh + 8);
+    partials[3 * g + blockIdx.x] = lds_sum4(sh + 12);
   }
 }
 
@@ -126,17 +111,15 @@ __global__ __launch_bounds__(kVecBlock) void bounds_gradient_max_kernel(BalFreeB
     const double xi = x[a];
     m = fmax(m, fabs(xi - clamp_b(xi - gi, lower[a], upper[a])));
   });
-  m = wave_max_b(m);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+  m = wave_max(m);
+  wave_to_lds(m, sh);
   __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+  if (threadIdx.x == 0) partials[blockIdx.x] = lds_max4(sh);
 }
 
 // work items: doubles in the plain form, free blocks in the other
-int grid_for(const BalBounds& K) {
-  const int64_t n = K.B.block ? K.B.n_free_points + K.B.n_free_cameras : K.B.n_free_points;
-  const int64_t g = (n + kVecBlock - 1) / kVecBlock;
-  return int(g < 1 ? 1 : (g > kMaxVecGrid ? kMaxVecGrid : g));
+int bounds_grid(const BalBounds& K) {
+  return vec_grid(K.B.block ? K.B.n_free_points + K.B.n_free_cameras : K.B.n_free_points, kMaxVecGrid);
 }
 // 0: plain, 9 | 10: free blocks; -1: a width no kernel was built for
 int form_of(const BalBounds& K) {
@@ -155,7 +138,7 @@ int form_of(const BalBounds& K) {
   }
 
 hipError_t LaunchBoundsProject(const BalBounds& K, double* x, unsigned long long* counts, int* nparts, hipStream_t stream) {
-  const int grid = grid_for(K);
+  const int grid = bounds_grid(K);
   *nparts = grid;
   BOUNDS_DISPATCH(bounds_project_kernel, K.B, K.lower, K.upper, x, counts)
   return hipGetLastError();
@@ -163,7 +146,7 @@ hipError_t LaunchBoundsProject(const BalBounds& K, double* x, unsigned long long
 
 hipError_t LaunchBoundsTrialPoint(const BalBounds& K, const double* x, const double* step, const double* scale, const double* grad, double t,
                                   bool fold, double* delta, double* out, double* partials, int* nparts, hipStream_t stream) {
-  const int grid = grid_for(K);
+  const int grid = bounds_grid(K);
   *nparts = grid;
   BOUNDS_DISPATCH(bounds_trial_kernel, K.B, K.lower, K.upper, x, step, scale, grad, t, fold ? 1 : 0, delta, out, partials)
   return hipGetLastError();
@@ -171,7 +154,7 @@ hipError_t LaunchBoundsTrialPoint(const BalBounds& K, const double* x, const dou
 
 hipError_t LaunchBoundsGradientMax(const BalBounds& K, const double* x, const double* g, const double* scale, double* partials, int* nparts,
                                    hipStream_t stream) {
-  const int grid = grid_for(K);
+  const int grid = bounds_grid(K);
   *nparts = grid;
   BOUNDS_DISPATCH(bounds_gradient_max_kernel, K.B, K.lower, K.upper, x, g, scale, partials)
   return hipGetLastError();

@@ -7,22 +7,12 @@
 #include <hip/hip_runtime.h>
 
 #include "device.h"
+#include "reduce.h"
 #include "quaternion_plus.h"
 
 namespace chip {
 
 namespace {
-
-__device__ __forceinline__ double wave_sum_c(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max_c(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-  return v;
-}
 
 // CM: the camera model — SW state doubles, CW tangent entries per camera; the manifold's Plus on q, x + delta everywhere else
 template <int CM>
@@ -79,12 +69,12 @@ __global__ __launch_bounds__(kVecBlock) void bal_candidate_free_kernel(BalFreeBl
       }
     }
   }
-  xn = wave_sum_c(xn); dn = wave_sum_c(dn);
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = xn; sh[4 + (threadIdx.x >> 6)] = dn; }
+  xn = wave_sum(xn); dn = wave_sum(dn);
+  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = xn; sh[4 + (threadIdx.x >> 6)] = dn; }   // (one branch for both: two wave_to_lds change the code)
   __syncthreads();
   if (threadIdx.x == 0) {
-    partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    partials[gridDim.x + blockIdx.x] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
+    partials[blockIdx.x] = lds_sum4(sh);
+    partials[gridDim.x + blockIdx.x] = lds_sum4(sh + 4);
   }
 }
 
@@ -113,22 +103,17 @@ __global__ __launch_bounds__(kVecBlock) void bal_gradient_max_quat_free_kernel(B
 #pragma unroll
     for (int j = 3; j < 9; ++j) m = fmax(m, fabs(gt[j]));
   }
-  m = wave_max_c(m);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+  m = wave_max(m);
+  wave_to_lds(m, sh);
   __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
-}
-
-int grid_for(int64_t n) {
-  int64_t g = (n + kVecBlock - 1) / kVecBlock;
-  return int(g < 1 ? 1 : (g > kMaxVecGrid ? kMaxVecGrid : g));
+  if (threadIdx.x == 0) partials[blockIdx.x] = lds_max4(sh);
 }
 
 }  // namespace
 
 hipError_t LaunchBalCandidateFree(const BalFreeBlocks& B, int camera_model, const double* x, const double* step, const double* scale,
                                   double* delta, double* cand, double* partials, int* nparts, hipStream_t stream) {
-  const int grid = grid_for(B.n_free_points + B.n_free_cameras);
+  const int grid = vec_grid(B.n_free_points + B.n_free_cameras, kMaxVecGrid);
   *nparts = grid;
   switch (camera_model) {
     case kCamAngleAxis:
@@ -148,7 +133,7 @@ hipError_t LaunchBalCandidateFree(const BalFreeBlocks& B, int camera_model, cons
 
 hipError_t LaunchBalGradientMaxQuatFree(const BalFreeBlocks& B, const double* g, const double* scale, const double* x, double* partials,
                                         int* nparts, hipStream_t stream) {
-  const int grid = grid_for(B.n_free_points + B.n_free_cameras);
+  const int grid = vec_grid(B.n_free_points + B.n_free_cameras, kMaxVecGrid);
   *nparts = grid;
   hipLaunchKernelGGL(bal_gradient_max_quat_free_kernel, dim3(grid), dim3(kVecBlock), 0, stream, B, g, scale, x, partials);
   return hipGetLastError();

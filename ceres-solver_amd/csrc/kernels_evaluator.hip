@@ -15,6 +15,7 @@
 #include <type_traits>
 
 #include "device.h"
+#include "reduce.h"
 #include "robust_loss.h"
 #include "bal_evaluate.h"
 #include "snavely.h"
@@ -22,17 +23,6 @@
 namespace chip {
 
 namespace {
-
-__device__ __forceinline__ double wave_sum_e(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max_e(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-  return v;
-}
 
 // The same evaluation in TILE order (round 4): one wavefront per tile of 64 observation slots, the Jacobian goes straight
 // into the layout the solver's passes read — J[tile][12][64] double2 (E pairs 0-2, F pairs 3-11), b[tile][64] double2, zeros in
@@ -227,10 +217,10 @@ __global__ __launch_bounds__(kVecBlock) __attribute__((amdgpu_waves_per_eu(2, 2)
     }
     ix = ix1; ix1 = ix2; rec = rec1;
   }
-  cost = wave_sum_e(cost);
+  cost = wave_sum(cost);
   if (lane == 0) sh[wave] = cost;
   __syncthreads();
-  if (threadIdx.x == 0) A.partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  if (threadIdx.x == 0) A.partials[blockIdx.x] = lds_sum4(sh);
 }
 
 // delta = step .* scale ; candidate = x + delta ; partials: |x|^2 at [b], |delta|^2 at [grid + b]
@@ -246,12 +236,12 @@ __global__ __launch_bounds__(kVecBlock) void bal_candidate_kernel(const double* 
     xn += xi * xi;
     dn += d * d;
   }
-  xn = wave_sum_e(xn); dn = wave_sum_e(dn);
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = xn; sh[4 + (threadIdx.x >> 6)] = dn; }
+  xn = wave_sum(xn); dn = wave_sum(dn);
+  wave_to_lds(xn, sh); wave_to_lds(dn, sh + 4);
   __syncthreads();
   if (threadIdx.x == 0) {
-    partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    partials[gridDim.x + blockIdx.x] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
+    partials[blockIdx.x] = lds_sum4(sh);
+    partials[gridDim.x + blockIdx.x] = lds_sum4(sh + 4);
   }
 }
 
@@ -261,10 +251,10 @@ __global__ __launch_bounds__(kVecBlock) void bal_gradient_max_kernel(const doubl
   double m = 0;
   for (int64_t i = int64_t(blockIdx.x) * kVecBlock + threadIdx.x; i < n; i += int64_t(gridDim.x) * kVecBlock)
     m = fmax(m, fabs(scale ? g[i] / scale[i] : g[i]));
-  m = wave_max_e(m);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+  m = wave_max(m);
+  wave_to_lds(m, sh);
   __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+  if (threadIdx.x == 0) partials[blockIdx.x] = lds_max4(sh);
 }
 
 // scale = 1 / (1 + sqrt(squared column norm))      I/trust_region_minimizer.cc:263-270
@@ -273,17 +263,11 @@ __global__ __launch_bounds__(kVecBlock) void bal_jacobi_scale_kernel(const doubl
     scale[i] = 1.0 / (1.0 + sqrt(colnorm2[i]));
 }
 
-int grid_for(int64_t n) {
-  int64_t g = (n + kVecBlock - 1) / kVecBlock;
-  return int(g < 1 ? 1 : (g > kMaxVecGrid ? kMaxVecGrid : g));
-}
-
 }  // namespace
 
 hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, hipStream_t stream, int camera_model) {
   // one observation per thread and several per thread at scale: 2048 workgroups keep 256 CUs busy
-  int64_t g = (A.n_rows + kVecBlock - 1) / kVecBlock;
-  const int grid = int(g < 1 ? 1 : (g > kMaxEvalGrid ? kMaxEvalGrid : g));
+  const int grid = vec_grid(A.n_rows, kMaxEvalGrid);
   *nparts = grid;
   if (camera_model != kCamAngleAxis) return LaunchBalEvaluateQuat(A, jacobian, grid, stream, camera_model);   // (kernels_quaternion.hip)
   if (A.loss.type == kLossNone) {
@@ -298,8 +282,7 @@ hipError_t LaunchBalEvaluate(const BalEvalArgs& A, bool jacobian, int* nparts, h
 
 // the reduced program's Jacobian evaluation (the quaternion cameras' instantiations: kernels_quaternion.hip)
 hipError_t LaunchBalEvaluateConst(const BalEvalConstArgs& A, int* nparts, hipStream_t stream, int camera_model) {
-  int64_t g = (A.n_rows + kVecBlock - 1) / kVecBlock;
-  const int grid = int(g < 1 ? 1 : (g > kMaxEvalGrid ? kMaxEvalGrid : g));
+  const int grid = vec_grid(A.n_rows, kMaxEvalGrid);
   *nparts = grid;
   if (!A.row_fpos || !A.row_scam || !A.row_spt || !A.values) return hipErrorInvalidValue;
   if (camera_model != kCamAngleAxis) return LaunchBalEvaluateConstQuat(A, grid, stream, camera_model);
@@ -354,21 +337,21 @@ hipError_t LaunchBalEvaluateTiles(const BalEvalTilesArgs& T, int64_t n_points, i
 
 hipError_t LaunchBalCandidate(const double* x, const double* step, const double* scale, double* delta, double* cand, int64_t n,
                               double* partials, int* nparts, hipStream_t stream) {
-  const int grid = grid_for(n);
+  const int grid = vec_grid(n, kMaxVecGrid);
   *nparts = grid;
   hipLaunchKernelGGL(bal_candidate_kernel, dim3(grid), dim3(kVecBlock), 0, stream, x, step, scale, delta, cand, n, partials);
   return hipGetLastError();
 }
 
 hipError_t LaunchBalGradientMax(const double* g, const double* scale, int64_t n, double* partials, int* nparts, hipStream_t stream) {
-  const int grid = grid_for(n);
+  const int grid = vec_grid(n, kMaxVecGrid);
   *nparts = grid;
   hipLaunchKernelGGL(bal_gradient_max_kernel, dim3(grid), dim3(kVecBlock), 0, stream, g, scale, n, partials);
   return hipGetLastError();
 }
 
 hipError_t LaunchBalJacobiScale(const double* colnorm2, double* scale, int64_t n, hipStream_t stream) {
-  hipLaunchKernelGGL(bal_jacobi_scale_kernel, dim3(grid_for(n)), dim3(kVecBlock), 0, stream, colnorm2, scale, n);
+  hipLaunchKernelGGL(bal_jacobi_scale_kernel, dim3(vec_grid(n, kMaxVecGrid)), dim3(kVecBlock), 0, stream, colnorm2, scale, n);
   return hipGetLastError();
 }
 

@@ -28,6 +28,7 @@
 #include <cfloat>
 
 #include "device.h"
+#include "reduce.h"
 #include "robust_loss.h"
 #include "snavely.h"
 
@@ -47,18 +48,12 @@ struct InnerSizes {
 template <int NP>
 __device__ constexpr int tri(int i, int j) { return i * NP - i * (i - 1) / 2 + (j - i); }
 
-__device__ __forceinline__ double wave_sum_i(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // Sum acc[0 .. N) over the team (T = 64: a fixed-order butterfly); afterwards every lane of the team holds the same bits.
 template <int T, int N>
 __device__ __forceinline__ void team_sum(double (&acc)[N]) {
   if constexpr (T == 64) {
 #pragma unroll
-    for (int k = 0; k < N; ++k) acc[k] = wave_sum_i(acc[k]);
+    for (int k = 0; k < N; ++k) acc[k] = wave_sum(acc[k]);
   }
 }
 
@@ -325,10 +320,10 @@ __global__ __launch_bounds__(kVecBlock) void bal_diff_norm_kernel(const double* 
     const double d = a[i] - b[i];
     s += d * d;
   }
-  s = wave_sum_i(s);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+  s = wave_sum(s);
+  wave_to_lds(s, sh);
   __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  if (threadIdx.x == 0) partials[blockIdx.x] = lds_sum4(sh);
 }
 
 }  // namespace
@@ -353,8 +348,7 @@ hipError_t LaunchInnerBlocks(const InnerArgs& A, int form, hipStream_t stream) {
 }
 
 hipError_t LaunchBalDiffNorm(const double* a, const double* b, int64_t n, double* partials, int* nparts, hipStream_t stream) {
-  int64_t g = (n + kVecBlock - 1) / kVecBlock;
-  const int grid = int(g < 1 ? 1 : (g > kMaxVecGrid ? kMaxVecGrid : g));
+  const int grid = vec_grid(n, kMaxVecGrid);
   *nparts = grid;
   hipLaunchKernelGGL(bal_diff_norm_kernel, dim3(grid), dim3(kVecBlock), 0, stream, a, b, n, partials);
   return hipGetLastError();

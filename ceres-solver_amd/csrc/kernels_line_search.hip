@@ -19,6 +19,7 @@
 #include <algorithm>
 
 #include "device.h"
+#include "reduce.h"
 #include "line_search_gradient.h"
 #include "quaternion_plus.h"
 
@@ -26,26 +27,20 @@ namespace chip {
 
 namespace {
 
-__device__ __forceinline__ double ls_wave_max(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-  return v;
-}
-
 // the workgroup's sum / maximum of one value per thread (kVecBlock threads; sh: 4 doubles); every thread gets it
 __device__ __forceinline__ double ls_block_sum(double v, double* sh) {
-  v = ls_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  v = wave_sum(v);
+  wave_to_lds(v, sh);
   __syncthreads();
-  const double r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  const double r = lds_sum4(sh);
   __syncthreads();
   return r;
 }
 __device__ __forceinline__ double ls_block_max(double v, double* sh) {
-  v = ls_wave_max(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  v = wave_max(v);
+  wave_to_lds(v, sh);
   __syncthreads();
-  const double r = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
+  const double r = lds_max4(sh);
   __syncthreads();
   return r;
 }
@@ -308,11 +303,6 @@ __global__ __launch_bounds__(kVecBlock) void lbfgs_second_loop_kernel(LbfgsArgs 
   if (threadIdx.x == 0) A.parts[((q + 1) & 1) * kMaxVecGrid + blockIdx.x] = acc;
 }
 
-int ls_grid_for(int64_t n) {
-  int64_t g = (n + kVecBlock - 1) / kVecBlock;
-  return int(g < 1 ? 1 : (g > kMaxVecGrid ? kMaxVecGrid : g));
-}
-
 }  // namespace
 
 hipError_t LaunchLsGradient(const LsGradArgs& A, bool gradient, int camera_model, int* nparts, hipStream_t stream) {
@@ -351,7 +341,7 @@ hipError_t LaunchLsGradient(const LsGradArgs& A, bool gradient, int camera_model
 
 hipError_t LaunchLsTrialPoint(const BalFreeBlocks& B, int camera_model, const double* x, const double* direction, double t, double* out,
                               double* partials, int* nparts, hipStream_t stream) {
-  const int grid = ls_grid_for(B.n_free_points + B.n_free_cameras);
+  const int grid = vec_grid(B.n_free_points + B.n_free_cameras, kMaxVecGrid);
   *nparts = grid;
   switch (camera_model) {
     case kCamAngleAxis: hipLaunchKernelGGL((ls_plus_kernel<kCamAngleAxis, false>), dim3(grid), dim3(kVecBlock), 0, stream, B, x, direction, t, out, partials); break;
@@ -366,7 +356,7 @@ hipError_t LaunchLsTrialPoint(const BalFreeBlocks& B, int camera_model, const do
 
 hipError_t LaunchLsGradientNorms(const BalFreeBlocks& B, int camera_model, const double* x, const double* g, double* partials, int* nparts,
                                  hipStream_t stream) {
-  const int grid = ls_grid_for(B.n_free_points + B.n_free_cameras);
+  const int grid = vec_grid(B.n_free_points + B.n_free_cameras, kMaxVecGrid);
   *nparts = grid;
   switch (camera_model) {
     case kCamAngleAxis: hipLaunchKernelGGL((ls_plus_kernel<kCamAngleAxis, true>), dim3(grid), dim3(kVecBlock), 0, stream, B, x, g, -1.0, nullptr, partials); break;
@@ -380,7 +370,7 @@ hipError_t LaunchLsGradientNorms(const BalFreeBlocks& B, int camera_model, const
 }
 
 hipError_t LaunchLsDots(const double* a, const double* b, const double* c, int64_t n, double* partials, int* nparts, hipStream_t stream) {
-  const int grid = ls_grid_for(n);
+  const int grid = vec_grid(n, kMaxVecGrid);
   *nparts = grid;
   hipLaunchKernelGGL(ls_dots_kernel, dim3(grid), dim3(kVecBlock), 0, stream, a, b, c, n, partials);
   return hipGetLastError();
@@ -388,7 +378,7 @@ hipError_t LaunchLsDots(const double* a, const double* b, const double* c, int64
 
 hipError_t LaunchLsCombine(double alpha, const double* x, double beta, const double* y, double gamma, const double* w, double* z, int64_t n,
                            hipStream_t stream) {
-  hipLaunchKernelGGL(ls_combine_kernel, dim3(ls_grid_for(n)), dim3(kVecBlock), 0, stream, alpha, x, beta, y, gamma, w, z, n);
+  hipLaunchKernelGGL(ls_combine_kernel, dim3(vec_grid(n, kMaxVecGrid)), dim3(kVecBlock), 0, stream, alpha, x, beta, y, gamma, w, z, n);
   return hipGetLastError();
 }
 
@@ -399,7 +389,7 @@ hipError_t LaunchLbfgsReset(const LbfgsArgs& A, hipStream_t stream) {
 
 hipError_t LaunchLbfgsUpdate(const LbfgsArgs& A, double a, const double* sv, const double* y1, const double* y0, int log_index, hipStream_t stream) {
   if (A.n <= 0 || A.rank <= 0) return hipErrorInvalidValue;
-  const int grid = ls_grid_for(A.n);
+  const int grid = vec_grid(A.n, kMaxVecGrid);
   hipLaunchKernelGGL(lbfgs_update_dots_kernel, dim3(grid), dim3(kVecBlock), 0, stream, A, a, sv, y1, y0);
   hipLaunchKernelGGL(lbfgs_update_store_kernel, dim3(grid), dim3(kVecBlock), 0, stream, A, a, sv, y1, y0);
   hipLaunchKernelGGL(lbfgs_update_commit_kernel, dim3(1), dim3(kVecBlock), 0, stream, A, grid, log_index);
@@ -408,7 +398,7 @@ hipError_t LaunchLbfgsUpdate(const LbfgsArgs& A, double a, const double* sv, con
 
 hipError_t LaunchLbfgsDirection(const LbfgsArgs& A, const double* g, double* d, int max_live, int* nparts, hipStream_t stream) {
   if (A.n <= 0 || A.rank <= 0) return hipErrorInvalidValue;
-  const int grid = ls_grid_for(A.n);
+  const int grid = vec_grid(A.n, kMaxVecGrid);
   *nparts = grid;
   const int steps = std::min(max_live, int(A.rank));
   hipLaunchKernelGGL(lbfgs_begin_kernel, dim3(grid), dim3(kVecBlock), 0, stream, A, g, d);

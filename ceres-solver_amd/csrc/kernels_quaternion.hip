@@ -7,22 +7,12 @@
 
 #include "bal_evaluate.h"
 #include "device.h"
+#include "reduce.h"
 #include "quaternion_plus.h"
 
 namespace chip {
 
 namespace {
-
-__device__ __forceinline__ double wave_sum_q(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-__device__ __forceinline__ double wave_max_q(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m, 64));
-  return v;
-}
 
 // bal_candidate_kernel for quaternion-manifold cameras: delta = step .* scale (tangent: 9 per camera), candidate = Plus(x, delta)
 // (ambient: 10 per camera, QuaternionManifold on q, Euclidean on the rest).  One item per point coordinate, then one per camera: each
@@ -63,12 +53,12 @@ __global__ __launch_bounds__(kVecBlock) void bal_candidate_quat_kernel(const dou
       xn += xi * xi;
     }
   }
-  xn = wave_sum_q(xn); dn = wave_sum_q(dn);
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = xn; sh[4 + (threadIdx.x >> 6)] = dn; }
+  xn = wave_sum(xn); dn = wave_sum(dn);
+  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = xn; sh[4 + (threadIdx.x >> 6)] = dn; }   // (one branch for both: two wave_to_lds change the code)
   __syncthreads();
   if (threadIdx.x == 0) {
-    partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    partials[gridDim.x + blockIdx.x] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
+    partials[blockIdx.x] = lds_sum4(sh);
+    partials[gridDim.x + blockIdx.x] = lds_sum4(sh + 4);
   }
 }
 
@@ -98,22 +88,17 @@ __global__ __launch_bounds__(kVecBlock) void bal_gradient_max_quat_kernel(const 
 #pragma unroll
     for (int j = 3; j < 9; ++j) m = fmax(m, fabs(gt[j]));
   }
-  m = wave_max_q(m);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
+  m = wave_max(m);
+  wave_to_lds(m, sh);
   __syncthreads();
-  if (threadIdx.x == 0) partials[blockIdx.x] = fmax(fmax(sh[0], sh[1]), fmax(sh[2], sh[3]));
-}
-
-int grid_for(int64_t n) {
-  int64_t g = (n + kVecBlock - 1) / kVecBlock;
-  return int(g < 1 ? 1 : (g > kMaxVecGrid ? kMaxVecGrid : g));
+  if (threadIdx.x == 0) partials[blockIdx.x] = lds_max4(sh);
 }
 
 }  // namespace
 
 hipError_t LaunchBalCandidateQuat(const double* x, const double* step, const double* scale, double* delta, double* cand, int64_t n_points,
                                   int64_t n_cameras, double* partials, int* nparts, hipStream_t stream) {
-  const int grid = grid_for(3 * n_points + n_cameras);
+  const int grid = vec_grid(3 * n_points + n_cameras, kMaxVecGrid);
   *nparts = grid;
   hipLaunchKernelGGL(bal_candidate_quat_kernel, dim3(grid), dim3(kVecBlock), 0, stream, x, step, scale, delta, cand, n_points, n_cameras,
                      partials);
@@ -122,7 +107,7 @@ hipError_t LaunchBalCandidateQuat(const double* x, const double* step, const dou
 
 hipError_t LaunchBalGradientMaxQuat(const double* g, const double* scale, const double* x, int64_t n_points, int64_t n_cameras,
                                     double* partials, int* nparts, hipStream_t stream) {
-  const int grid = grid_for(3 * n_points + n_cameras);
+  const int grid = vec_grid(3 * n_points + n_cameras, kMaxVecGrid);
   *nparts = grid;
   hipLaunchKernelGGL(bal_gradient_max_quat_kernel, dim3(grid), dim3(kVecBlock), 0, stream, g, scale, x, n_points, n_cameras, partials);
   return hipGetLastError();

@@ -16,18 +16,13 @@
 #include <hip/hip_runtime.h>
 
 #include "device.h"
+#include "reduce.h"
 #include "robust_loss.h"
 #include "snavely.h"
 
 namespace chip {
 
 namespace {
-
-__device__ __forceinline__ double wave_sum_s(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 constexpr bool subset_is_free(int mask, int j) { return j < 6 || !((mask >> (j - 6)) & 1); }
 constexpr int subset_width(int mask) { return 9 - (mask & 1) - ((mask >> 1) & 1) - ((mask >> 2) & 1); }
@@ -94,10 +89,10 @@ __global__ __launch_bounds__(kVecBlock) void bal_evaluate_subset_kernel(BalEvalC
       for (int j = 0; j < CW; ++j) fo[j] = make_double2(f[2 * j], f[2 * j + 1]);
     }
   }
-  cost = wave_sum_s(cost);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = cost;
+  cost = wave_sum(cost);
+  wave_to_lds(cost, sh);
   __syncthreads();
-  if (threadIdx.x == 0) A.partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  if (threadIdx.x == 0) A.partials[blockIdx.x] = lds_sum4(sh);
 }
 
 // delta = step .* scale (tangent), cand = x with delta added on the free coordinates, the marked ones copied; one work item per free
@@ -139,12 +134,12 @@ __global__ __launch_bounds__(kVecBlock) void bal_candidate_subset_kernel(BalFree
       ++t;
     }
   }
-  xn = wave_sum_s(xn); dn = wave_sum_s(dn);
-  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = xn; sh[4 + (threadIdx.x >> 6)] = dn; }
+  xn = wave_sum(xn); dn = wave_sum(dn);
+  if ((threadIdx.x & 63) == 0) { sh[threadIdx.x >> 6] = xn; sh[4 + (threadIdx.x >> 6)] = dn; }   // (one branch for both: two wave_to_lds change the code)
   __syncthreads();
   if (threadIdx.x == 0) {
-    partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    partials[gridDim.x + blockIdx.x] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
+    partials[blockIdx.x] = lds_sum4(sh);
+    partials[gridDim.x + blockIdx.x] = lds_sum4(sh + 4);
   }
 }
 
@@ -157,8 +152,7 @@ void launch_subset(const BalEvalConstArgs& A, int grid, hipStream_t stream) {
 }  // namespace
 
 hipError_t LaunchBalEvaluateSubset(const BalEvalConstArgs& A, int mask, int* nparts, hipStream_t stream) {
-  int64_t g = (A.n_rows + kVecBlock - 1) / kVecBlock;
-  const int grid = int(g < 1 ? 1 : (g > kMaxEvalGrid ? kMaxEvalGrid : g));
+  const int grid = vec_grid(A.n_rows, kMaxEvalGrid);
   *nparts = grid;
   if (!A.row_fpos || !A.row_scam || !A.row_spt || !A.values) return hipErrorInvalidValue;
   switch (mask) {
@@ -178,8 +172,7 @@ hipError_t LaunchBalCandidateSubset(const BalFreeBlocks& B, int mask, int64_t n_
                                     double* delta, double* cand, double* partials, int* nparts, hipStream_t stream) {
   if (mask < 1 || mask > 7) return hipErrorInvalidValue;
   const int64_t n = B.n_free_points + B.n_free_cameras;
-  int64_t g = (n + kVecBlock - 1) / kVecBlock;
-  const int grid = int(g < 1 ? 1 : (g > kMaxVecGrid ? kMaxVecGrid : g));
+  const int grid = vec_grid(n, kMaxVecGrid);
   *nparts = grid;
   const int cw = subset_width(mask);
   if (B.block) hipLaunchKernelGGL(bal_candidate_subset_kernel<true>, dim3(grid), dim3(kVecBlock), 0, stream, B, mask, cw, n_points, x, step, scale, delta, cand, partials);

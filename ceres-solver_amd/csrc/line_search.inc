@@ -416,7 +416,6 @@ LsSearchOptions ls_search_options(const ceres_hip_line_search_options& o) {
 struct BalLineSearch {
   LsGradArgs G;                 // the structure part of the evaluator's arguments (device pointers)
   int64_t* d_blocks = nullptr;  // BalFreeBlocks::block for every handle
-  double *d_parts = nullptr, *h_parts = nullptr;   // kLsParts partial sums (h: pinned)
   double* d_dir = nullptr;      // the search direction (tangent)
   std::vector<double*> slot_x, slot_g;   // the sample pool
   std::vector<int> free_slots;
@@ -431,11 +430,6 @@ struct BalLineSearch {
 namespace {
 
 constexpr int kLsMaxSlots = 12;
-// h_parts / d_parts: cost partials [0, 2048), then seven sets of kMaxVecGrid: two of the trial point, two of the gradient norms and
-// THREE of ls_dots_kernel (a . b, a . c, max |a|; with room for two, a tangent vector of more than 341 workgroups wrote — and the
-// host copied — up to kMaxVecGrid doubles past the end of both buffers)
-constexpr int kLsCostParts = 2048, kLsParts = kLsCostParts + 7 * kMaxVecGrid;
-static_assert(kMaxEvalGrid <= kLsCostParts, "one cost partial per workgroup of the evaluators");
 
 // give the history and the per-slot scalars back before a larger rank's replace them
 void ls_release_history(ceres_hip_solver* s, BalLineSearch* ls) {
@@ -527,7 +521,6 @@ int bal_ls_prepare(ceres_hip_bal* p) {
   TRY(dev_upload(s, &ls->d_blocks, blocks));
   TRY(dev_alloc(s, &G.wave_parts, size_t(6 * ((no + 63) / 64))));
   TRY(dev_alloc(s, &G.chunk_parts, size_t(kLsChunkPitch) * size_t(std::max(n_partials, 1))));
-  TRY(dev_alloc(s, &ls->d_parts, size_t(kLsParts)));
   TRY(dev_alloc(s, &ls->d_dir, size_t(p->n_t)));
   HIP_TRY(s, hipStreamSynchronize(s->stream));   // (the uploads read host vectors that go out of scope here)
   G.n_rows = no; G.row_cam = p->d_row_cam; G.row_pt = p->d_row_pt; G.row_obs = p->d_row_obs; G.row_pdst = d_pdst;
@@ -536,17 +529,26 @@ int bal_ls_prepare(ceres_hip_bal* p) {
   G.n_chunks = int32_t(ch_cam.size()); G.chunk_cam = d_ccam; G.chunk_start = d_cstart; G.chunk_len = d_clen; G.chunk_dst = d_cdst;
   G.cm_pt = d_cmpt; G.cm_obs = reinterpret_cast<const double2*>(d_cmobs);
   G.n_fin = int32_t(fin_dst.size()); G.fin_dst = d_fdst; G.fin_first = d_ffirst; G.fin_count = d_fcount;
-  G.cost_partials = ls->d_parts;
-  HIP_TRY(s, hipHostMalloc(reinterpret_cast<void**>(&ls->h_parts), sizeof(double) * kLsParts));
   p->ls = ls.release();
   return 0;
 }
 
-// enqueue cost (and gradient) at a device state; the cost partials land in ls->d_parts[0 .. *nparts)
-int bal_ls_evaluate_enqueue(ceres_hip_bal* p, const double* d_state, double* d_gradient, int* nparts) {
+// enqueue cost (and gradient) at a device state; *cost: the set of the cost's partial sums
+int bal_ls_evaluate_enqueue(ceres_hip_bal* p, const double* d_state, double* d_gradient, PartialSet* cost) {
   LsGradArgs A = p->ls->G;
   A.state = d_state; A.grad = d_gradient; A.loss = p->loss;
-  HIP_TRY(p->s, LaunchLsGradient(A, d_gradient != nullptr, p->camera_model, nparts, p->s->stream));
+  TRY(bal_parts_room(p, kMaxEvalGrid, &A.cost_partials));
+  int nparts = 0;
+  HIP_TRY(p->s, LaunchLsGradient(A, d_gradient != nullptr, p->camera_model, &nparts, p->s->stream));
+  *cost = p->parts.take(nparts);
+  return 0;
+}
+// a . b, a . c (0 without c) and max |a| of tangent vectors, enqueued: the three sets of ls_dots_kernel
+int bal_ls_dots_enqueue(ceres_hip_bal* p, const double* a, const double* b, const double* c, PartialSet* ab, PartialSet* ac, PartialSet* amax) {
+  int nd = 0; double* parts = nullptr;
+  TRY(bal_parts_room(p, 3 * kMaxVecGrid, &parts));
+  HIP_TRY(p->s, LaunchLsDots(a, b, c, p->n_t, parts, &nd, p->s->stream));
+  *ab = p->parts.take(nd); *ac = p->parts.take(nd); *amax = p->parts.take(nd);
   return 0;
 }
 
@@ -554,7 +556,6 @@ int bal_ls_evaluate_enqueue(ceres_hip_bal* p, const double* d_state, double* d_g
 
 void bal_ls_free(ceres_hip_bal* p) {
   if (!p->ls) return;
-  if (p->ls->h_parts) (void)hipHostFree(p->ls->h_parts);
   delete p->ls;
   p->ls = nullptr;
 }
@@ -601,13 +602,10 @@ int ceres_hip_bal_evaluate_gradient(ceres_hip_bal* p, const double* state, doubl
   HIP_TRY(s, hipSetDevice(s->opt.device));
   BAL_TRY(p, bal_ls_prepare(p));
   BAL_TRY(p, up(s, p->d_cand, state, size_t(p->n_a)));   // (d_cand, d_delta: scratch of the trust-region loop between its calls)
-  int nparts = 0;
-  BAL_TRY(p, bal_ls_evaluate_enqueue(p, p->d_cand, gradient ? p->d_delta : nullptr, &nparts));
-  HIP_TRY(s, hipMemcpyAsync(p->ls->h_parts, p->ls->d_parts, sizeof(double) * nparts, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  double c = 0;
-  for (int i = 0; i < nparts; ++i) c += p->ls->h_parts[i];   // fixed order
-  *cost = c;
+  PartialSet c;
+  BAL_TRY(p, bal_ls_evaluate_enqueue(p, p->d_cand, gradient ? p->d_delta : nullptr, &c));
+  BAL_TRY(p, bal_parts_collect(p));
+  *cost = p->parts.sum(c);
   if (gradient) BAL_TRY(p, down(s, gradient, p->d_delta, size_t(p->n_t)));
   return 0;
 }
@@ -697,34 +695,28 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
   double fixed_cost = 0.0;
   if (p->has_const) BAL_TRY(p, bal_fixed_cost_device(p, p->d_x, &fixed_cost));
 
-  // one evaluation's partial sums, copied and added after ONE synchronisation
-  double* hp = ls->h_parts;
-  double* dp = ls->d_parts;
-  constexpr int kTrial = kLsCostParts, kNorms = kLsCostParts + 2 * kMaxVecGrid, kDots = kLsCostParts + 4 * kMaxVecGrid;
-  static_assert(kDots + 3 * kMaxVecGrid <= kLsParts, "room for the three sets of ls_dots_kernel");
-  auto sum_parts = [&](int off, int n) { double v = 0; for (int i = 0; i < n; ++i) v += hp[off + i]; return v; };
-  auto max_parts = [&](int off, int n) { double v = 0; for (int i = 0; i < n; ++i) v = std::max(v, hp[off + i]); return v; };
+  // one evaluation's partial sums (and a trial point's, enqueued before it), copied and added after ONE synchronisation
+  PartialSums& P = p->parts;
   // cost, gradient and the gradient norms at slot k (vector_x already there); direction != nullptr: also direction . gradient
-  auto evaluate_slot = [&](int k, bool want_gradient, bool trial, const double* direction, LsSample* out) -> int {
+  auto evaluate_slot = [&](int k, bool want_gradient, const double* direction, LsSample* out) -> int {
     const auto t0 = std::chrono::steady_clock::now();
-    int nc = 0, nn = 0, nd = 0;
-    TRY(bal_ls_evaluate_enqueue(p, ls->slot_x[k], want_gradient ? ls->slot_g[k] : nullptr, &nc));
+    PartialSet cost, norm2, norm_max, dg, unused;
+    TRY(bal_ls_evaluate_enqueue(p, ls->slot_x[k], want_gradient ? ls->slot_g[k] : nullptr, &cost));
     ++S->num_function_evaluations;
     if (want_gradient) {
       ++S->num_gradient_evaluations;
-      HIP_TRY(s, LaunchLsGradientNorms(ls_blocks(p), p->camera_model, ls->slot_x[k], ls->slot_g[k], dp + kNorms, &nn, st));
-      if (direction) HIP_TRY(s, LaunchLsDots(direction, ls->slot_g[k], nullptr, nt, dp + kDots, &nd, st));
+      int nn = 0; double* parts = nullptr;
+      TRY(bal_parts_room(p, 2 * kMaxVecGrid, &parts));
+      HIP_TRY(s, LaunchLsGradientNorms(ls_blocks(p), p->camera_model, ls->slot_x[k], ls->slot_g[k], parts, &nn, st));
+      norm2 = P.take(nn); norm_max = P.take(nn);
+      if (direction) TRY(bal_ls_dots_enqueue(p, direction, ls->slot_g[k], nullptr, &dg, &unused, &unused));
     }
-    // (one copy from the buffer's start to the end of the last set this evaluation wrote: cost, trial point, norms, dots)
-    const int last = want_gradient ? (direction ? kDots + nd : kNorms + 2 * nn) : (trial ? kTrial + 2 * kMaxVecGrid : nc);
-    HIP_TRY(s, hipMemcpyAsync(hp, dp, sizeof(double) * last, hipMemcpyDeviceToHost, st));
-    HIP_TRY(s, hipStreamSynchronize(st));
-    out->value = sum_parts(0, nc);
+    TRY(bal_parts_collect(p));
+    out->value = P.sum(cost);
     out->value_is_valid = std::isfinite(out->value);
     if (want_gradient) {
-      out->gradient_norm2 = sum_parts(kNorms, nn);
-      out->gradient_max = max_parts(kNorms + nn, nn);
-      if (direction) out->gradient = sum_parts(kDots, nd);
+      out->gradient_norm2 = P.sum(norm2); out->gradient_max = P.max(norm_max);
+      if (direction) out->gradient = P.sum(dg);
     }
     S->evaluation_seconds += seconds_since(t0);
     return 0;
@@ -742,7 +734,7 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
   double cur_cost = 0, prev_cost = 0, cur_dirderiv = 0, prev_step_size = 0, prev_gnorm2 = 0;
   BAL_TRY(p, acquire(&cur.slot));
   HIP_TRY(s, hipMemcpyAsync(ls->slot_x[*cur.slot], p->d_x, sizeof(double) * na, hipMemcpyDeviceToDevice, st));
-  BAL_TRY(p, evaluate_slot(*cur.slot, true, false, nullptr, &cur));
+  BAL_TRY(p, evaluate_slot(*cur.slot, true, nullptr, &cur));
   int rc = 0;
   auto write_back = [&]() -> int {
     S->final_cost = cur_cost + fixed_cost;
@@ -779,15 +771,17 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
     // the direction; d . g and max |d| come back in one round trip
     const auto td = std::chrono::steady_clock::now();
     bool line_search_status = true;
-    int nd = 0;
     double dmax = 0;
+    PartialSet dots_ab, dots_ac, dots_max;
+    auto direction_dots = [&]() -> int {   // d . g and max |d| of the direction in `dir`
+      TRY(bal_ls_dots_enqueue(p, dir, g, nullptr, &dots_ab, &dots_ac, &dots_max));
+      TRY(bal_parts_collect(p));
+      cur_dirderiv = P.sum(dots_ab); dmax = P.max(dots_max);
+      return 0;
+    };
     auto steepest = [&]() -> int {
       HIP_TRY(s, LaunchLsCombine(-1.0, g, 0.0, nullptr, 0.0, nullptr, dir, nt, st));
-      HIP_TRY(s, LaunchLsDots(dir, g, nullptr, nt, dp + kDots, &nd, st));
-      HIP_TRY(s, hipMemcpyAsync(hp + kDots, dp + kDots, sizeof(double) * 3 * nd, hipMemcpyDeviceToHost, st));
-      HIP_TRY(s, hipStreamSynchronize(st));
-      cur_dirderiv = sum_parts(kDots, nd); dmax = max_parts(kDots + 2 * nd, nd);
-      return 0;
+      return direction_dots();
     };
     if (iteration == 1 || o->line_search_direction_type == CERES_HIP_STEEPEST_DESCENT) {
       BAL_TRY(p, steepest());
@@ -795,10 +789,16 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
       // Update(previous.search_direction * previous.step_size, gradient - previous.gradient), then -H g: no synchronisation until d . g
       HIP_TRY(s, LaunchLbfgsUpdate(ls->L, prev_step_size, dir, g, ls->slot_g[*prev.slot], -1, st));
       lbfgs_updates = std::min(lbfgs_updates + 1, ls->lbfgs_rank);
+      // THE EXCEPTION — the one read-back that does not come from the stage's device buffer: LaunchLbfgsDirection leaves d . g and
+      // max |d| in its own L.parts (sets 2 and 3, kMaxVecGrid apart); they are copied into pinned storage taken from the stage
+      int nd = 0; double* unused = nullptr;
       HIP_TRY(s, LaunchLbfgsDirection(ls->L, g, dir, lbfgs_updates, &nd, st));
-      HIP_TRY(s, hipMemcpyAsync(hp + kDots, ls->L.parts + 2 * kMaxVecGrid, sizeof(double) * 2 * kMaxVecGrid, hipMemcpyDeviceToHost, st));
+      BAL_TRY(p, bal_parts_room(p, 2 * kMaxVecGrid, &unused));
+      const PartialSet both = P.take(2 * kMaxVecGrid);
+      P.drop();
+      HIP_TRY(s, hipMemcpyAsync(P.host(both), ls->L.parts + 2 * kMaxVecGrid, sizeof(double) * 2 * kMaxVecGrid, hipMemcpyDeviceToHost, st));
       HIP_TRY(s, hipStreamSynchronize(st));
-      cur_dirderiv = sum_parts(kDots, nd); dmax = max_parts(kDots + kMaxVecGrid, nd);
+      cur_dirderiv = P.sum(PartialSet{both.offset, nd}); dmax = P.max(PartialSet{both.offset + kMaxVecGrid, nd});
       if (cur_dirderiv >= 0.0) line_search_status = false;   // the inverse Hessian approximation is not positive definite
     } else {   // NonlinearConjugateGradient
       const double* gp = ls->slot_g[*prev.slot];
@@ -807,17 +807,13 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
         beta = cur.gradient_norm2 / prev_gnorm2;
       } else {   // g . (g - g_prev) and d_prev . (g - g_prev): the change is formed once, in the pool's scratch of the step vector
         HIP_TRY(s, LaunchLsCombine(1.0, g, -1.0, gp, 0.0, nullptr, p->d_step, nt, st));
-        HIP_TRY(s, LaunchLsDots(p->d_step, g, dir, nt, dp + kDots, &nd, st));
-        HIP_TRY(s, hipMemcpyAsync(hp + kDots, dp + kDots, sizeof(double) * 3 * nd, hipMemcpyDeviceToHost, st));
-        HIP_TRY(s, hipStreamSynchronize(st));
-        const double g_dg = sum_parts(kDots, nd), d_dg = sum_parts(kDots + nd, nd);
+        BAL_TRY(p, bal_ls_dots_enqueue(p, p->d_step, g, dir, &dots_ab, &dots_ac, &dots_max));
+        BAL_TRY(p, bal_parts_collect(p));
+        const double g_dg = P.sum(dots_ab), d_dg = P.sum(dots_ac);
         beta = o->nonlinear_conjugate_gradient_type == CERES_HIP_POLAK_RIBIERE ? g_dg / prev_gnorm2 : g_dg / d_dg;
       }
       HIP_TRY(s, LaunchLsCombine(beta, dir, -1.0, g, 0.0, nullptr, dir, nt, st));   // -g + beta d_prev
-      HIP_TRY(s, LaunchLsDots(dir, g, nullptr, nt, dp + kDots, &nd, st));
-      HIP_TRY(s, hipMemcpyAsync(hp + kDots, dp + kDots, sizeof(double) * 3 * nd, hipMemcpyDeviceToHost, st));
-      HIP_TRY(s, hipStreamSynchronize(st));
-      cur_dirderiv = sum_parts(kDots, nd); dmax = max_parts(kDots + 2 * nd, nd);
+      BAL_TRY(p, direction_dots());
       if (cur_dirderiv > -o->function_tolerance) BAL_TRY(p, steepest());   // "Restarting non-linear conjugate gradients"
     }
     if (!line_search_status && restarts >= o->max_num_line_search_direction_restarts) {
@@ -848,11 +844,13 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
       *out = LsSample();
       out->x = x;
       TRY(acquire(&out->slot));
-      int ntp = 0;
-      HIP_TRY(s, LaunchLsTrialPoint(ls_blocks(p), p->camera_model, position, dir, x, ls->slot_x[*out->slot], dp + kTrial, &ntp, st));
+      int ntp = 0; double* parts = nullptr;
+      TRY(bal_parts_room(p, 2 * kMaxVecGrid, &parts));
+      HIP_TRY(s, LaunchLsTrialPoint(ls_blocks(p), p->camera_model, position, dir, x, ls->slot_x[*out->slot], parts, &ntp, st));
+      const PartialSet x_norm2 = P.take(ntp), step_norm2 = P.take(ntp);
       out->vector_x_is_valid = true;
-      TRY(evaluate_slot(*out->slot, want_gradient, true, dir, out));
-      out->x_norm2 = sum_parts(kTrial, ntp); out->step_norm2 = sum_parts(kTrial + ntp, ntp);
+      TRY(evaluate_slot(*out->slot, want_gradient, dir, out));
+      out->x_norm2 = P.sum(x_norm2); out->step_norm2 = P.sum(step_norm2);
       position_norm2 = out->x_norm2;
       if (!out->value_is_valid || !want_gradient) return 0;
       if (!std::isfinite(out->gradient)) return 0;
@@ -884,7 +882,7 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
     prev = cur; prev_cost = cur_cost; prev_gnorm2 = cur.gradient_norm2;
     if (!opt.vector_gradient_is_valid) {   // the accepted point's gradient is reused where the search has it; otherwise evaluated here
       LsSample e2;
-      if ((rc = evaluate_slot(*opt.slot, true, false, nullptr, &e2)) != 0) break;
+      if ((rc = evaluate_slot(*opt.slot, true, nullptr, &e2)) != 0) break;
       if (!e2.value_is_valid) { finish(CERES_HIP_MINIMIZER_FAILURE, "Cost and jacobian evaluation failed."); --iteration; break; }
       opt.value = e2.value; opt.gradient_norm2 = e2.gradient_norm2; opt.gradient_max = e2.gradient_max;
     }

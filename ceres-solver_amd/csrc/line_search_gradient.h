@@ -23,18 +23,13 @@
 #include <hip/hip_runtime.h>
 
 #include "device.h"
+#include "reduce.h"
 #include "robust_loss.h"
 #include "snavely.h"
 
 namespace chip {
 
 namespace {
-
-__device__ __forceinline__ double ls_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
 
 // residual, Jacobian and the loss of one observation: w = rho' (1 without a loss), half_rho = the observation's cost
 template <int CM, bool ROBUST, bool JAC>
@@ -110,10 +105,10 @@ __global__ __launch_bounds__(kVecBlock) void ls_point_pass_kernel(LsGradArgs A) 
       }
     }
   }
-  cost = ls_wave_sum(cost);
+  cost = wave_sum(cost);
   if (lane == 0) sh[wave] = cost;
   __syncthreads();
-  if (threadIdx.x == 0) A.cost_partials[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  if (threadIdx.x == 0) A.cost_partials[blockIdx.x] = lds_sum4(sh);
 }
 
 template <int CM, bool ROBUST>
@@ -135,7 +130,7 @@ __global__ __launch_bounds__(kVecBlock) void ls_camera_pass_kernel(LsGradArgs A)
     double mine = 0.0;
 #pragma unroll
     for (int j = 0; j < CW; ++j) {
-      const double t = ls_wave_sum(g[j]);
+      const double t = wave_sum(g[j]);
       if (lane == j) mine = t;
     }
     if (lane < CW) {

@@ -31,6 +31,7 @@
 #include <vector>
 
 #include "device.h"
+#include "partial_sums.h"
 
 namespace chip {
 namespace {

@@ -8,6 +8,7 @@ import pytest
 import constant_blocks_reference as CB
 import frontend_reference as F
 import inner_reference as IR
+import line_search_reference as LR
 from test_gpu_frontend_matrix import (CASES, EDGE_INEXACT_SOLVERS, FACTORS, LOSS_PARAMS, MODELS, NAMES, allowed, case_id, clean_scene, edge_scene,
                                       exceeded, limits, pairs, set_env, tolerances, trajectory)
 from test_gpu_operators import rel
@@ -398,6 +399,25 @@ def test_poisoned_allocations_do_not_reach_the_results(hip, oracle, loop_scene, 
         assert S.final_cost < S.initial_cost and np.array_equal(x[w.constant_state], x0[w.constant_state])
         xr, Sr = F.minimize(w, x0, "lm", max_num_iterations=8)
         assert abs(S.final_cost - (Sr["final_cost"] + w.fixed_cost(x0))) <= tolerances(("angle_axis", "huber", 1.0, "lm", solver, 0, None, 1, None, None))[0] * S.final_cost
+        # Two further inputs, whose every read-back comes through the same stage of partial sums as the loop's (csrc/partial_sums.h) and
+        # which no other poisoned test reaches: the line search minimizer (handles with bounds or fixed intrinsics refuse it) on every
+        # handle, and the dogleg strategy on the DENSE_SCHUR one (it needs an exact factorisation).  The same bound as the LM run above.
+        cost_tol = tolerances(("angle_axis", "huber", 1.0, "lm", solver, 0, None, 1, None, None))[0]
+        xl, Sl = gp.minimize_line_search(x0, max_num_iterations=8)
+        xlr, Slr = LR.minimize(w, x0, max_num_iterations=8)
+        assert np.all(np.isfinite(xl)) and all(np.isfinite(Sl.iterations[k].cost) and np.isfinite(Sl.iterations[k].gradient_max_norm) and
+                                               np.isfinite(Sl.iterations[k].step_norm) for k in range(Sl.num_iterations_logged))
+        assert Sl.final_cost < Sl.initial_cost and np.array_equal(xl[w.constant_state], x0[w.constant_state])
+        print("line search: final cost against the restatement", abs(Sl.final_cost - Slr["final_cost"]) / Sl.final_cost, "bound", cost_tol)
+        assert abs(Sl.final_cost - Slr["final_cost"]) <= cost_tol * Sl.final_cost
+        if solver == (3, 0):
+            gp.set_trust_region_strategy("dogleg", "traditional")
+            xd, Sd = gp.minimize(x0, max_num_iterations=8, eta=1e-12)
+            assert np.all(np.isfinite(xd)) and all(np.isfinite(t[2]) and np.isfinite(t[3]) for t in trajectory(Sd))
+            assert Sd.final_cost < Sd.initial_cost and np.array_equal(xd[w.constant_state], x0[w.constant_state])
+            xdr, Sdr = F.minimize(w, x0, "traditional", max_num_iterations=8)
+            print("dogleg: final cost against the restatement", abs(Sd.final_cost - (Sdr["final_cost"] + w.fixed_cost(x0))) / Sd.final_cost, "bound", cost_tol)
+            assert abs(Sd.final_cost - (Sdr["final_cost"] + w.fixed_cost(x0))) <= cost_tol * Sd.final_cost
     finally:
         gp.close()
 
