@@ -255,5 +255,16 @@ struct HybridRequest { int groups = 0, rows = 0; int64_t lds_bytes = 0; };   // 
 constexpr int kReorderNever = 0, kReorderAlways = 1, kReorderIfContiguous = 2;
 void BuildBalPlan(const HostStructure& hs, int reorder_mode, const HybridRequest& hyb, BalPlan* plan);
 
+// The streamed upload's plan (ceres_hip_values_ready, solver_stream.inc): which ranges of the value array does a run of row blocks own?
+// streams = 1: every row's cells lie back to back and the rows one behind the other; 2: that holds for the rows' first cells (class 0)
+// and for their other cells (class 1) separately — Ceres' Schur-ordered layout, all E cells then all F cells; 0: neither (nothing goes up
+// before _end).  lo[k][r] / hi[k][r]: the range of class k that row block r owns, in doubles; a row without a cell of the class owns the
+// empty range where the class's stream stands, so that row blocks [r0, r1) own exactly [lo[k][r0], hi[k][r1 - 1]).
+struct ValueStreamPlan {
+  int streams = 0;
+  std::vector<int64_t> lo[2], hi[2];   // nrb entries each (zeros for a class that is not in use)
+};
+void PlanValueStreams(const HostStructure& hs, ValueStreamPlan* plan);
+
 }  // namespace chip
 #endif

@@ -151,6 +151,48 @@ std::string AnalyzeStructure(const ceres_hip_block_structure& bs, int nelim, Hos
   return "";
 }
 
+// Which value ranges does a run of row blocks own?  Ceres' BlockJacobianWriter lays a Schur-ordered Jacobian out as all E cells (row
+// order) then all F cells (row order) (I/block_jacobian_writer.cc:68-167): two monotone streams; a row-sequential layout is one.
+void PlanValueStreams(const HostStructure& h, ValueStreamPlan* plan) {
+  ValueStreamPlan& P = *plan;
+  P.streams = 0;
+  for (int k = 0; k < 2; ++k) { P.lo[k].assign(size_t(h.nrb), 0); P.hi[k].assign(size_t(h.nrb), 0); }
+  auto cell_range = [&](int r, int c, int64_t& lo, int64_t& hi) {
+    lo = h.cval[c];
+    hi = lo + int64_t(h.rsz[r]) * h.csz[h.ccol[c]];
+  };
+  // try ONE stream (rows contiguous one after the other), then TWO (first cell | other cells)
+  for (int streams = 1; streams <= 2 && P.streams == 0; ++streams) {
+    bool ok = true;
+    for (int k = 0; k < streams && ok; ++k) {
+      std::vector<int64_t>& L = P.lo[k];
+      std::vector<int64_t>& H = P.hi[k];
+      int64_t prev_hi = -1;
+      for (int r = 0; r < h.nrb && ok; ++r) {
+        int64_t lo = INT64_MAX, hi = -1, total = 0;
+        for (int c = h.rptr[r]; c < h.rptr[r + 1]; ++c) {
+          if (streams == 2 && ((c != h.rptr[r]) != (k == 1))) continue;   // class 0: the row's first cell; class 1: its other cells
+          int64_t a, b;
+          cell_range(r, c, a, b);
+          lo = std::min(lo, a); hi = std::max(hi, b); total += b - a;
+        }
+        if (hi < 0) { L[size_t(r)] = H[size_t(r)] = -1; continue; }               // no cell of this class in the row (filled in below)
+        if (hi - lo != total || (prev_hi >= 0 && lo != prev_hi)) { ok = false; break; }   // cells not back to back / not behind the previous row's
+        L[size_t(r)] = lo; H[size_t(r)] = hi; prev_hi = hi;
+      }
+      if (!ok) break;
+      // rows without a cell of the class own the empty range where the stream stands
+      int64_t at = -1;
+      for (int r = 0; r < h.nrb; ++r) { if (L[size_t(r)] >= 0) at = H[size_t(r)]; else if (at >= 0) L[size_t(r)] = H[size_t(r)] = at; }
+      at = -1;
+      for (int r = h.nrb - 1; r >= 0; --r) { if (L[size_t(r)] >= 0) at = L[size_t(r)]; else L[size_t(r)] = H[size_t(r)] = (at >= 0 ? at : 0); }
+    }
+    if (ok) P.streams = streams;
+  }
+  // (a class that is not in use owns nothing: the ranges of a failed attempt are not left behind)
+  for (int k = P.streams; k < 2; ++k) { std::fill(P.lo[k].begin(), P.lo[k].end(), 0); std::fill(P.hi[k].begin(), P.hi[k].end(), 0); }
+}
+
 void BuildBalPlan(const HostStructure& h, int reorder_mode, const HybridRequest& hyb_in, BalPlan* plan) {
   BalPlan& P = *plan;
   P = BalPlan();

@@ -1629,8 +1629,18 @@ int upload_schur_pairs(ceres_hip_solver* s, const SchurStorage& Q, SchurPairs* o
   return 0;
 }
 
+// Between ceres_hip_values_begin and ceres_hip_values_end own_values / own_b are half uploaded while `loaded` still says what the step
+// before left: every entry point that reads or replaces the loaded values is refused until the session is closed.  The session itself
+// is left as it is (a following _ready / _end completes it).  Under stream_mu: _ready runs on the evaluator's threads.
+int refuse_while_streaming(ceres_hip_solver* s, const char* entry) {
+  std::lock_guard<std::mutex> lock(s->stream_mu);
+  if (s->streaming) return fail(s, CERES_HIP_E_INVALID, "%s between ceres_hip_values_begin and ceres_hip_values_end: the values are still going up", entry);
+  return 0;
+}
+
 int require_loaded(ceres_hip_solver* s) {
   if (!s) return CERES_HIP_E_INVALID;
+  TRY(refuse_while_streaming(s, "a call that reads the loaded values"));
   if (!s->have_structure) return fail(s, CERES_HIP_E_INVALID, "ceres_hip_set_structure has not been called");
   if (!s->loaded) return fail(s, CERES_HIP_E_INVALID, "no values loaded (ceres_hip_load / ceres_hip_solve)");
   return 0;
@@ -2734,6 +2744,7 @@ int ceres_hip_get_info(const ceres_hip_solver* s, ceres_hip_info* info) {
 
 int ceres_hip_load(ceres_hip_solver* s, const double* hv, const double* hb, const double* hD) {
   if (!s) return CERES_HIP_E_INVALID;
+  TRY(refuse_while_streaming(s, "ceres_hip_load"));
   HIP_TRY(s, hipSetDevice(s->opt.device));
   TRY(load_host(s, hv, hb, hD));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -2741,6 +2752,7 @@ int ceres_hip_load(ceres_hip_solver* s, const double* hv, const double* hb, cons
 }
 int ceres_hip_load_device(ceres_hip_solver* s, const double* dv, const double* db, const double* dD) {
   if (!s) return CERES_HIP_E_INVALID;
+  TRY(refuse_while_streaming(s, "ceres_hip_load_device"));
   HIP_TRY(s, hipSetDevice(s->opt.device));
   TRY(load_device(s, dv, db, dD));
   HIP_TRY(s, hipStreamSynchronize(s->stream));
@@ -2757,6 +2769,7 @@ int ceres_hip_solve(ceres_hip_solver* s, const double* hv, const double* hb, con
     snprintf(summary->message, sizeof(summary->message), "%s", s->err.c_str());
     return rc;
   };
+  if (int busy = refuse_while_streaming(s, "ceres_hip_solve")) return fatal(busy);
   if (!s->have_structure) return fatal(fail(s, CERES_HIP_E_INVALID, "ceres_hip_set_structure has not been called"));
   (void)rec(s, 0);
   // upload (ev0..ev1), pack (ev1..ev2)
@@ -2790,6 +2803,7 @@ int ceres_hip_solve_unchanged_values(ceres_hip_solver* s, const double* hD, doub
     snprintf(summary->message, sizeof(summary->message), "%s", s->err.c_str());
     return rc;
   };
+  if (int busy = refuse_while_streaming(s, "ceres_hip_solve_unchanged_values")) return fatal(busy);
   if (!s->have_structure || !s->loaded || !s->have_b)
     return fatal(fail(s, CERES_HIP_E_INVALID, "ceres_hip_solve_unchanged_values needs the values and b of a previous ceres_hip_solve / ceres_hip_load"));
   (void)rec(s, 0);
@@ -2822,6 +2836,7 @@ int ceres_hip_solve_device(ceres_hip_solver* s, const double* dv, const double* 
     snprintf(summary->message, sizeof(summary->message), "%s", s->err.c_str());
     return rc;
   };
+  if (int busy = refuse_while_streaming(s, "ceres_hip_solve_device")) return fatal(busy);
   (void)rec(s, 0);
   (void)rec(s, 1);
   int rc = load_device(s, dv, db, dD);
@@ -2974,6 +2989,7 @@ int lm_step_loaded(ceres_hip_solver* s, const ceres_hip_lm_options* o, double* d
 int ceres_hip_lm_compute_step_device(ceres_hip_solver* s, const double* dv, const double* db,
                                      const ceres_hip_lm_options* o, double* dx, ceres_hip_lm_result* res) {
   if (!s || !o || !dx || !res) return CERES_HIP_E_INVALID;
+  TRY(refuse_while_streaming(s, "ceres_hip_lm_compute_step_device"));
   HIP_TRY(s, hipSetDevice(s->opt.device));
   (void)rec(s, 0);
   (void)rec(s, 1);
@@ -2992,6 +3008,7 @@ int ceres_hip_lm_compute_step_device(ceres_hip_solver* s, const double* dv, cons
 int ceres_hip_lm_compute_step(ceres_hip_solver* s, const double* hv, const double* hb, const ceres_hip_lm_options* o,
                               double* hx, ceres_hip_lm_result* res) {
   if (!s || !o || !hx || !res) return CERES_HIP_E_INVALID;
+  TRY(refuse_while_streaming(s, "ceres_hip_lm_compute_step"));
   HIP_TRY(s, hipSetDevice(s->opt.device));
   (void)rec(s, 0);
   if (o->values_unchanged) {   // the copies of the previous call are still in HBM: nothing crosses PCIe but the step

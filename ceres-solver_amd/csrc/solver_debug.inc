@@ -77,6 +77,36 @@ int ceres_hip_debug_plan(const ceres_hip_block_structure* bs, int32_t num_elimin
   } catch (...) { return CERES_HIP_E_INVALID; }   // (host allocations sized by the caller's structure: no C++ exception crosses the C boundary)
 }
 
+// the plan of the streamed upload (plan.cc, PlanValueStreams): host only, no device
+int ceres_hip_debug_value_streams(const ceres_hip_block_structure* bs, int32_t* value_streams, int64_t* lo, int64_t* hi) {
+  try {
+  if (!bs || !value_streams) return CERES_HIP_E_INVALID;
+  HostStructure h;
+  if (!AnalyzeStructure(*bs, 0, &h).empty()) return CERES_HIP_E_INVALID;   // (the plan does not depend on the elimination order)
+  ValueStreamPlan P;
+  PlanValueStreams(h, &P);
+  *value_streams = P.streams;
+  for (int k = 0; k < 2; ++k) {
+    if (lo) std::copy(P.lo[k].begin(), P.lo[k].end(), lo + size_t(k) * size_t(h.nrb));
+    if (hi) std::copy(P.hi[k].begin(), P.hi[k].end(), hi + size_t(k) * size_t(h.nrb));
+  }
+  return 0;
+  } catch (...) { return CERES_HIP_E_INVALID; }   // (host allocations sized by the caller's structure: no C++ exception crosses the C boundary)
+}
+
+// what the device holds as the loaded values and residuals of the handle's own copies (ceres_hip_load, ceres_hip_lm_compute_step,
+// ceres_hip_values_end): tests compare the bytes that arrived, not a step computed from them.  Waits for the copy stream and the solver's.
+int ceres_hip_debug_read_loaded(ceres_hip_solver* s, double* host_values_out, double* host_b_out) {
+  if (!s) return CERES_HIP_E_INVALID;
+  if (!s->have_structure) return fail(s, CERES_HIP_E_INVALID, "ceres_hip_set_structure has not been called");
+  HIP_TRY(s, hipSetDevice(s->opt.device));
+  if (s->copy_stream) HIP_TRY(s, hipStreamSynchronize(s->copy_stream));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  if (host_values_out) HIP_TRY(s, hipMemcpy(host_values_out, s->own_values, sizeof(double) * size_t(s->hs.values_extent), hipMemcpyDeviceToHost));
+  if (host_b_out) HIP_TRY(s, hipMemcpy(host_b_out, s->own_b, sizeof(double) * size_t(s->hs.num_rows), hipMemcpyDeviceToHost));
+  return 0;
+}
+
 int ceres_hip_op_dense_cholesky_solve(ceres_hip_solver* s, int32_t n, const double* A, const double* b, double* x, int32_t repeats,
                                       double* factor_ms, int32_t* failed) {
   if (!s || !A || !b || !x || n < 1 || repeats < 1) return CERES_HIP_E_INVALID;

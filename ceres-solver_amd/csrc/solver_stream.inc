@@ -2,45 +2,13 @@
 
 // ---- streamed upload: the evaluator's finished rows go up while it is still writing the later ones ----------------------------
 namespace {
-// Which value ranges does a run of row blocks own?  Ceres' BlockJacobianWriter lays a Schur-ordered Jacobian out as all E cells (row
-// order) then all F cells (row order) (I/block_jacobian_writer.cc:68-167): two monotone streams; a row-sequential layout is one.
+// (stream_mu held) the plan of the value streams, once per structure: plan.cc, PlanValueStreams
 void plan_value_streams(ceres_hip_solver* s) {
-  const HostStructure& h = s->hs;
+  ValueStreamPlan P;
+  PlanValueStreams(s->hs, &P);
+  s->n_value_streams = P.streams;
+  for (int k = 0; k < 2; ++k) { s->stream_lo[k].swap(P.lo[k]); s->stream_hi[k].swap(P.hi[k]); }
   s->stream_plan_ready = true;
-  s->n_value_streams = 0;
-  for (int k = 0; k < 2; ++k) { s->stream_lo[k].assign(size_t(h.nrb), 0); s->stream_hi[k].assign(size_t(h.nrb), 0); }
-  auto cell_range = [&](int r, int c, int64_t& lo, int64_t& hi) {
-    lo = h.cval[c];
-    hi = lo + int64_t(h.rsz[r]) * h.csz[h.ccol[c]];
-  };
-  // try ONE stream (rows contiguous one after the other), then TWO (first cell | other cells)
-  for (int streams = 1; streams <= 2 && s->n_value_streams == 0; ++streams) {
-    bool ok = true;
-    for (int k = 0; k < streams && ok; ++k) {
-      std::vector<int64_t>& L = s->stream_lo[k];
-      std::vector<int64_t>& H = s->stream_hi[k];
-      int64_t prev_hi = -1;
-      for (int r = 0; r < h.nrb && ok; ++r) {
-        int64_t lo = INT64_MAX, hi = -1, total = 0;
-        for (int c = h.rptr[r]; c < h.rptr[r + 1]; ++c) {
-          if (streams == 2 && ((c != h.rptr[r]) != (k == 1))) continue;   // class 0: the row's first cell; class 1: its other cells
-          int64_t a, b;
-          cell_range(r, c, a, b);
-          lo = std::min(lo, a); hi = std::max(hi, b); total += b - a;
-        }
-        if (hi < 0) { L[size_t(r)] = H[size_t(r)] = -1; continue; }               // no cell of this class in the row (filled in below)
-        if (hi - lo != total || (prev_hi >= 0 && lo != prev_hi)) { ok = false; break; }   // cells not back to back / not behind the previous row's
-        L[size_t(r)] = lo; H[size_t(r)] = hi; prev_hi = hi;
-      }
-      if (!ok) break;
-      // rows without a cell of the class own the empty range where the stream stands
-      int64_t at = -1;
-      for (int r = 0; r < h.nrb; ++r) { if (L[size_t(r)] >= 0) at = H[size_t(r)]; else if (at >= 0) L[size_t(r)] = H[size_t(r)] = at; }
-      at = -1;
-      for (int r = h.nrb - 1; r >= 0; --r) { if (L[size_t(r)] >= 0) at = L[size_t(r)]; else L[size_t(r)] = H[size_t(r)] = (at >= 0 ? at : 0); }
-    }
-    if (ok) s->n_value_streams = streams;
-  }
 }
 }  // namespace
 
@@ -49,6 +17,8 @@ int ceres_hip_values_begin(ceres_hip_solver* s, const double* host_values, const
   if (!s->have_structure) return fail(s, CERES_HIP_E_INVALID, "ceres_hip_set_structure has not been called");
   HIP_TRY(s, hipSetDevice(s->opt.device));
   std::lock_guard<std::mutex> lock(s->stream_mu);
+  // (a second _begin would reset stream_row_sent under copies that are still queued; the open session stays as it is)
+  if (s->streaming) return fail(s, CERES_HIP_E_INVALID, "ceres_hip_values_begin between ceres_hip_values_begin and ceres_hip_values_end");
   if (!s->copy_stream) {
     HIP_TRY(s, hipStreamCreateWithFlags(&s->copy_stream, hipStreamNonBlocking));
     HIP_TRY(s, hipEventCreateWithFlags(&s->copy_done, hipEventDisableTiming));
@@ -124,7 +94,10 @@ int ceres_hip_values_end(ceres_hip_solver* s, const double* host_column_scale) {
     }
   }
   HIP_TRY(s, hipEventRecord(s->copy_done, s->copy_stream));
-  HIP_TRY(s, hipStreamWaitEvent(s->stream, s->copy_done, 0));
+  HIP_TRY(s, hipStreamWaitEvent(s->stream, s->copy_done, 0));   // (work queued behind it is ordered without relying on the host)
+  // the HOST waits too: the copies enqueued above read the caller's (pinned) arrays asynchronously, and the caller may write, scale or
+  // free them as soon as this returns (Ceres scales its Jacobian in place right behind the evaluation)
+  HIP_TRY(s, hipEventSynchronize(s->copy_done));
   TRY(load_device(s, s->own_values, s->own_b, nullptr));
   if (host_column_scale) {   // BlockSparseMatrix::ScaleColumns on the copy in HBM (I/block_sparse_matrix.cc:403-450, I/trust_region_minimizer.cc:263-279)
     HIP_TRY(s, hipMemcpyAsync(s->scratch_vec, host_column_scale, sizeof(double) * size_t(h.num_cols), hipMemcpyHostToDevice, s->stream));

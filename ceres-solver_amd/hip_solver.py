@@ -152,6 +152,8 @@ ABI = [
     ("ceres_hip_values_ready", c_int32, [c_void_p, c_int32, c_int32]),
     ("ceres_hip_values_end", c_int32, [c_void_p, _DP]),
     ("ceres_hip_get_stream_stats", c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int32)]),
+    ("ceres_hip_debug_value_streams", c_int32, [POINTER(CBlockStructure), POINTER(c_int32), POINTER(c_int64), POINTER(c_int64)]),
+    ("ceres_hip_debug_read_loaded", c_int32, [c_void_p, _DP, _DP]),
     ("ceres_hip_op_scale_columns", c_int32, [c_void_p, _DP, _DP]),
     ("ceres_hip_time_op", c_int32, [c_void_p, c_int32, c_int32, _DP]),
     ("ceres_hip_get_last_timing", c_int32, [c_void_p, POINTER(CTiming)]),
@@ -490,6 +492,12 @@ class HipLinearSolver:
         if rc != 0:
             raise HipError(f"ceres_hip error {rc}: {self._lib.ceres_hip_last_error(self._h).decode()}")
 
+    def _check_not_streaming(self, rc):
+        """The solve entries report a failure as a FATAL_ERROR summary, like a LinearSolver that could not run; a call the library
+        refused because a streamed upload is open (values_begin without values_end) is the caller's mistake and raises like the others."""
+        if rc != 0 and getattr(self, "_stream_keep", None) is not None:
+            self._check(rc)
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.ceres_hip_destroy(self._h)
@@ -532,6 +540,7 @@ class HipLinearSolver:
         s = CSummary()
         rc = self._lib.ceres_hip_solve(self._h, _p(values), _p(b), _p(D), per_solve_options.q_tolerance,
                                        per_solve_options.r_tolerance, _p(x), byref(s))
+        self._check_not_streaming(rc)
         summary = Summary(s.residual_norm, s.num_iterations, s.termination_type, s.message.decode(errors="replace"))
         if rc != 0:
             summary.termination_type = FATAL_ERROR
@@ -547,6 +556,7 @@ class HipLinearSolver:
         s = CSummary()
         rc = self._lib.ceres_hip_solve_unchanged_values(self._h, _p(D) if D is not None else None, per_solve.q_tolerance,
                                                         per_solve.r_tolerance, _p(x), byref(s))
+        self._check_not_streaming(rc)
         summary = Summary(s.residual_norm, s.num_iterations, s.termination_type, s.message.decode(errors="replace"))
         if rc != 0:
             summary.termination_type = FATAL_ERROR
@@ -557,6 +567,7 @@ class HipLinearSolver:
         """Same with raw device pointers (e.g. torch tensor .data_ptr()); nothing crosses PCIe."""
         s = CSummary()
         rc = self._lib.ceres_hip_solve_device(self._h, d_values, d_b, d_D or None, q_tolerance, r_tolerance, d_x, byref(s))
+        self._check_not_streaming(rc)
         summary = Summary(s.residual_norm, s.num_iterations, s.termination_type, s.message.decode(errors="replace"))
         if rc != 0:
             summary.termination_type = FATAL_ERROR
@@ -614,10 +625,11 @@ class HipLinearSolver:
     # -- the upload hidden behind the evaluator ---------------------------------
     def values_begin(self, values, residuals):
         """values / residuals: the (pinned) host arrays the evaluator is about to fill; kept alive until values_end."""
-        self._stream_keep = (_f64(values, self._values_extent, "values"), _f64(residuals, self._info.num_rows, "residuals"))
-        if self._stream_keep[0] is not values or self._stream_keep[1] is not residuals:
+        keep = (_f64(values, self._values_extent, "values"), _f64(residuals, self._info.num_rows, "residuals"))
+        if keep[0] is not values or keep[1] is not residuals:
             raise ValueError("values_begin needs contiguous float64 arrays (they are filled in place while rows go up)")
         self._check(self._lib.ceres_hip_values_begin(self._h, _p(values), _p(residuals)))
+        self._stream_keep = keep   # (only now: a refused second values_begin leaves the open session's arrays alive)
 
     def values_ready(self, first_row_block: int, num_row_blocks: int):
         """Thread-safe: row blocks [first, first + n) are complete."""
@@ -634,6 +646,13 @@ class HipLinearSolver:
         a, b, k = c_int64(0), c_int64(0), c_int32(0)
         self._check(self._lib.ceres_hip_get_stream_stats(self._h, byref(a), byref(b), byref(k)))
         return int(a.value), int(b.value), int(k.value)
+
+    def read_loaded(self):
+        """(values, residuals) as the device holds them in the handle's own copies (ceres_hip_debug_read_loaded): what a load, an LM step
+        on host values or a streamed upload left in HBM, after the copy stream and the solver's stream have drained."""
+        values, b = np.full(self._values_extent, np.nan), np.full(self._info.num_rows, np.nan)
+        self._check(self._lib.ceres_hip_debug_read_loaded(self._h, _p(values), _p(b)))
+        return values, b
 
     def lm_diagonal(self):
         out = np.full(self._info.num_cols, np.nan)
@@ -904,6 +923,19 @@ def debug_plan(bs: BlockStructure, num_eliminate_blocks: int):
     return {"eligible": True, "n_tiles": nt, "slot_row": row, "slot_cam": cam, "slot_pt": pt, "seg_first": seg & 0xff,
             "seg_last": (seg >> 8) & 0xff, "valid": (seg >> 16) & 1, "tail_a": (seg >> 17) & 63, "has_a": (seg >> 23) & 1,
             "tail_b": (seg >> 24) & 63, "has_b": (seg >> 30) & 1, "tile_kind": kind, "tile_aux": aux}
+
+
+def debug_value_streams(bs: BlockStructure):
+    """The plan of the streamed upload (csrc/plan.cc, PlanValueStreams; no device): (streams, lo, hi) with lo / hi of shape
+    (2, num_row_blocks) — row blocks [r0, r1) own the doubles [lo[k, r0], hi[k, r1 - 1]) of the value array in class k < streams."""
+    lib = load_library()
+    c = bs.as_ctypes()
+    k = c_int32(-1)
+    lo, hi = (np.zeros((2, int(bs.num_row_blocks)), dtype=np.int64) for _ in range(2))
+    rc = lib.ceres_hip_debug_value_streams(byref(c), byref(k), lo.ctypes.data_as(POINTER(c_int64)), hi.ctypes.data_as(POINTER(c_int64)))
+    if rc != 0:
+        raise HipError(f"ceres_hip_debug_value_streams: error {rc}")
+    return int(k.value), lo, hi
 
 
 def debug_cluster_cameras(bs: BlockStructure, num_eliminate_blocks: int, visibility_clustering_type: int = CANONICAL_VIEWS):

@@ -169,7 +169,8 @@ class HipLinearSolver final : public LinearSolver {
   // The upload hidden behind the evaluator (include/ceres_hip.h: ceres_hip_values_begin / _ready / _end): BeginValues before
   // ProgramEvaluator::Evaluate's parallel loop starts writing jacobian->values() and residuals; ValuesReady from any evaluator thread
   // when a run of row blocks is complete; EndValues(jacobian_scaling) after the loop (the UNSCALED values went up: Jacobi scaling happens
-  // on the device); then ComputeLmStepOnStreamedValues.
+  // on the device) and BEFORE jacobian->ScaleColumns() on the host — EndValues sends the rows nobody announced, which must still be
+  // unscaled, and returns when its copies have left the host arrays; then ComputeLmStepOnStreamedValues.
   bool BeginValues(BlockSparseMatrix* jacobian, const double* residuals, Summary* summary = nullptr) {
     Summary local;
     if (!EnsureStructure(jacobian, summary ? summary : &local)) return false;

@@ -246,6 +246,9 @@ int RunStreamedLmStep(const char* name, BlockSparseMatrix* A, const std::vector<
     });
   for (auto& th : pool) th.join();
   if (failed || !solver.EndValues(with_scale ? scale.data() : nullptr)) { std::printf("FAIL %s: streaming: %s\n", name, ceres_hip_last_error(solver.handle())); return 1; }
+  // the Ceres order: EndValues has returned, so the host copy is the caller's again — TrustRegionMinimizer scales its Jacobian in
+  // place now (jacobian_->ScaleColumns, I/trust_region_minimizer.cc:263-279).  The rows EndValues sent itself went up unscaled before this.
+  if (with_scale) for (int i = 0; i < A->num_nonzeros(); ++i) A->mutable_values()[i] = scaled[i];
   const auto r = solver.ComputeLmStepOnStreamedValues(1e4, 1e-13, step.data());
   int64_t early = 0, late = 0; int32_t streams = 0;
   ceres_hip_get_stream_stats(solver.handle(), &early, &late, &streams);

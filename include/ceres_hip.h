@@ -427,7 +427,7 @@ int ceres_hip_lm_compute_step_device(ceres_hip_solver* s, const double* dev_valu
  * values_ of BlockSparseMatrix(use_page_locked_memory), I/block_jacobian_writer.cc:261-262): finished rows can go up while later
  * rows are still being evaluated.
  *   _begin(values, residuals)      before the evaluator starts: the host arrays it will fill (pinned for the copies to be asynchronous;
- *                                  they must stay valid until _end returns)
+ *                                  they must stay valid and — once announced — unwritten until _end returns)
  *   _ready(first_row_block, n)     THREAD-SAFE; row blocks [first, first + n) are complete in both arrays: their value ranges and
  *                                  residuals are enqueued on a copy stream.  Every row block at most once; any order; any granularity.
  *                                  (Layouts whose rows are not one or two monotone value streams — Ceres' own are: all E cells then
@@ -435,6 +435,13 @@ int ceres_hip_lm_compute_step_device(ceres_hip_solver* s, const double* dev_valu
  *   _end(column_scale)             rows nobody announced go up now; the solver's stream waits for the copies; column_scale != NULL:
  *                                  BlockSparseMatrix::ScaleColumns on the copy in HBM (I/block_sparse_matrix.cc:403-450) — the evaluator
  *                                  hands over the UNSCALED Jacobian, Jacobi scaling (I/trust_region_minimizer.cc:263-279) happens here.
+ *                                  The HOST waits for the copies before _end returns: from then on the caller may write, scale or free
+ *                                  both arrays.
+ * ORDER: _end comes BEFORE the caller's own jacobian->ScaleColumns().  _end sends the rows nobody announced (every row, where the layout
+ * has no value streams) from the host array and then scales the copy in HBM: rows that were already scaled on the host would be scaled
+ * twice.  The caller scales its host copy after _end has returned.
+ * Between _begin and _end the device copy is half written: every entry point that reads or replaces the loaded values (ceres_hip_load*,
+ * ceres_hip_solve*, ceres_hip_lm_compute_step*, ceres_hip_op_*, a second _begin) returns CERES_HIP_E_INVALID and leaves the session open.
  * The values then count as loaded by ceres_hip_load: ceres_hip_lm_compute_step(s, NULL, NULL, {.., values_unchanged = 1}, ..) computes the
  * step without another copy (the first pass re-lays the tiles out as after any load).                                              */
 int ceres_hip_values_begin(ceres_hip_solver* s, const double* host_values, const double* host_residuals);
@@ -903,6 +910,14 @@ int ceres_hip_debug_plan(const ceres_hip_block_structure* bs, int32_t num_elimin
                          int64_t* n_tiles, int32_t* slot_row, int32_t* slot_cam, int32_t* slot_pt,
                          uint32_t* slot_seg, int32_t* tile_kind, int32_t* tile_aux, int64_t slot_capacity,
                          char* why_not, int32_t why_capacity);
+
+/* Debug: the plan of the streamed upload (ceres_hip_values_ready).  Pure host code.  *value_streams = 0, 1 or 2; lo / hi (each
+ * 2 * num_row_blocks entries, class-major; either may be NULL): row blocks [r0, r1) own the doubles [lo[k][r0], hi[k][r1 - 1]) of the
+ * value array in class k < *value_streams (1 stream: whole rows; 2: k = 0 the rows' first cells, k = 1 their other cells). */
+int ceres_hip_debug_value_streams(const ceres_hip_block_structure* bs, int32_t* value_streams, int64_t* lo, int64_t* hi);
+/* Debug: the handle's own device copies of the loaded values (values_extent doubles) and residuals (num_rows), after waiting for the
+ * copy stream and the solver's stream.  Either pointer may be NULL. */
+int ceres_hip_debug_read_loaded(ceres_hip_solver* s, double* host_values_out, double* host_residuals_out);
 
 /* Debug: the inner-iteration ordering of a BAL structure (pure host code; what a handle with ceres_hip_bal_set_inner_iterations(p,
  * blocks, ...) runs): group_of_block[num_points + num_cameras] = the group of every block in state order (points, then cameras), -1 for a
