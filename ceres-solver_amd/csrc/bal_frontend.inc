@@ -66,6 +66,13 @@ struct ceres_hip_bal {
   // ceres_hip_bal_create_with_fixed_intrinsics (SubsetManifold on every camera; kernels_subset.hip): bit k set — coordinate 6 + k of every
   // camera is constant.  cs stays 9, cw = 9 - bits; 0 on every other handle
   int intrinsics_mask = 0;
+  // ceres_hip_bal_create_with_shared_intrinsics (kernels_shared.hip): the number of intrinsics groups, 0 on every other handle.  cs stays
+  // 9, cw = 6 (the pose); the tangent is [points | free cameras' poses | groups], n_t = 3 np + 6 nfc + 3 n_groups; every row has an E
+  // cell and a group cell, the rows of free cameras a pose cell between them.  group_of / group_first: a camera's group, a group's
+  // first camera (the one the state check compares the others with, the one that adds the group's norms in Plus)
+  int n_groups = 0;
+  std::vector<int32_t> group_of, group_first;
+  int32_t *d_row_gpos = nullptr, *d_row_sgrp = nullptr, *d_cam_pose = nullptr, *d_cam_group = nullptr, *d_cam_first = nullptr;
   // ceres_hip_bal_evaluate_gradient / ceres_hip_bal_minimize_line_search (line_search.inc): their lists and vectors, made on first use
   struct BalLineSearch* ls = nullptr;
   // ceres_hip_bal_covariance (covariance.inc): its lists and buffers, made on first use
@@ -110,6 +117,29 @@ int bal_parts_collect(ceres_hip_bal* p) {
   HIP_TRY(p->s, p->parts.collect(p->s->stream));
   return 0;
 }
+// Jacobian values of the program: E cells, F cells, and with shared intrinsics a group cell per row
+int64_t bal_num_values(const ceres_hip_bal* p) { return 6 * p->n_rows_e + 2 * p->cw * p->n_rows_f + (p->n_groups ? 6 * p->no : 0); }
+
+// Shared intrinsics: the doubles 6 .. 8 of a group's cameras are one parameter block — bit-identical, checked on the host before any
+// device call of an entry point that takes a state.  0, or CERES_HIP_E_INVALID naming the first offending camera and coordinate.
+int bal_shared_check(ceres_hip_bal* p, const char* fn, const double* state) {
+  if (!p->n_groups) return 0;
+  for (int c = 0; c < p->nc; ++c) {
+    const int f = p->group_first[p->group_of[c]];
+    if (f == c) continue;
+    const double* a = state + 3 * int64_t(p->np) + 9 * int64_t(c) + 6;
+    const double* b = state + 3 * int64_t(p->np) + 9 * int64_t(f) + 6;
+    for (int j = 0; j < 3; ++j) {
+      if (memcmp(a + j, b + j, sizeof(double)) == 0) continue;
+      p->err = std::string(fn) + ": shared intrinsics: camera " + std::to_string(c) + " coordinate " + std::to_string(6 + j) +
+               " differs from camera " + std::to_string(f) + ", the first of group " + std::to_string(p->group_of[c]) +
+               " (the intrinsics of a group must be bit-identical)";
+      return CERES_HIP_E_INVALID;
+    }
+  }
+  return 0;
+}
+
 // cost (and residuals / Jacobian values in the solver's layout) at a device state vector, enqueued: *cost is the set of its partial sums
 // (removed_rows: over the rows whose blocks are both constant instead — the fixed cost)
 int bal_evaluate_enqueue(ceres_hip_bal* p, const double* d_state, bool jacobian, const double* d_scale, double* d_residuals, PartialSet* cost,
@@ -122,7 +152,12 @@ int bal_evaluate_enqueue(ceres_hip_bal* p, const double* d_state, bool jacobian,
   A.state = d_state; A.cam_base = 3 * int64_t(p->np); A.scale = d_scale;
   A.residuals = d_residuals; A.values = jacobian ? p->d_vals : nullptr; A.loss = p->loss;
   int nparts = 0;
-  if (p->intrinsics_mask && jacobian) {   // fixed intrinsics: F cells of 2 x cw (the cost alone has no columns to remove)
+  if (p->n_groups && jacobian) {   // shared intrinsics: a pose cell and a group cell per row (the cost alone has no cell to split)
+    BalEvalSharedArgs H;
+    static_cast<BalEvalArgs&>(H) = A;
+    H.row_fpos = p->d_row_fpos; H.row_scam = p->d_row_scam; H.row_spt = p->d_row_spt; H.row_gpos = p->d_row_gpos; H.row_sgrp = p->d_row_sgrp;
+    HIP_TRY(s, LaunchBalEvaluateShared(H, &nparts, s->stream));
+  } else if (p->intrinsics_mask && jacobian) {   // fixed intrinsics: F cells of 2 x cw (the cost alone has no columns to remove)
     A.row_fpos = p->d_row_fpos; A.row_scam = p->d_row_scam; A.row_spt = p->d_row_spt;   // (uploaded with or without constant blocks)
     HIP_TRY(s, LaunchBalEvaluateSubset(A, p->intrinsics_mask, &nparts, s->stream));
   } else if (p->has_const && jacobian) {   // a reduced program: the cells of constant blocks are neither scaled nor stored
@@ -149,7 +184,7 @@ bool bal_writes_tiles(const ceres_hip_bal* p) {
   const ceres_hip_solver* s = p->s;
   // (the tile evaluator computes the angle-axis Jacobian: quaternion cameras keep the two-pass form — the manifold's <2,3,9> included)
   if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) return false;
-  if (p->intrinsics_mask) return false;   // (the tile evaluator writes <2,3,9> tiles)
+  if (p->intrinsics_mask || p->n_groups) return false;   // (the tile evaluator writes <2,3,9> tiles)
   // (constant blocks: the tile evaluator's records exist for constant cameras alone — constant points leave remainder rows anyway)
   if (p->has_const && !p->d_pack_cam) return false;
   if (const char* e = getenv("CERES_HIP_EVAL_TILES")) if (atoi(e) == 0) return false;
@@ -165,7 +200,7 @@ bool bal_writes_tiles(const ceres_hip_bal* p) {
 // caller-layout copy of the Jacobian exists then — or read them from p->d_vals (CERES_HIP_EVAL_TILES=2: always; 3: never).
 bool bal_camera_pass_evaluates(const ceres_hip_bal* p) {
   if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) return false;   // (the evaluating pass is angle-axis)
-  if (p->intrinsics_mask) return false;                               // (and nine columns wide)
+  if (p->intrinsics_mask || p->n_groups) return false;                // (and nine columns wide)
   if (const char* e = getenv("CERES_HIP_EVAL_TILES")) {
     if (atoi(e) == 2) return false;
     if (atoi(e) == 3) return p->d_cm_obs != nullptr;   // (tests: the evaluating kernel whatever the item length)
@@ -237,6 +272,9 @@ int bal_candidate(ceres_hip_bal* p, const double* x, const double* scale, double
   if (p->is_constrained)
     HIP_TRY(s, LaunchBoundsTrialPoint(bal_bounds_args(p), x, p->d_step, scale, nullptr, bal_bounds_step_size(p), true, p->d_delta, cand, parts,
                                       &n, s->stream));
+  else if (p->n_groups)   // (shared intrinsics: one group step for many cameras; constant poses are copied)
+    HIP_TRY(s, LaunchBalCandidateShared(BalSharedCameras{p->np, p->nc, p->d_cam_pose, p->d_cam_group, p->d_cam_first}, x, p->d_step, scale,
+                                        p->d_delta, cand, parts, &n, s->stream));
   else if (p->intrinsics_mask)   // (fixed intrinsics: a narrower step scattered into the free coordinates, with or without constant blocks)
     HIP_TRY(s, LaunchBalCandidateSubset(BalFreeBlocks{p->has_const ? p->d_free_block : nullptr, p->nfp, p->nfc}, p->intrinsics_mask, p->np, x,
                                         p->d_step, scale, p->d_delta, cand, parts, &n, s->stream));
@@ -310,13 +348,15 @@ void ceres_hip_bal_destroy(ceres_hip_bal* p) {
 
 namespace {
 
-// ceres_hip_bal_create, ceres_hip_bal_create_with_camera, ceres_hip_bal_create_with_constant_blocks and
-// ceres_hip_bal_create_with_fixed_intrinsics (`fn` names the entry point in the messages).  The masks may be NULL; with none set the
+// ceres_hip_bal_create, ceres_hip_bal_create_with_camera, ceres_hip_bal_create_with_constant_blocks,
+// ceres_hip_bal_create_with_fixed_intrinsics and ceres_hip_bal_create_with_shared_intrinsics (`fn` names the entry point in the
+// messages).  The masks may be NULL; with none set the
 // reduction below is the identity, the camera keeps its width and the handle is what it always was.
 ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras, int32_t num_points,
                           int64_t num_observations, const int32_t* camera_index, const int32_t* point_index,
                           const double* observations, const uint8_t* camera_is_constant = nullptr,
-                          const uint8_t* point_is_constant = nullptr, const uint8_t* camera_coordinate_is_constant = nullptr) try {   // (host vectors sized by the caller's counts: no C++ exception crosses the C boundary)
+                          const uint8_t* point_is_constant = nullptr, const uint8_t* camera_coordinate_is_constant = nullptr,
+                          const int32_t* camera_group = nullptr, int32_t num_groups = 0) try {   // (host vectors sized by the caller's counts: no C++ exception crosses the C boundary)
   const std::string name(fn);
   static_assert(kCamAngleAxis == CERES_HIP_CAMERA_ANGLE_AXIS && kCamQuaternion == CERES_HIP_CAMERA_QUATERNION &&
                 kCamQuaternionManifold == CERES_HIP_CAMERA_QUATERNION_MANIFOLD, "device camera models are the ABI's");
@@ -330,6 +370,32 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
     return nullptr;
   }
   const int cs = camera_model == CERES_HIP_CAMERA_ANGLE_AXIS ? 9 : 10;       // state doubles per camera
+  // Shared intrinsics (camera_group != NULL): every camera in exactly one group, every group id used; angle-axis cameras only
+  const int ng = camera_group ? num_groups : 0;
+  std::vector<int32_t> group_first;
+  if (camera_group) {
+    if (camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) {
+      g_create_error = name + ": shared intrinsics are supported for the angle-axis camera only (camera_model " + std::to_string(camera_model) + ")";
+      return nullptr;
+    }
+    if (num_groups <= 0 || num_groups > num_cameras) {
+      g_create_error = name + ": num_groups " + std::to_string(num_groups) + " is not in [1, num_cameras = " + std::to_string(num_cameras) + "]";
+      return nullptr;
+    }
+    group_first.assign(size_t(num_groups), -1);
+    for (int c = 0; c < num_cameras; ++c) {
+      if (camera_group[c] < 0 || camera_group[c] >= num_groups) {
+        g_create_error = name + ": camera " + std::to_string(c) + " has group " + std::to_string(camera_group[c]) + ", not in [0, " + std::to_string(num_groups) + ")";
+        return nullptr;
+      }
+      if (group_first[camera_group[c]] < 0) group_first[camera_group[c]] = c;
+    }
+    for (int g = 0; g < num_groups; ++g) {
+      if (group_first[g] >= 0) continue;
+      g_create_error = name + ": group " + std::to_string(g) + " has no camera (every id in [0, num_groups) must be used)";
+      return nullptr;
+    }
+  }
   // SubsetManifold on every camera (one mask of cs entries; NULL: none): the intrinsics f, k1, k2 of the angle-axis camera alone
   int intrinsics_mask = 0;
   for (int j = 0; camera_coordinate_is_constant && j < cs; ++j) {
@@ -346,8 +412,8 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
     return nullptr;
   }
   // Jacobian columns per camera (tangent): the free coordinates
-  const int cw = (camera_model == CERES_HIP_CAMERA_QUATERNION ? 10 : 9) - ((intrinsics_mask & 1) + ((intrinsics_mask >> 1) & 1) + ((intrinsics_mask >> 2) & 1));
-  const int64_t per_obs = 6 + 2 * cw;                                        // Jacobian values per observation: 24, 26 or 24 (18 .. 22 with fixed intrinsics)
+  const int cw = ng ? 6 : (camera_model == CERES_HIP_CAMERA_QUATERNION ? 10 : 9) - ((intrinsics_mask & 1) + ((intrinsics_mask >> 1) & 1) + ((intrinsics_mask >> 2) & 1));
+  const int64_t per_obs = 6 + 2 * cw + (ng ? 6 : 0);                                        // Jacobian values per observation: 24, 26 or 24 (18 .. 22 with fixed intrinsics, 24 with shared ones)
   if (num_observations * per_obs > int64_t(INT32_MAX)) {  // cell.position is an int in the reference too (I/block_structure.h:64)
     g_create_error = name + ": more than " + std::to_string(int64_t(INT32_MAX) / per_obs / 1000000) +
                      " M observations do not fit 32-bit value positions";
@@ -378,6 +444,10 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
     g_create_error = name + ": more than 2^31 state doubles with constant blocks";
     return nullptr;
   }
+  if (ng && 3 * int64_t(num_points) + cs * int64_t(num_cameras) > int64_t(INT32_MAX)) {   // (row_scam / row_sgrp / row_spt are 32-bit)
+    g_create_error = name + ": more than 2^31 state doubles with shared intrinsics";
+    return nullptr;
+  }
   if (intrinsics_mask && 3 * int64_t(num_points) + cs * int64_t(num_cameras) > int64_t(INT32_MAX)) {   // (row_scam / row_spt are 32-bit)
     g_create_error = name + ": more than 2^31 state doubles with fixed intrinsics";
     return nullptr;
@@ -393,7 +463,9 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
   p->nfc = nfc; p->nfp = nfp; p->has_const = has_const;
   p->camera_model = camera_model; p->cs = cs; p->cw = cw; p->intrinsics_mask = intrinsics_mask;
   p->n_a = 3 * int64_t(num_points) + cs * int64_t(num_cameras);
-  p->n_t = 3 * int64_t(nfp) + cw * int64_t(nfc);
+  p->n_t = 3 * int64_t(nfp) + cw * int64_t(nfc) + 3 * int64_t(ng);
+  p->n_groups = ng; p->group_first = group_first;
+  if (ng) p->group_of.assign(camera_group, camera_group + num_cameras);
   auto bail = [&](const char* what) -> ceres_hip_bal* {
     g_create_error = std::string(what) + ": " + s->err;
     ceres_hip_bal_destroy(p);
@@ -401,17 +473,20 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
   };
   p->row_obs = R.row_obs;
   const int64_t ne = R.num_rows_e;
-  const int ncb = nfp + nfc;
+  const int ncb = nfp + nfc + ng;   // column blocks: points, free cameras (with shared intrinsics: their poses), groups
   std::vector<int32_t> rsz(no, 2), rpos(no), csz(ncb), cpos(ncb), rptr(no + 1), ccol, cval, rcam(no), rpt(no), rfpos(no), rscam(no), rspt(no);
+  std::vector<int32_t> rgpos(ng ? no : 0), rsgrp(ng ? no : 0);
   std::vector<int32_t> frow;   // F cell (in row order) -> row
   std::vector<double> robs(2 * no);
-  ccol.reserve(2 * no); cval.reserve(2 * no); frow.reserve(no);
+  ccol.reserve((ng ? 3 : 2) * no); cval.reserve((ng ? 3 : 2) * no); frow.reserve(no);
   for (int q = 0; q < nfp; ++q) { csz[q] = 3; cpos[q] = 3 * q; }
   for (int c = 0; c < nfc; ++c) { csz[nfp + c] = cw; cpos[nfp + c] = 3 * nfp + cw * c; }
+  for (int g = 0; g < ng; ++g) { csz[nfp + nfc + g] = 3; cpos[nfp + nfc + g] = 3 * nfp + cw * nfc + 3 * g; }
   for (int64_t r = 0; r < no; ++r) if (R.camera_column[camera_index[p->row_obs[r]]] >= 0) frow.push_back(int32_t(r));
   const int64_t nf = int64_t(frow.size());
   p->n_rows_e = ne; p->n_rows_f = nf;
-  const int64_t nvals = 6 * ne + 2 * cw * nf;
+  const int64_t nvals = 6 * ne + 2 * cw * nf + (ng ? 6 * no : 0);
+  int64_t next = 6 * ne;   // (shared intrinsics: a row's pose cell and group cell back to back, in column order)
   for (int64_t r = 0, f = 0; r < no; ++r) {
     const int ob = p->row_obs[r];
     rpos[r] = int32_t(2 * r);
@@ -423,6 +498,13 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
     rscam[r] = cc >= 0 ? 3 * nfp + cw * cc : -1;
     rfpos[r] = -1;
     if (pc >= 0) { ccol.push_back(pc); cval.push_back(int32_t(6 * r)); }                             // E cell (rows with one come first)
+    if (ng) {
+      if (cc >= 0) { rfpos[r] = int32_t(next); next += 12; ccol.push_back(nfp + cc); cval.push_back(rfpos[r]); }   // pose cell
+      const int g = camera_group[rcam[r]];
+      rgpos[r] = int32_t(next); next += 6; rsgrp[r] = 3 * nfp + cw * nfc + 3 * g;
+      ccol.push_back(nfp + nfc + g); cval.push_back(rgpos[r]);                                                     // group cell
+      continue;
+    }
     if (cc >= 0) { rfpos[r] = int32_t(6 * ne + 2 * cw * f++); ccol.push_back(nfp + cc); cval.push_back(rfpos[r]); }   // F cell
   }
   rptr[no] = int32_t(ccol.size());
@@ -463,14 +545,26 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
       p->d_rm_obs = reinterpret_cast<double2*>(md);
     }
   }
-  // fixed intrinsics without constant blocks: the evaluator's per-row positions all the same (kernels_subset.hip has the one form)
-  if (ok && intrinsics_mask && !has_const)
+  // fixed or shared intrinsics without constant blocks: the evaluator's per-row positions all the same (kernels_subset.hip and
+  // kernels_shared.hip have the one form)
+  if (ok && (intrinsics_mask || ng) && !has_const)
     ok = dev_upload(s, &p->d_row_fpos, rfpos) == 0 && dev_upload(s, &p->d_row_scam, rscam) == 0 && dev_upload(s, &p->d_row_spt, rspt) == 0;
+  if (ok && ng) {   // shared intrinsics: the group cell's positions, and Plus' per-camera records (kernels_shared.hip)
+    std::vector<int32_t> cpose(num_cameras), cgrp(num_cameras), cfirst(num_cameras);
+    for (int c = 0; c < num_cameras; ++c) {
+      const int cc = R.camera_column[c];
+      cpose[c] = cc >= 0 ? 3 * nfp + cw * cc : -1;
+      cgrp[c] = 3 * nfp + cw * nfc + 3 * camera_group[c];
+      cfirst[c] = group_first[camera_group[c]] == c;
+    }
+    ok = dev_upload(s, &p->d_row_gpos, rgpos) == 0 && dev_upload(s, &p->d_row_sgrp, rsgrp) == 0 && dev_upload(s, &p->d_cam_pose, cpose) == 0 &&
+         dev_upload(s, &p->d_cam_group, cgrp) == 0 && dev_upload(s, &p->d_cam_first, cfirst) == 0;
+  }
   // the rows' camera / point / pixel in slot order: the tile evaluator's and the evaluating camera-major pass's records (angle-axis only;
   // with constant blocks: constant cameras alone — every row then has its E cell, no row is outside the tiles; nine columns wide: not
   // with fixed intrinsics)
   if (ok && s->path == CERES_HIP_PATH_BAL && !s->plan.slot_bpos.empty() && camera_model == CERES_HIP_CAMERA_ANGLE_AXIS && nfp == num_points &&
-      intrinsics_mask == 0) {
+      intrinsics_mask == 0 && ng == 0) {
     const size_t ns = s->plan.slot_bpos.size();
     // camera records: the free cameras in the solver's order, the constant ones behind them (the identity without constants)
     std::vector<int32_t> rec_of(num_cameras), pack_cam(num_cameras), pack_scale(num_cameras);
@@ -564,6 +658,18 @@ ceres_hip_bal* ceres_hip_bal_create_with_fixed_intrinsics(const ceres_hip_option
                     any ? camera_coordinate_is_constant : nullptr);
 }
 
+ceres_hip_bal* ceres_hip_bal_create_with_shared_intrinsics(const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras,
+                                                           int32_t num_points, int64_t num_observations, const int32_t* camera_index,
+                                                           const int32_t* point_index, const double* observations,
+                                                           const uint8_t* camera_is_constant, const int32_t* camera_group, int32_t num_groups) {
+  // (no grouping: the handle — and the messages — of ceres_hip_bal_create_with_constant_blocks)
+  if (!camera_group)
+    return bal_create("ceres_hip_bal_create_with_constant_blocks", options, camera_model, num_cameras, num_points, num_observations, camera_index,
+                      point_index, observations, camera_is_constant, nullptr);
+  return bal_create("ceres_hip_bal_create_with_shared_intrinsics", options, camera_model, num_cameras, num_points, num_observations, camera_index,
+                    point_index, observations, camera_is_constant, nullptr, nullptr, camera_group, num_groups);
+}
+
 int ceres_hip_bal_reduced_sizes(const ceres_hip_bal* p, int64_t* num_rows, int64_t* num_rows_e, int64_t* num_rows_removed,
                                 int32_t* num_free_cameras, int32_t* num_free_points) {
   if (!p) return CERES_HIP_E_INVALID;
@@ -577,6 +683,7 @@ int ceres_hip_bal_reduced_sizes(const ceres_hip_bal* p, int64_t* num_rows, int64
 
 int ceres_hip_bal_fixed_cost(ceres_hip_bal* p, const double* state, double* fixed_cost) {
   if (!p || !state || !fixed_cost) return CERES_HIP_E_INVALID;
+  if (int rc = bal_shared_check(p, "ceres_hip_bal_fixed_cost", state)) return rc;
   ceres_hip_solver* s = p->s;
   HIP_TRY(s, hipSetDevice(s->opt.device));
   BAL_TRY(p, up(s, p->d_cand, state, size_t(p->n_a)));
@@ -588,7 +695,7 @@ int ceres_hip_bal_sizes(const ceres_hip_bal* p, int64_t* num_parameters, int64_t
   if (!p) return CERES_HIP_E_INVALID;
   if (num_parameters) *num_parameters = p->n_a;
   if (num_residuals) *num_residuals = 2 * p->no;
-  if (num_jacobian_values) *num_jacobian_values = 6 * p->n_rows_e + 2 * p->cw * p->n_rows_f;
+  if (num_jacobian_values) *num_jacobian_values = bal_num_values(p);
   return 0;
 }
 
@@ -642,6 +749,7 @@ int ceres_hip_bal_set_loss(ceres_hip_bal* p, int32_t loss_type, double a, double
 int ceres_hip_bal_evaluate(ceres_hip_bal* p, const double* state, double* cost, double* residuals, double* gradient,
                            double* jacobian_values) {
   if (!p || !state || !cost) return CERES_HIP_E_INVALID;
+  if (int rc = bal_shared_check(p, "ceres_hip_bal_evaluate", state)) return rc;
   ceres_hip_solver* s = p->s;
   HIP_TRY(s, hipSetDevice(s->opt.device));
   BAL_TRY(p, up(s, p->d_x, state, size_t(p->n_a)));
@@ -651,7 +759,7 @@ int ceres_hip_bal_evaluate(ceres_hip_bal* p, const double* state, double* cost, 
   if (jac) {
     bal_set_camera_eval(p, false);
     BAL_TRY(p, load_device(s, p->d_vals, p->d_res, nullptr));
-    if (jacobian_values) BAL_TRY(p, down(s, jacobian_values, p->d_vals, size_t(6 * p->n_rows_e + 2 * p->cw * p->n_rows_f)));
+    if (jacobian_values) BAL_TRY(p, down(s, jacobian_values, p->d_vals, size_t(bal_num_values(p))));
     if (gradient) {
       BAL_TRY(p, op_jtb(s, p->d_grad));
       BAL_TRY(p, down(s, gradient, p->d_grad, size_t(p->n_t)));
@@ -671,6 +779,10 @@ int ceres_hip_debug_bal_evaluate_tiles_timing(ceres_hip_bal* p, const double* st
   }
   if (p->intrinsics_mask) {
     p->err = "ceres_hip_debug_bal_evaluate_tiles_timing: the tile evaluator is not supported on handles with fixed intrinsics";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
+  if (p->n_groups) {
+    p->err = "ceres_hip_debug_bal_evaluate_tiles_timing: the tile evaluator is not supported on handles with shared intrinsics";
     return CERES_HIP_E_UNSUPPORTED;
   }
   HIP_TRY(s, hipSetDevice(s->opt.device));
@@ -717,6 +829,15 @@ int ceres_hip_bal_minimize(ceres_hip_bal* p, const ceres_hip_minimizer_options* 
   if (!p || !o || !state || !S) return CERES_HIP_E_INVALID;
   ceres_hip_solver* s = p->s;
   hipStream_t st = s->stream;
+  if (int rc = bal_shared_check(p, "ceres_hip_bal_minimize", state)) return rc;
+  if (p->n_groups && s->world > 1) {
+    p->err = "ceres_hip_bal_minimize: shared intrinsics are not supported on sharded handles";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
+  if (p->n_groups && p->inner_blocks != CERES_HIP_INNER_NONE) {   // (unreachable through ceres_hip_bal_set_inner_iterations)
+    p->err = "ceres_hip_bal_minimize: inner iterations are not supported on handles with shared intrinsics";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
   if (p->is_constrained) {   // Program::IsFeasible for the constant blocks (I/program.cc:240-289), before any device call
     const std::string why = bal_bounds_constant_infeasible(p, state);
     if (!why.empty()) {

@@ -226,6 +226,8 @@ int ceres_hip_bal_set_bounds(ceres_hip_bal* p, const double* lower, const double
     if (lo >= hi && bal_bounds_coordinate(p, i, &block, &j))
       return refuse(CERES_HIP_E_INVALID, ls_format("ParameterBlock: %s has at least one infeasible bound. First infeasible bound is at index: %d. "
                                                    "Lower bound: %.17g, upper bound: %.17g", block.c_str(), j, lo, hi));
+    // (shared intrinsics: a bound on one camera's intrinsics would be a bound on its group's block; bounds that constrain nothing pass)
+    if (p->n_groups && (lo > -dmax || hi < dmax)) return refuse(CERES_HIP_E_UNSUPPORTED, "bounds are not supported on handles with shared intrinsics");
     constrained = constrained || lo > -dmax || hi < dmax;
   }
   if (constrained) {

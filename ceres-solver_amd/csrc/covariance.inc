@@ -269,6 +269,7 @@ int ceres_hip_bal_covariance(ceres_hip_bal* p, const ceres_hip_covariance_option
   if (!std::isfinite(o.min_scaled_pivot) || o.min_scaled_pivot < 0.0) return refuse(CERES_HIP_E_INVALID, "min_scaled_pivot must be finite and >= 0");
   ceres_hip_solver* s = p->s;
   if (p->intrinsics_mask) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with fixed intrinsics");
+  if (p->n_groups) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with shared intrinsics");
   if (!is_dense_schur(s)) return refuse(CERES_HIP_E_UNSUPPORTED, "the handle's linear solver is not CERES_HIP_DENSE_SCHUR");
   if (s->world > 1) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on sharded handles");
   const int64_t num_blocks = int64_t(p->np) + p->nc;

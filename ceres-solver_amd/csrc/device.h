@@ -740,6 +740,28 @@ hipError_t LaunchBalEvaluateSubset(const BalEvalConstArgs& A, int mask, int* npa
 hipError_t LaunchBalCandidateSubset(const BalFreeBlocks& B, int mask, int64_t n_points, const double* x, const double* step, const double* scale,
                                     double* delta, double* cand, double* partials, int* nparts, hipStream_t stream);
 
+// ---- shared camera intrinsics (kernels_shared.hip; ceres_hip_bal_create_with_shared_intrinsics) ----
+// The Jacobian evaluation of a program whose column blocks are points (3), free cameras' poses (6) and intrinsics groups (3): columns
+// 0 .. 5 of the corrected 2 x 9 camera Jacobian go to the pose cell at row_fpos (-1: a constant camera, no pose cell; scale from
+// row_scam), columns 6 .. 8 to the group cell at row_gpos (scale from row_sgrp).  An argument type of its own, as BalEvalConstArgs is.
+struct BalEvalSharedArgs : BalEvalConstArgs {
+  const int32_t* row_gpos = nullptr;
+  const int32_t* row_sgrp = nullptr;
+};
+hipError_t LaunchBalEvaluateShared(const BalEvalSharedArgs& A, int* nparts, hipStream_t stream);
+// Plus on such a handle: one work item per block, n_points points (all free, tangent entries at 3 i) then n_cameras cameras.  Camera c:
+// pose += step .* scale at cam_pose[c] (-1: constant — the pose is copied), intrinsics += the group's scaled step at cam_group[c], the
+// same arithmetic for every member; cam_first[c] != 0: the camera writes its group's delta and adds its |x|^2 and |delta|^2 terms.
+struct BalSharedCameras {
+  int64_t n_points = 0, n_cameras = 0;
+  const int32_t* cam_pose = nullptr;
+  const int32_t* cam_group = nullptr;
+  const int32_t* cam_first = nullptr;
+};
+// partials as LaunchBalCandidateFree's: [0..g) = |x|^2 over the program's parameter blocks, [g..2g) = |delta|^2
+hipError_t LaunchBalCandidateShared(const BalSharedCameras& B, const double* x, const double* step, const double* scale, double* delta,
+                                    double* cand, double* partials, int* nparts, hipStream_t stream);
+
 // ---- bound constraints (kernels_bounds.hip; bounds.inc: ceres_hip_bal_set_bounds) ----
 // Problem::SetParameterLowerBound / SetParameterUpperBound: lower / upper in the state's (ambient) layout, no bound = -inf / +inf.  Plus
 // is x + delta on every handle that takes bounds (angle-axis and Euclidean quaternion cameras), so a coordinate's ambient and tangent

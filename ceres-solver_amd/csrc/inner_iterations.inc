@@ -319,6 +319,10 @@ int ceres_hip_bal_set_inner_iterations(ceres_hip_bal* p, int32_t blocks, double 
     p->err = "ceres_hip_bal_set_inner_iterations: inner iterations are not supported with quaternion cameras";
     return CERES_HIP_E_UNSUPPORTED;
   }
+  if (blocks != CERES_HIP_INNER_NONE && p->n_groups) {   // (kernels_inner.hip: every camera block owns its nine coordinates)
+    p->err = "ceres_hip_bal_set_inner_iterations: inner iterations are not supported on handles with shared intrinsics";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
   if (blocks != CERES_HIP_INNER_NONE && p->intrinsics_mask) {   // (kernels_inner.hip: camera blocks of nine free coordinates)
     p->err = "ceres_hip_bal_set_inner_iterations: inner iterations are not supported on handles with fixed intrinsics";
     return CERES_HIP_E_UNSUPPORTED;
@@ -338,6 +342,7 @@ int ceres_hip_bal_inner_iterate(ceres_hip_bal* p, double* state, double* cost_be
   if (!state || !cost_before || !cost_after) return refuse(CERES_HIP_E_INVALID, "NULL state or cost");
   if (p->camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported with quaternion cameras");
   if (p->intrinsics_mask) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with fixed intrinsics");
+  if (p->n_groups) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with shared intrinsics");
   if (p->is_constrained) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with bounds");   // (the passes do not project)
   if (p->inner_blocks == CERES_HIP_INNER_NONE) return refuse(CERES_HIP_E_INVALID, "no inner iterations set (ceres_hip_bal_set_inner_iterations)");
   if (s->world > 1) return refuse(CERES_HIP_E_UNSUPPORTED, "not on sharded handles");

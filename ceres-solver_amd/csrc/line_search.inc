@@ -595,6 +595,10 @@ int ceres_hip_bal_evaluate_gradient(ceres_hip_bal* p, const double* state, doubl
     p->err = "ceres_hip_bal_evaluate_gradient: not supported on sharded handles";
     return CERES_HIP_E_UNSUPPORTED;
   }
+  if (p->n_groups) {   // (kernels_line_search.hip sums nine columns per camera, none over a group)
+    p->err = "ceres_hip_bal_evaluate_gradient: not supported on handles with shared intrinsics";
+    return CERES_HIP_E_UNSUPPORTED;
+  }
   if (p->intrinsics_mask) {   // (kernels_line_search.hip sums nine columns per camera)
     p->err = "ceres_hip_bal_evaluate_gradient: not supported on handles with fixed intrinsics";
     return CERES_HIP_E_UNSUPPORTED;
@@ -627,6 +631,7 @@ int ceres_hip_bal_minimize_line_search(ceres_hip_bal* p, const ceres_hip_line_se
   ceres_hip_solver* s = p->s;
   if (s->world > 1) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on sharded handles");
   if (p->intrinsics_mask) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with fixed intrinsics");
+  if (p->n_groups) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with shared intrinsics");
   if (p->is_constrained) return refuse(CERES_HIP_E_INVALID, "LINE_SEARCH Minimizer does not support bounds.");   // I/line_search_preprocessor.cc:47-51
   hipStream_t st = s->stream;
   HIP_TRY(s, hipSetDevice(s->opt.device));

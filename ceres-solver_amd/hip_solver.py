@@ -210,6 +210,8 @@ ABI += [
     ("ceres_hip_bal_create_with_fixed_intrinsics", c_void_p, [POINTER(COptions), c_int32, c_int32, c_int32, c_int64, POINTER(c_int32),
                                                               POINTER(c_int32), _DP, POINTER(ctypes.c_uint8), POINTER(ctypes.c_uint8),
                                                               POINTER(ctypes.c_uint8)]),
+    ("ceres_hip_bal_create_with_shared_intrinsics", c_void_p, [POINTER(COptions), c_int32, c_int32, c_int32, c_int64, POINTER(c_int32),
+                                                               POINTER(c_int32), _DP, POINTER(ctypes.c_uint8), POINTER(c_int32), c_int32]),
     ("ceres_hip_bal_reduced_sizes", c_int32, [c_void_p, POINTER(c_int64), POINTER(c_int64), POINTER(c_int64), POINTER(c_int32),
                                               POINTER(c_int32)]),
     ("ceres_hip_bal_fixed_cost", c_int32, [c_void_p, _DP, _DP]),
@@ -1265,10 +1267,17 @@ class BalProblem:
     mask of nine — the intrinsics held fixed on all cameras while poses and points move; angle-axis cameras only.  The state stays
     nine per camera (marked coordinates are read, never written); `camera_tangent_size` = 9 - (number marked) is the width of a
     camera in the gradient, the step and the Jacobian — see ceres_hip_bal_create_with_fixed_intrinsics in include/ceres_hip.h for what
-    such a handle offers."""
+    such a handle offers.
+
+    camera_groups (shared intrinsics: one [f, k1, k2] parameter block per group of cameras beside a 6-wide pose block per camera, as
+    examples/libmv_bundle_adjuster.cc builds its problem): a sequence of num_cameras ints in [0, num_groups), every id used; angle-axis
+    cameras only, exclusive with constant_intrinsics and constant_points.  The state stays nine per camera, the intrinsics of a group
+    bit-identical in all its cameras; the gradient and the step are [points | free cameras' poses | groups]
+    (`num_effective_parameters`), `camera_tangent_size` is 6 and `num_intrinsics_groups` the number of groups; constant_cameras holds
+    poses constant — see ceres_hip_bal_create_with_shared_intrinsics in include/ceres_hip.h for what such a handle offers."""
 
     def __init__(self, options: LinearSolverOptions, num_cameras, num_points, camera_index, point_index, observations,
-                 camera_model="angle_axis", constant_cameras=None, constant_points=None, constant_intrinsics=None):
+                 camera_model="angle_axis", constant_cameras=None, constant_points=None, constant_intrinsics=None, camera_groups=None):
         self._lib = load_library()
         self.options = options
         if isinstance(camera_model, str):
@@ -1291,7 +1300,21 @@ class BalProblem:
         cm = _constant_mask(constant_cameras, self.num_cameras, "constant_cameras")
         pm = _constant_mask(constant_points, self.num_points, "constant_points")
         im = _intrinsics_mask(constant_intrinsics, 9 if self.camera_model == CAMERA_ANGLE_AXIS else 10)
-        if im is not None:
+        self.num_intrinsics_groups = 0
+        if camera_groups is not None:
+            if im is not None or pm is not None:
+                raise ValueError("camera_groups cannot be combined with constant_intrinsics or constant_points")
+            groups = np.ascontiguousarray(camera_groups, dtype=np.int32).reshape(-1)
+            if groups.shape[0] != self.num_cameras:
+                raise ValueError(f"camera_groups has one entry per camera: {self.num_cameras}, got {groups.shape[0]}")
+            # (the number of groups is the largest id + 1: an unused or negative id, or a quaternion model, is the library's refusal)
+            ng = int(groups.max()) + 1
+            self._h = self._lib.ceres_hip_bal_create_with_shared_intrinsics(byref(c), self.camera_model, self.num_cameras, self.num_points,
+                                                                            self.num_observations, cam.ctypes.data_as(POINTER(c_int32)),
+                                                                            pt.ctypes.data_as(POINTER(c_int32)), _p(obs), _u8p(cm),
+                                                                            groups.ctypes.data_as(POINTER(c_int32)), ng)
+            self.num_intrinsics_groups = ng
+        elif im is not None:
             self._h = self._lib.ceres_hip_bal_create_with_fixed_intrinsics(byref(c), self.camera_model, self.num_cameras, self.num_points,
                                                                            self.num_observations, cam.ctypes.data_as(POINTER(c_int32)),
                                                                            pt.ctypes.data_as(POINTER(c_int32)), _p(obs), _u8p(cm), _u8p(pm),
@@ -1318,6 +1341,8 @@ class BalProblem:
         self.camera_state_size = 9 if self.camera_model == CAMERA_ANGLE_AXIS else 10
         # Jacobian columns per camera: the tangent of the manifold, less the coordinates constant_intrinsics marks
         self.camera_tangent_size = (10 if self.camera_model == CAMERA_QUATERNION else 9) - (int(im.sum()) if im is not None else 0)
+        if self.num_intrinsics_groups:   # (the pose; the intrinsics are the groups' blocks)
+            self.camera_tangent_size = 6
         self.num_rows = self.num_residuals // 2   # (= num_observations without constant blocks)
 
     @classmethod

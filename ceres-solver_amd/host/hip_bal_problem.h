@@ -4,6 +4,7 @@
 #ifndef CERES_HIP_HOST_BAL_PROBLEM_H_
 #define CERES_HIP_HOST_BAL_PROBLEM_H_
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <stdexcept>
@@ -104,9 +105,16 @@ class HipBalProblem {
   // on all cameras — only the intrinsics, coordinates 6 .. 8, of the angle-axis camera (ceres_hip_bal_create_with_fixed_intrinsics: the
   // state stays nine per camera, a camera is CameraTangentSize() wide in the gradient and the Jacobian; what such a handle refuses is
   // listed in include/ceres_hip.h).
+  // camera_group (shared intrinsics: one [f k1 k2] parameter block per group beside a 6-wide pose block per camera, as
+  // examples/libmv_bundle_adjuster.cc:697-728 adds its residual blocks): empty = none, else one group id in [0, num_groups) per camera,
+  // every id used; angle-axis cameras only, not together with constant points or a coordinate mask
+  // (ceres_hip_bal_create_with_shared_intrinsics: the state stays nine per camera, a group's intrinsics bit-identical in its cameras;
+  // the gradient is [points | free cameras' poses | groups], CameraTangentSize() is 6; camera_is_constant holds poses constant).
   HipBalProblem(const LinearSolver::Options& options, const BalData& d, int camera_model = CERES_HIP_CAMERA_ANGLE_AXIS,
                 const std::vector<uint8_t>& camera_is_constant = {}, const std::vector<uint8_t>& point_is_constant = {},
-                const std::vector<uint8_t>& camera_coordinate_is_constant = {}) {
+                const std::vector<uint8_t>& camera_coordinate_is_constant = {}, const std::vector<int32_t>& camera_group = {}) {
+    if (!camera_group.empty() && (camera_group.size() != size_t(d.num_cameras) || !point_is_constant.empty() || !camera_coordinate_is_constant.empty()))
+      throw std::invalid_argument("HipBalProblem: camera_group has one entry per camera and excludes constant points and a coordinate mask");
     if ((!camera_is_constant.empty() && camera_is_constant.size() != size_t(d.num_cameras)) ||
         (!point_is_constant.empty() && point_is_constant.size() != size_t(d.num_points)))
       throw std::invalid_argument("HipBalProblem: a constant-block mask has one entry per block");
@@ -122,7 +130,14 @@ class HipBalProblem {
     o.max_num_iterations = options.max_num_iterations;
     o.residual_reset_period = options.residual_reset_period;
     o.device = options.device;
-    if (!camera_coordinate_is_constant.empty())
+    if (!camera_group.empty()) {
+      for (int32_t g : camera_group) num_intrinsics_groups_ = std::max(num_intrinsics_groups_, g + 1);
+      camera_tangent_size_ = 6;
+      handle_ = ceres_hip_bal_create_with_shared_intrinsics(&o, camera_model, d.num_cameras, d.num_points, int64_t(d.camera_index.size()),
+                                                            d.camera_index.data(), d.point_index.data(), d.observations.data(),
+                                                            camera_is_constant.empty() ? nullptr : camera_is_constant.data(),
+                                                            camera_group.data(), num_intrinsics_groups_);
+    } else if (!camera_coordinate_is_constant.empty())
       handle_ = ceres_hip_bal_create_with_fixed_intrinsics(&o, camera_model, d.num_cameras, d.num_points, int64_t(d.camera_index.size()),
                                                            d.camera_index.data(), d.point_index.data(), d.observations.data(),
                                                            camera_is_constant.empty() ? nullptr : camera_is_constant.data(),
@@ -148,6 +163,7 @@ class HipBalProblem {
   int NumResiduals() const { return int(num_residuals_); }     // Evaluator::NumResiduals, :158
   int NumEffectiveParameters() const { return int(num_effective_parameters_); }   // Evaluator::NumEffectiveParameters: the gradient's length
   int CameraTangentSize() const { return camera_tangent_size_; }   // Jacobian columns per free camera (Manifold::TangentSize of the block)
+  int NumIntrinsicsGroups() const { return num_intrinsics_groups_; }   // shared intrinsics: the 3-wide blocks behind the poses (0: none)
   // What Program::RemoveFixedBlocks left: rows kept, rows with an E cell (they come first), rows removed (both blocks constant), free
   // cameras, free points; any pointer may be null
   bool ReducedSizes(int64_t* num_rows, int64_t* num_rows_e, int64_t* num_rows_removed, int32_t* num_free_cameras, int32_t* num_free_points) const {
@@ -252,6 +268,7 @@ class HipBalProblem {
   ceres_hip_bal* handle_ = nullptr;
   int64_t num_parameters_ = 0, num_residuals_ = 0, num_jacobian_values_ = 0, num_effective_parameters_ = 0;
   int camera_tangent_size_ = 9;
+  int32_t num_intrinsics_groups_ = 0;
 };
 
 }  // namespace ceres_hip

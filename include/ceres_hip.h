@@ -555,6 +555,45 @@ ceres_hip_bal* ceres_hip_bal_create_with_fixed_intrinsics(const ceres_hip_option
                                                           const int32_t* point_index, const double* observations,
                                                           const uint8_t* camera_is_constant, const uint8_t* point_is_constant,
                                                           const uint8_t* camera_coordinate_is_constant /* cs entries */);
+/* Shared camera intrinsics: one 3-wide parameter block [f k1 k2] per GROUP of cameras beside a 6-wide pose block [angle-axis(3) t(3)]
+ * per camera (examples/libmv_bundle_adjuster.cc:697-728: every residual block of a camera's images on the camera's intrinsics block).
+ * camera_group: num_cameras entries in [0, num_groups); NULL: exactly the handle ceres_hip_bal_create_with_constant_blocks builds
+ * (num_groups is not read).  Angle-axis cameras only; every camera belongs to exactly one group, every id in [0, num_groups) is used.
+ *   - STATE: ambient and unchanged, 3 n_p + 9 n_c doubles.  The intrinsics of a group are the doubles 6 .. 8 of its cameras and must
+ *     be BIT-IDENTICAL within a group: ceres_hip_bal_evaluate, ceres_hip_bal_minimize and ceres_hip_bal_fixed_cost check it on the
+ *     host before any device call (CERES_HIP_E_INVALID; the message names the first offending camera and coordinate).  After
+ *     ceres_hip_bal_minimize every camera of a group holds the same bits again.
+ *   - TANGENT: [points | poses of the free cameras | groups], 3 n_p + 6 (free cameras) + 3 num_groups entries
+ *     (ceres_hip_bal_num_effective_parameters).
+ *   - COLUMN BLOCKS of the program: points (3), the free cameras' poses (6), groups (3), in that order.  A row has an E cell, a pose
+ *     cell (2 x 6) unless its camera is constant, and a group cell (2 x 3).
+ *   - VALUES: [E cells, 6 per row | per row, back to back in column order: pose cell 12, group cell 6] — 24 per row of a free camera.
+ *   - JACOBIAN: the ambient 2 x 9 one after the Corrector; columns 0 .. 5 go to the pose cell, columns 6 .. 8 to the group cell, then
+ *     the Jacobi scale.  A group's columns of J hold the rows of all its cameras; J^T r, column norms and the LM diagonal are the
+ *     linear solver's operators over this structure.
+ *   - PLUS: pose += step; every camera of group g gets x[6 .. 8] + delta_g — the same arithmetic on the same bits for every member.
+ *   - The gradient's max norm is |g_i|_inf over the tangent, the step norm the tangent |delta|; |x| of the parameter-tolerance test
+ *     counts each group's three doubles ONCE and a constant camera's pose not at all (the program's parameter blocks).
+ *   - camera_is_constant (NULL-able) holds a camera's POSE constant; its rows keep the E and the group cell, its group stays free.
+ *     No row is removed, the fixed cost is 0.  Constant points are not offered by this creator.
+ *   - Which kernels run is ceres_hip_set_structure's decision (ceres_hip_get_info), made from the structure alone: one or two groups
+ *     take the fused <2,3,6> path with the 4- or 8-scalar shared strip, constant cameras being its rows without a camera cell — with
+ *     CGNR too, since this front end hands over the elimination order; three or more groups exceed the strip and run the generic
+ *     kernels, and so does a grouping in which a group has a single camera.  The loop evaluates in the caller layout.
+ * NULL (message in ceres_hip_bal_last_error(NULL)), before any device call: a quaternion camera model, num_groups <= 0 or
+ * > num_cameras, a group id out of range, an unused group id, and what ceres_hip_bal_create_with_constant_blocks refuses.
+ * On such a handle ceres_hip_bal_evaluate, ceres_hip_bal_minimize (LEVENBERG_MARQUARDT on ITERATIVE_SCHUR, CGNR and DENSE_SCHUR, both
+ * DOGLEG types on DENSE_SCHUR), ceres_hip_bal_set_loss, ceres_hip_bal_sizes, ceres_hip_bal_reduced_sizes,
+ * ceres_hip_bal_get_row_order and ceres_hip_bal_fixed_cost work as usual.  CERES_HIP_E_UNSUPPORTED, with a message that says "shared
+ * intrinsics": ceres_hip_bal_set_inner_iterations with anything but NONE, ceres_hip_bal_inner_iterate,
+ * ceres_hip_bal_evaluate_gradient, ceres_hip_bal_minimize_line_search, ceres_hip_bal_covariance, ceres_hip_bal_set_bounds with a
+ * finite bound, ceres_hip_debug_bal_evaluate_tiles_timing, and ceres_hip_bal_minimize on a sharded handle. */
+ceres_hip_bal* ceres_hip_bal_create_with_shared_intrinsics(const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras,
+                                                           int32_t num_points, int64_t num_observations, const int32_t* camera_index,
+                                                           const int32_t* point_index, const double* observations,
+                                                           const uint8_t* camera_is_constant /* NULL-able */,
+                                                           const int32_t* camera_group /* num_cameras entries in [0, num_groups) */,
+                                                           int32_t num_groups);
 /* What the reduction made of the problem (all NULL-able): rows kept, rows with an E cell (they come first), rows dropped because both
  * blocks are constant, free cameras, free points. */
 int ceres_hip_bal_reduced_sizes(const ceres_hip_bal* p, int64_t* num_rows, int64_t* num_rows_e, int64_t* num_rows_removed,
