@@ -23,7 +23,7 @@ SOURCES = (["plan.cc", "visibility.cc", "kernels_generic.hip", "kernels_cg.hip",
            ["kernels_schur.hip", "kernels_cluster.hip", "kernels_evaluator.hip", "kernels_quaternion.hip", "kernels_constant.hip", "kernels_subset.hip", "kernels_shared.hip", "kernels_bounds.hip", "kernels_inner.hip", "kernels_dogleg.hip", "kernels_line_search.hip", "kernels_line_search_quat.hip", "kernels_covariance.hip", "solver.hip"])
 # visibility.cc: the clustering is compared bit-for-bit with a restatement in the tests — no contraction of a * b + c into one rounding
 EXTRA_FLAGS = {"visibility.cc": ["-ffp-contract=off"]}
-HEADERS = ["common.h", "device.h", "p2p.h", "snavely.h", "bal_evaluate.h", "robust_loss.h", "bal_frontend.inc", "constant_blocks.inc", "inner_iterations.inc", "dogleg.inc", "line_search.inc", "bounds.inc", "covariance.inc", "line_search_gradient.h", "quaternion_plus.h", "reduce.h", "partial_sums.h", "solver_comm.inc", "solver_stream.inc", "solver_ops.inc", "solver_debug.inc", "kernels_bal.inc", os.path.join("..", "..", "include", "ceres_hip.h")]
+HEADERS = ["common.h", "device.h", "p2p.h", "snavely.h", "bal_evaluate.h", "robust_loss.h", "bal_frontend.inc", "constant_blocks.inc", "inner_iterations.inc", "dogleg.inc", "line_search.inc", "bounds.inc", "covariance.inc", "line_search_gradient.h", "quaternion_plus.h", "reduce.h", "partial_sums.h", "bal_layout.h", "solver_comm.inc", "solver_stream.inc", "solver_ops.inc", "solver_debug.inc", "kernels_bal.inc", os.path.join("..", "..", "include", "ceres_hip.h")]
 HOST_DRIVER_SRC = os.path.join(HERE, "host", "host_driver.cc")
 HOST_DRIVER = os.path.join(HERE, "host", "host_driver")
 

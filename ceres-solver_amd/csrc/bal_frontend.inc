@@ -12,6 +12,7 @@
 // The loop below follows the reference statement by statement (the same restatement as
 // oracle/bal_harness.cc, which is what the parity tests compare it with); only the places
 // where vectors live differ: everything of size num_parameters / num_residuals stays in HBM.
+#include "bal_layout.h"
 
 struct ceres_hip_bal {
   ceres_hip_solver* s = nullptr;
@@ -119,6 +120,37 @@ int bal_parts_collect(ceres_hip_bal* p) {
 }
 // Jacobian values of the program: E cells, F cells, and with shared intrinsics a group cell per row
 int64_t bal_num_values(const ceres_hip_bal* p) { return 6 * p->n_rows_e + 2 * p->cw * p->n_rows_f + (p->n_groups ? 6 * p->no : 0); }
+// A block's index among the free ones, -1: constant — the identity on a handle without constant blocks (which keeps no map)
+int bal_point_column(const ceres_hip_bal* p, int q) { return p->has_const ? p->pt_col[q] : q; }
+int bal_camera_column(const ceres_hip_bal* p, int c) { return p->has_const ? p->cam_col[c] : c; }
+
+// a pixel list (two doubles per entry) as the kernels take it
+int dev_upload_pixels(ceres_hip_solver* s, double2** d, const std::vector<double>& pixels) {
+  double* q = nullptr;
+  TRY(dev_upload(s, &q, pixels));
+  *d = reinterpret_cast<double2*>(q);
+  return 0;
+}
+
+// The handle's rows back on the host for the lists built on first use: the arrays asked for, copied on the solver's stream, one synchronisation.
+// The handle keeps no host copy — 28 bytes per row.  fpos: the value position of a row's F cell; a handle that uploaded none has one in every row.
+enum : int { kRowCam = 1, kRowPt = 2, kRowPixel = 4, kRowFpos = 8 };
+struct BalHostRows { std::vector<int32_t> cam, pt, fpos; std::vector<double> pixel; };
+int bal_fetch_rows(ceres_hip_bal* p, int which, BalHostRows& H) {
+  ceres_hip_solver* s = p->s;
+  const size_t no = size_t(p->no);
+  auto fetch = [&](auto& host, const void* dev, size_t n) { host.resize(n); return hipMemcpyAsync(host.data(), dev, n * sizeof(host[0]), hipMemcpyDeviceToHost, s->stream); };
+  if (which & kRowCam) HIP_TRY(s, fetch(H.cam, p->d_row_cam, no));
+  if (which & kRowPt) HIP_TRY(s, fetch(H.pt, p->d_row_pt, no));
+  if (which & kRowPixel) HIP_TRY(s, fetch(H.pixel, p->d_row_obs, 2 * no));
+  if ((which & kRowFpos) && p->d_row_fpos) HIP_TRY(s, fetch(H.fpos, p->d_row_fpos, no));
+  HIP_TRY(s, hipStreamSynchronize(s->stream));
+  if ((which & kRowFpos) && !p->d_row_fpos) {
+    H.fpos.resize(no);
+    for (size_t r = 0; r < no; ++r) H.fpos[r] = int32_t(6 * p->n_rows_e + 2 * int64_t(p->cw) * int64_t(r));
+  }
+  return 0;
+}
 
 // Shared intrinsics: the doubles 6 .. 8 of a group's cameras are one parameter block — bit-identical, checked on the host before any
 // device call of an entry point that takes a state.  0, or CERES_HIP_E_INVALID naming the first offending camera and coordinate.
@@ -218,22 +250,29 @@ void bal_set_camera_eval(ceres_hip_bal* p, bool on) {
   I.ev_loss = p->loss;
 }
 
+// The tile-order evaluator's arguments, all but the room for its partial sums; values: where the F cells' caller-layout copy goes, or nullptr
+BalEvalTilesConstArgs bal_tile_args(const ceres_hip_bal* p, const double* d_state, const double* d_scale, double* values, int debug_flags) {
+  const ceres_hip_solver* s = p->s;
+  BalEvalTilesConstArgs T;
+  T.debug_flags = debug_flags;
+  T.e.n_rows = p->no; T.e.row_cam = p->d_row_cam; T.e.row_pt = p->d_row_pt; T.e.row_obs = p->d_row_obs;
+  T.e.state = d_state; T.e.cam_base = 3 * int64_t(p->np); T.e.scale = d_scale;
+  T.e.residuals = p->d_res; T.e.values = values; T.e.loss = p->loss;
+  T.n_tiles = s->plan.n_tiles; T.slot_bpos = s->d_slot_bpos; T.slot_fpos = s->d_slot_fpos;
+  T.J_out = s->d_J; T.tile_pitch = s->ops->tile_pitch; T.b_out = s->d_bt;
+  T.slot_cam = p->d_slot_cam; T.slot_pt = p->d_slot_pt; T.slot_obs = p->d_slot_obs; T.pt_pack = p->d_pt_pack; T.cam_pack = p->d_cam_pack;
+  T.pack_cam = p->d_pack_cam; T.pack_scale = p->d_pack_scale; T.n_pack_cams = p->nc; T.scrap = p->d_scrap;   // (constant cameras; nullptr otherwise)
+  return T;
+}
+
 // Cost, residuals and the (scaled) Jacobian at a device state vector, the Jacobian written STRAIGHT INTO THE TILES (kernels_evaluator.hip):
 // afterwards the solver holds loaded, packed values — its first pass over J gathers nothing.  Of the caller layout only the F cells
 // exist (p->d_vals; the camera-major preconditioner pass reads them there).  Enqueued, as bal_evaluate_enqueue.
 int bal_evaluate_into_tiles(ceres_hip_bal* p, const double* d_state, const double* d_scale, PartialSet* cost, int debug_flags = 0) {
   ceres_hip_solver* s = p->s;
-  BalEvalTilesConstArgs T;
-  TRY(bal_parts_room(p, kMaxEvalGrid, &T.e.partials));
-  T.debug_flags = debug_flags;
-  T.e.n_rows = p->no; T.e.row_cam = p->d_row_cam; T.e.row_pt = p->d_row_pt; T.e.row_obs = p->d_row_obs;
-  T.e.state = d_state; T.e.cam_base = 3 * int64_t(p->np); T.e.scale = d_scale;
   const bool cam_eval = debug_flags == 0 && bal_camera_pass_evaluates(p);
-  T.e.residuals = p->d_res; T.e.values = cam_eval ? nullptr : p->d_vals; T.e.loss = p->loss;
-  T.n_tiles = s->plan.n_tiles; T.slot_bpos = s->d_slot_bpos; T.slot_fpos = s->d_slot_fpos;
-  T.J_out = s->d_J; T.tile_pitch = s->ops->tile_pitch; T.b_out = s->d_bt;
-  T.slot_cam = p->d_slot_cam; T.slot_pt = p->d_slot_pt; T.slot_obs = p->d_slot_obs; T.pt_pack = p->d_pt_pack; T.cam_pack = p->d_cam_pack;
-  T.pack_cam = p->d_pack_cam; T.pack_scale = p->d_pack_scale; T.n_pack_cams = p->nc; T.scrap = p->d_scrap;   // (constant cameras; nullptr otherwise)
+  BalEvalTilesConstArgs T = bal_tile_args(p, d_state, d_scale, cam_eval ? nullptr : p->d_vals, debug_flags);
+  TRY(bal_parts_room(p, kMaxEvalGrid, &T.e.partials));
   TRY(load_device(s, p->d_vals, p->d_res, nullptr));   // (marks the tiles stale: they are, until the launch below is enqueued)
   bal_set_camera_eval(p, cam_eval);
   int nparts = 0;
@@ -348,10 +387,9 @@ void ceres_hip_bal_destroy(ceres_hip_bal* p) {
 
 namespace {
 
-// ceres_hip_bal_create, ceres_hip_bal_create_with_camera, ceres_hip_bal_create_with_constant_blocks,
-// ceres_hip_bal_create_with_fixed_intrinsics and ceres_hip_bal_create_with_shared_intrinsics (`fn` names the entry point in the
-// messages).  The masks may be NULL; with none set the
-// reduction below is the identity, the camera keeps its width and the handle is what it always was.
+// ceres_hip_bal_create, ceres_hip_bal_create_with_camera, ceres_hip_bal_create_with_constant_blocks, ceres_hip_bal_create_with_fixed_intrinsics
+// and ceres_hip_bal_create_with_shared_intrinsics (`fn` names the entry point in the messages), in three stages.  The masks may be NULL;
+// with none set the reduction is the identity, the camera keeps its width and the handle is what it always was.
 ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras, int32_t num_points,
                           int64_t num_observations, const int32_t* camera_index, const int32_t* point_index,
                           const double* observations, const uint8_t* camera_is_constant = nullptr,
@@ -360,251 +398,70 @@ ceres_hip_bal* bal_create(const char* fn, const ceres_hip_options* options, int3
   const std::string name(fn);
   static_assert(kCamAngleAxis == CERES_HIP_CAMERA_ANGLE_AXIS && kCamQuaternion == CERES_HIP_CAMERA_QUATERNION &&
                 kCamQuaternionManifold == CERES_HIP_CAMERA_QUATERNION_MANIFOLD, "device camera models are the ABI's");
-  if (camera_model < CERES_HIP_CAMERA_ANGLE_AXIS || camera_model > CERES_HIP_CAMERA_QUATERNION_MANIFOLD) {
-    g_create_error = name + ": unknown camera_model " + std::to_string(camera_model);
+  static_assert(kBalAngleAxis == kCamAngleAxis && kBalQuaternion == kCamQuaternion && kBalQuaternionManifold == kCamQuaternionManifold, "and the layout's");
+  // ---- 1. validate and lay out (bal_layout.h); a local: the handle keeps of it what is moved or copied below
+  BalLayout L;
+  const std::string why = !options && bal_camera_model_known(camera_model) ? "bad arguments"
+      : bal_layout(camera_model, num_cameras, num_points, num_observations, camera_index, point_index, observations, camera_is_constant,
+                   point_is_constant, camera_coordinate_is_constant, camera_group, num_groups, L);
+  if (!why.empty()) {
+    g_create_error = name + ": " + why;
     return nullptr;
   }
-  if (!options || num_cameras <= 0 || num_points <= 0 || num_observations <= 0 || !camera_index || !point_index ||
-      !observations) {
-    g_create_error = name + ": bad arguments";
-    return nullptr;
-  }
-  const int cs = camera_model == CERES_HIP_CAMERA_ANGLE_AXIS ? 9 : 10;       // state doubles per camera
-  // Shared intrinsics (camera_group != NULL): every camera in exactly one group, every group id used; angle-axis cameras only
-  const int ng = camera_group ? num_groups : 0;
-  std::vector<int32_t> group_first;
-  if (camera_group) {
-    if (camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) {
-      g_create_error = name + ": shared intrinsics are supported for the angle-axis camera only (camera_model " + std::to_string(camera_model) + ")";
-      return nullptr;
-    }
-    if (num_groups <= 0 || num_groups > num_cameras) {
-      g_create_error = name + ": num_groups " + std::to_string(num_groups) + " is not in [1, num_cameras = " + std::to_string(num_cameras) + "]";
-      return nullptr;
-    }
-    group_first.assign(size_t(num_groups), -1);
-    for (int c = 0; c < num_cameras; ++c) {
-      if (camera_group[c] < 0 || camera_group[c] >= num_groups) {
-        g_create_error = name + ": camera " + std::to_string(c) + " has group " + std::to_string(camera_group[c]) + ", not in [0, " + std::to_string(num_groups) + ")";
-        return nullptr;
-      }
-      if (group_first[camera_group[c]] < 0) group_first[camera_group[c]] = c;
-    }
-    for (int g = 0; g < num_groups; ++g) {
-      if (group_first[g] >= 0) continue;
-      g_create_error = name + ": group " + std::to_string(g) + " has no camera (every id in [0, num_groups) must be used)";
-      return nullptr;
-    }
-  }
-  // SubsetManifold on every camera (one mask of cs entries; NULL: none): the intrinsics f, k1, k2 of the angle-axis camera alone
-  int intrinsics_mask = 0;
-  for (int j = 0; camera_coordinate_is_constant && j < cs; ++j) {
-    if (!camera_coordinate_is_constant[j]) continue;
-    if (camera_model != CERES_HIP_CAMERA_ANGLE_AXIS) {
-      g_create_error = name + ": constant camera coordinates are supported for the angle-axis camera only (camera_model " + std::to_string(camera_model) + ")";
-      return nullptr;
-    }
-    if (j >= 6) { intrinsics_mask |= 1 << (j - 6); continue; }
-    bool all = true;
-    for (int k = 0; k < cs; ++k) all = all && camera_coordinate_is_constant[k] != 0;
-    g_create_error = all ? name + ": every camera coordinate is constant: use constant cameras (camera_is_constant)"
-                         : name + ": camera coordinate " + std::to_string(j) + " cannot be constant: only the intrinsics, coordinates 6 .. 8 (f, k1, k2)";
-    return nullptr;
-  }
-  // Jacobian columns per camera (tangent): the free coordinates
-  const int cw = ng ? 6 : (camera_model == CERES_HIP_CAMERA_QUATERNION ? 10 : 9) - ((intrinsics_mask & 1) + ((intrinsics_mask >> 1) & 1) + ((intrinsics_mask >> 2) & 1));
-  const int64_t per_obs = 6 + 2 * cw + (ng ? 6 : 0);                                        // Jacobian values per observation: 24, 26 or 24 (18 .. 22 with fixed intrinsics, 24 with shared ones)
-  if (num_observations * per_obs > int64_t(INT32_MAX)) {  // cell.position is an int in the reference too (I/block_structure.h:64)
-    g_create_error = name + ": more than " + std::to_string(int64_t(INT32_MAX) / per_obs / 1000000) +
-                     " M observations do not fit 32-bit value positions";
-    return nullptr;
-  }
-  for (int64_t i = 0; i < num_observations; ++i) {
-    if (camera_index[i] < 0 || camera_index[i] >= num_cameras || point_index[i] < 0 || point_index[i] >= num_points) {
-      g_create_error = name + ": observation index out of range";
-      return nullptr;
-    }
-  }
-  bool has_const = false;
-  for (int c = 0; camera_is_constant && c < num_cameras; ++c) has_const = has_const || camera_is_constant[c] != 0;
-  for (int q = 0; point_is_constant && q < num_points; ++q) has_const = has_const || point_is_constant[q] != 0;
-  // Program::RemoveFixedBlocks and the Schur ordering (constant_blocks.inc).  Nothing constant: rows grouped by point, stable in
-  // observation order (points are elimination group 0), every block free.
-  BalReduction R;
-  {
-    const std::string why = bal_reduce(num_cameras, num_points, num_observations, camera_index, point_index, has_const ? camera_is_constant : nullptr,
-                                       has_const ? point_is_constant : nullptr, R);
-    if (!why.empty()) {
-      g_create_error = name + ": " + why;
-      return nullptr;
-    }
-  }
-  const int nfc = R.num_free_cameras, nfp = R.num_free_points;
-  if (has_const && 3 * int64_t(num_points) + cs * int64_t(num_cameras) > int64_t(INT32_MAX)) {
-    g_create_error = name + ": more than 2^31 state doubles with constant blocks";
-    return nullptr;
-  }
-  if (ng && 3 * int64_t(num_points) + cs * int64_t(num_cameras) > int64_t(INT32_MAX)) {   // (row_scam / row_sgrp / row_spt are 32-bit)
-    g_create_error = name + ": more than 2^31 state doubles with shared intrinsics";
-    return nullptr;
-  }
-  if (intrinsics_mask && 3 * int64_t(num_points) + cs * int64_t(num_cameras) > int64_t(INT32_MAX)) {   // (row_scam / row_spt are 32-bit)
-    g_create_error = name + ": more than 2^31 state doubles with fixed intrinsics";
-    return nullptr;
-  }
+  // ---- 2. the linear solver and its structure
   ceres_hip_options o = *options;
-  o.num_eliminate_blocks = nfp;
+  o.num_eliminate_blocks = L.nfp();
   ceres_hip_solver* s = ceres_hip_create(&o);
   if (!s) return nullptr;
   ceres_hip_bal* p = new ceres_hip_bal;
   p->s = s;
-  const int64_t no = int64_t(R.row_obs.size());   // kept rows
+  const int64_t no = L.n_rows;
   p->nc = num_cameras; p->np = num_points; p->no = no;
-  p->nfc = nfc; p->nfp = nfp; p->has_const = has_const;
-  p->camera_model = camera_model; p->cs = cs; p->cw = cw; p->intrinsics_mask = intrinsics_mask;
-  p->n_a = 3 * int64_t(num_points) + cs * int64_t(num_cameras);
-  p->n_t = 3 * int64_t(nfp) + cw * int64_t(nfc) + 3 * int64_t(ng);
-  p->n_groups = ng; p->group_first = group_first;
-  if (ng) p->group_of.assign(camera_group, camera_group + num_cameras);
+  p->nfc = L.nfc(); p->nfp = L.nfp(); const bool has_const = p->has_const = L.has_const;
+  p->camera_model = camera_model; p->cs = L.cs; p->cw = L.cw; p->intrinsics_mask = L.intrinsics_mask;
+  p->n_a = L.n_a; p->n_t = L.n_t; p->n_rows_e = L.n_rows_e; p->n_rows_f = L.n_rows_f; p->n_removed = int64_t(L.rm_cam.size());
+  p->n_groups = L.n_groups; p->group_first = L.group_first;
+  if (L.n_groups) p->group_of.assign(camera_group, camera_group + num_cameras);
+  p->row_obs = std::move(L.red.row_obs);
+  if (has_const) {   // the reduced program's maps, the caller's observations (the inner iterations' lists)
+    p->cam_col = L.red.camera_column; p->pt_col = L.red.point_column;
+    p->all_cam.assign(camera_index, camera_index + num_observations);
+    p->all_pt.assign(point_index, point_index + num_observations);
+    p->all_obs.assign(observations, observations + 2 * num_observations);
+  }
   auto bail = [&](const char* what) -> ceres_hip_bal* {
     g_create_error = std::string(what) + ": " + s->err;
     ceres_hip_bal_destroy(p);
     return nullptr;
   };
-  p->row_obs = R.row_obs;
-  const int64_t ne = R.num_rows_e;
-  const int ncb = nfp + nfc + ng;   // column blocks: points, free cameras (with shared intrinsics: their poses), groups
-  std::vector<int32_t> rsz(no, 2), rpos(no), csz(ncb), cpos(ncb), rptr(no + 1), ccol, cval, rcam(no), rpt(no), rfpos(no), rscam(no), rspt(no);
-  std::vector<int32_t> rgpos(ng ? no : 0), rsgrp(ng ? no : 0);
-  std::vector<int32_t> frow;   // F cell (in row order) -> row
-  std::vector<double> robs(2 * no);
-  ccol.reserve((ng ? 3 : 2) * no); cval.reserve((ng ? 3 : 2) * no); frow.reserve(no);
-  for (int q = 0; q < nfp; ++q) { csz[q] = 3; cpos[q] = 3 * q; }
-  for (int c = 0; c < nfc; ++c) { csz[nfp + c] = cw; cpos[nfp + c] = 3 * nfp + cw * c; }
-  for (int g = 0; g < ng; ++g) { csz[nfp + nfc + g] = 3; cpos[nfp + nfc + g] = 3 * nfp + cw * nfc + 3 * g; }
-  for (int64_t r = 0; r < no; ++r) if (R.camera_column[camera_index[p->row_obs[r]]] >= 0) frow.push_back(int32_t(r));
-  const int64_t nf = int64_t(frow.size());
-  p->n_rows_e = ne; p->n_rows_f = nf;
-  const int64_t nvals = 6 * ne + 2 * cw * nf + (ng ? 6 * no : 0);
-  int64_t next = 6 * ne;   // (shared intrinsics: a row's pose cell and group cell back to back, in column order)
-  for (int64_t r = 0, f = 0; r < no; ++r) {
-    const int ob = p->row_obs[r];
-    rpos[r] = int32_t(2 * r);
-    rptr[r] = int32_t(ccol.size());
-    rcam[r] = camera_index[ob]; rpt[r] = point_index[ob];
-    robs[2 * r] = observations[2 * int64_t(ob)]; robs[2 * r + 1] = observations[2 * int64_t(ob) + 1];
-    const int pc = R.point_column[rpt[r]], cc = R.camera_column[rcam[r]];
-    rspt[r] = pc >= 0 ? 3 * pc : -1;
-    rscam[r] = cc >= 0 ? 3 * nfp + cw * cc : -1;
-    rfpos[r] = -1;
-    if (pc >= 0) { ccol.push_back(pc); cval.push_back(int32_t(6 * r)); }                             // E cell (rows with one come first)
-    if (ng) {
-      if (cc >= 0) { rfpos[r] = int32_t(next); next += 12; ccol.push_back(nfp + cc); cval.push_back(rfpos[r]); }   // pose cell
-      const int g = camera_group[rcam[r]];
-      rgpos[r] = int32_t(next); next += 6; rsgrp[r] = 3 * nfp + cw * nfc + 3 * g;
-      ccol.push_back(nfp + nfc + g); cval.push_back(rgpos[r]);                                                     // group cell
-      continue;
-    }
-    if (cc >= 0) { rfpos[r] = int32_t(6 * ne + 2 * cw * f++); ccol.push_back(nfp + cc); cval.push_back(rfpos[r]); }   // F cell
-  }
-  rptr[no] = int32_t(ccol.size());
-  ceres_hip_block_structure flat{int32_t(no), ncb, rsz.data(), rpos.data(), csz.data(), cpos.data(), rptr.data(), ccol.data(),
-                                 cval.data()};
+  ceres_hip_block_structure flat{int32_t(no), int32_t(L.col_size.size()), L.row_size.data(), L.row_pos.data(), L.col_size.data(), L.col_pos.data(),
+                                 L.row_ptr.data(), L.cell_col.data(), L.cell_pos.data()};
   if (ceres_hip_set_structure(s, &flat) != CERES_HIP_OK) return bail((name + ": set_structure").c_str());
   if (hipSetDevice(s->opt.device) != hipSuccess) return bail((name + ": hipSetDevice").c_str());
-  bool ok = dev_upload(s, &p->d_row_cam, rcam) == 0 && dev_upload(s, &p->d_row_pt, rpt) == 0;
-  double* obs_dev = nullptr;
-  ok = ok && dev_upload(s, &obs_dev, robs) == 0;
-  p->d_row_obs = reinterpret_cast<double2*>(obs_dev);
-  ok = ok && dev_alloc(s, &p->d_x, size_t(p->n_a)) == 0 && dev_alloc(s, &p->d_cand, size_t(p->n_a)) == 0 &&
-       dev_alloc(s, &p->d_step, size_t(p->n_t)) == 0 && dev_alloc(s, &p->d_delta, size_t(p->n_t)) == 0 &&
-       dev_alloc(s, &p->d_scale, size_t(p->n_t)) == 0 && dev_alloc(s, &p->d_grad, size_t(p->n_t)) == 0 &&
-       dev_alloc(s, &p->d_res, size_t(2 * no)) == 0 && dev_alloc(s, &p->d_vals, size_t(nvals)) == 0 &&
-       dev_alloc(s, &p->parts.device, size_t(kPartialSumsCapacity)) == 0;
-  if (ok && has_const) {   // the reduced program's maps, the removed rows, the caller's observations (the inner iterations' lists)
-    p->cam_col = R.camera_column; p->pt_col = R.point_column;
-    p->all_cam.assign(camera_index, camera_index + num_observations);
-    p->all_pt.assign(point_index, point_index + num_observations);
-    p->all_obs.assign(observations, observations + 2 * num_observations);
-    std::vector<int64_t> fb;
-    fb.reserve(size_t(ncb));
-    for (int q = 0; q < num_points; ++q) if (R.point_column[q] >= 0) fb.push_back(3 * int64_t(q));
-    for (int c = 0; c < num_cameras; ++c) if (R.camera_column[c] >= 0) fb.push_back(3 * int64_t(num_points) + cs * int64_t(c));
-    ok = dev_upload(s, &p->d_row_fpos, rfpos) == 0 && dev_upload(s, &p->d_row_scam, rscam) == 0 && dev_upload(s, &p->d_row_spt, rspt) == 0 &&
-         dev_upload(s, &p->d_free_block, fb) == 0;
-    p->n_removed = int64_t(R.removed_obs.size());
-    if (ok && p->n_removed > 0) {
-      std::vector<int32_t> mc, mp;
-      std::vector<double> mo;
-      for (int32_t ob : R.removed_obs) {
-        mc.push_back(camera_index[ob]); mp.push_back(point_index[ob]);
-        mo.push_back(observations[2 * int64_t(ob)]); mo.push_back(observations[2 * int64_t(ob) + 1]);
-      }
-      double* md = nullptr;
-      ok = dev_upload(s, &p->d_rm_cam, mc) == 0 && dev_upload(s, &p->d_rm_pt, mp) == 0 && dev_upload(s, &md, mo) == 0;
-      p->d_rm_obs = reinterpret_cast<double2*>(md);
-    }
-  }
-  // fixed or shared intrinsics without constant blocks: the evaluator's per-row positions all the same (kernels_subset.hip and
-  // kernels_shared.hip have the one form)
-  if (ok && (intrinsics_mask || ng) && !has_const)
-    ok = dev_upload(s, &p->d_row_fpos, rfpos) == 0 && dev_upload(s, &p->d_row_scam, rscam) == 0 && dev_upload(s, &p->d_row_spt, rspt) == 0;
-  if (ok && ng) {   // shared intrinsics: the group cell's positions, and Plus' per-camera records (kernels_shared.hip)
-    std::vector<int32_t> cpose(num_cameras), cgrp(num_cameras), cfirst(num_cameras);
-    for (int c = 0; c < num_cameras; ++c) {
-      const int cc = R.camera_column[c];
-      cpose[c] = cc >= 0 ? 3 * nfp + cw * cc : -1;
-      cgrp[c] = 3 * nfp + cw * nfc + 3 * camera_group[c];
-      cfirst[c] = group_first[camera_group[c]] == c;
-    }
-    ok = dev_upload(s, &p->d_row_gpos, rgpos) == 0 && dev_upload(s, &p->d_row_sgrp, rsgrp) == 0 && dev_upload(s, &p->d_cam_pose, cpose) == 0 &&
-         dev_upload(s, &p->d_cam_group, cgrp) == 0 && dev_upload(s, &p->d_cam_first, cfirst) == 0;
-  }
-  // the rows' camera / point / pixel in slot order: the tile evaluator's and the evaluating camera-major pass's records (angle-axis only;
-  // with constant blocks: constant cameras alone — every row then has its E cell, no row is outside the tiles; nine columns wide: not
-  // with fixed intrinsics)
-  if (ok && s->path == CERES_HIP_PATH_BAL && !s->plan.slot_bpos.empty() && camera_model == CERES_HIP_CAMERA_ANGLE_AXIS && nfp == num_points &&
-      intrinsics_mask == 0 && ng == 0) {
-    const size_t ns = s->plan.slot_bpos.size();
-    // camera records: the free cameras in the solver's order, the constant ones behind them (the identity without constants)
-    std::vector<int32_t> rec_of(num_cameras), pack_cam(num_cameras), pack_scale(num_cameras);
-    for (int c = 0, k = nfc; c < num_cameras; ++c) {
-      const int cc = R.camera_column[c];
-      rec_of[c] = cc >= 0 ? cc : k++;
-      pack_cam[rec_of[c]] = c;
-      pack_scale[rec_of[c]] = cc >= 0 ? 3 * nfp + 9 * cc : -1;
-    }
-    std::vector<int32_t> scam(ns, 0), spt(ns, 0);
-    std::vector<double> sobs(2 * ns, 0.0);
-    for (size_t q = 0; q < ns; ++q) {
-      const int bp = s->plan.slot_bpos[q];
-      if (bp < 0) continue;
-      const int64_t r = bp >> 1;
-      scam[q] = rec_of[rcam[r]]; spt[q] = rpt[r]; sobs[2 * q] = robs[2 * r]; sobs[2 * q + 1] = robs[2 * r + 1];
-    }
-    double* so = nullptr;
-    ok = dev_upload(s, &p->d_slot_cam, scam) == 0 && dev_upload(s, &p->d_slot_pt, spt) == 0 && dev_upload(s, &so, sobs) == 0 &&
-         dev_alloc(s, &p->d_pt_pack, size_t(6) * num_points) == 0 && dev_alloc(s, &p->d_cam_pack, size_t(18) * num_cameras) == 0;
-    p->d_slot_obs = reinterpret_cast<double2*>(so);
-    if (ok && has_const) {
-      double* scrap = nullptr;
-      ok = dev_upload(s, &p->d_pack_cam, pack_cam) == 0 && dev_upload(s, &p->d_pack_scale, pack_scale) == 0 && dev_alloc(s, &scrap, 2 * ns) == 0;
-      p->d_scrap = reinterpret_cast<double2*>(scrap);
-    }
-    // camera-major entry -> its row (through the F cell's position) -> point, pixel: the lists of the free cameras
-    const std::vector<int32_t>& cp = s->plan.cam_ptr;
-    if (ok && cp.size() == size_t(nfc) + 1 && cp[nfc] == nf && (has_const ? s->plan.cam_fpos.size() >= size_t(nf) : s->plan.cam_fpos.size() == size_t(no))) {
-      std::vector<int32_t> cpt(nf);
-      std::vector<double> cobs(2 * size_t(nf));
-      for (int64_t q = 0; q < nf; ++q) {
-        const int64_t r = frow[(int64_t(s->plan.cam_fpos[q]) - 6 * ne) / 18];
-        cpt[q] = rpt[r]; cobs[2 * q] = robs[2 * r]; cobs[2 * q + 1] = robs[2 * r + 1];
-      }
-      double* co = nullptr;
-      ok = dev_upload(s, &p->d_cm_pt, cpt) == 0 && dev_upload(s, &co, cobs) == 0;
-      p->d_cm_obs = reinterpret_cast<double2*>(co);
-    }
-  }
+  // ---- 3. upload: a flat list, every line one device array of the handle
+  auto U = [&](auto** d, const auto& v) { return dev_upload(s, d, v) == 0; };
+  auto P = [&](double2** d, const std::vector<double>& v) { return dev_upload_pixels(s, d, v) == 0; };
+  auto A = [&](auto** d, size_t n) { return dev_alloc(s, d, n) == 0; };
+  bool ok = U(&p->d_row_cam, L.row_cam) && U(&p->d_row_pt, L.row_pt) && P(&p->d_row_obs, L.row_pixel) &&
+            A(&p->d_x, size_t(p->n_a)) && A(&p->d_cand, size_t(p->n_a)) &&
+            A(&p->d_step, size_t(p->n_t)) && A(&p->d_delta, size_t(p->n_t)) && A(&p->d_scale, size_t(p->n_t)) && A(&p->d_grad, size_t(p->n_t)) &&
+            A(&p->d_res, size_t(2 * no)) && A(&p->d_vals, size_t(L.n_values)) && A(&p->parts.device, size_t(kPartialSumsCapacity));
+  // the evaluators' per-row positions: constant blocks, fixed or shared intrinsics (kernels_constant.hip, kernels_subset.hip, kernels_shared.hip)
+  if (has_const || L.intrinsics_mask || L.n_groups) ok = ok && U(&p->d_row_fpos, L.row_fpos) && U(&p->d_row_scam, L.row_scam) && U(&p->d_row_spt, L.row_spt);
+  if (has_const) ok = ok && U(&p->d_free_block, L.free_block);
+  if (has_const && p->n_removed > 0) ok = ok && U(&p->d_rm_cam, L.rm_cam) && U(&p->d_rm_pt, L.rm_pt) && P(&p->d_rm_obs, L.rm_pixel);
+  if (L.n_groups)   // shared intrinsics: the group cell's positions, and Plus' per-camera records (kernels_shared.hip)
+    ok = ok && U(&p->d_row_gpos, L.row_gpos) && U(&p->d_row_sgrp, L.row_sgrp) && U(&p->d_cam_pose, L.cam_pose) && U(&p->d_cam_group, L.cam_group) &&
+         U(&p->d_cam_first, L.cam_first);
+  // the tile evaluator's and the evaluating camera-major pass's records, where the fused path's plan and the layout have them
+  const BalRecords K = s->path == CERES_HIP_PATH_BAL ? bal_records(L, s->plan.slot_bpos, s->plan.cam_ptr, s->plan.cam_fpos) : BalRecords{};
+  if (K.slots)
+    ok = ok && U(&p->d_slot_cam, K.slot_cam) && U(&p->d_slot_pt, K.slot_pt) && P(&p->d_slot_obs, K.slot_pixel) &&
+         A(&p->d_pt_pack, size_t(6) * num_points) && A(&p->d_cam_pack, size_t(18) * num_cameras);
+  if (K.slots && has_const) ok = ok && U(&p->d_pack_cam, K.pack_cam) && U(&p->d_pack_scale, K.pack_scale) && A(&p->d_scrap, K.slot_cam.size());
+  if (K.camera_major) ok = ok && U(&p->d_cm_pt, K.cm_pt) && P(&p->d_cm_obs, K.cm_pixel);
+  // (every upload above is a stream copy that reads a vector of L or K, gone at the return: one wait for all, on every path, as the on-demand builders wait)
+  ok = ok && hipStreamSynchronize(s->stream) == hipSuccess;
   if (!ok) return bail((name + ": device allocation").c_str());
   if (hipHostMalloc(reinterpret_cast<void**>(&p->parts.pinned), sizeof(double) * kPartialSumsCapacity) != hipSuccess)
     return bail((name + ": pinned allocation").c_str());
@@ -648,7 +505,7 @@ ceres_hip_bal* ceres_hip_bal_create_with_fixed_intrinsics(const ceres_hip_option
                                                           const uint8_t* camera_coordinate_is_constant) {
   // (nothing marked: the handle — and the messages — of ceres_hip_bal_create_with_constant_blocks; an unknown camera model: the mask's
   // length is unknown too, it is not read)
-  const bool known = camera_model >= CERES_HIP_CAMERA_ANGLE_AXIS && camera_model <= CERES_HIP_CAMERA_QUATERNION_MANIFOLD;
+  const bool known = bal_camera_model_known(camera_model);
   bool any = false;
   for (int j = 0; known && camera_coordinate_is_constant && j < (camera_model == CERES_HIP_CAMERA_ANGLE_AXIS ? 9 : 10); ++j)
     any = any || camera_coordinate_is_constant[j] != 0;
@@ -797,16 +654,10 @@ int ceres_hip_debug_bal_evaluate_tiles_timing(ceres_hip_bal* p, const double* st
   for (int w = 0; w < 2 && !rc; ++w)
     if ((rc = bal_evaluate_into_tiles(p, p->d_x, nullptr, &cost, flags)) == 0) rc = bal_parts_collect(p);
   float ms = 0;
-  BalEvalTilesConstArgs T;   // (the launches alone: every one writes the same partial sums, which nobody takes; no synchronisation in between)
+  // (the launches alone: every one writes the same partial sums, which nobody takes; no synchronisation in between; the loss ceres_hip_bal_minimize runs)
+  BalEvalTilesConstArgs T = bal_tile_args(p, p->d_x, nullptr, p->d_vals, flags);
   if (!rc) rc = bal_parts_room(p, kMaxEvalGrid, &T.e.partials);
   if (!rc) {
-    T.debug_flags = flags;
-    T.e.n_rows = p->no; T.e.state = p->d_x; T.e.cam_base = 3 * int64_t(p->np); T.e.residuals = p->d_res; T.e.values = p->d_vals;
-    T.e.loss = p->loss;   // (what ceres_hip_bal_minimize runs)
-    T.n_tiles = s->plan.n_tiles; T.slot_bpos = s->d_slot_bpos; T.slot_fpos = s->d_slot_fpos;
-    T.J_out = s->d_J; T.tile_pitch = s->ops->tile_pitch; T.b_out = s->d_bt;
-    T.slot_cam = p->d_slot_cam; T.slot_pt = p->d_slot_pt; T.slot_obs = p->d_slot_obs; T.pt_pack = p->d_pt_pack; T.cam_pack = p->d_cam_pack;
-    T.pack_cam = p->d_pack_cam; T.pack_scale = p->d_pack_scale; T.n_pack_cams = p->nc; T.scrap = p->d_scrap;
     int nparts = 0;
     (void)hipEventRecord(e0, s->stream);
     for (int i = 0; i < iters; ++i) {

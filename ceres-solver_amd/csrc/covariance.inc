@@ -24,14 +24,6 @@ struct BalCovariance {
 
 namespace {
 
-void cov_release(ceres_hip_solver* s, void* q, int64_t bytes) {
-  if (!q) return;
-  auto it = std::find(s->allocs.begin(), s->allocs.end(), q);
-  if (it != s->allocs.end()) s->allocs.erase(it);
-  (void)hipFree(q);
-  s->device_bytes -= bytes;
-}
-
 int64_t cov_device_bytes(const BalCovariance* c) {
   return c->fixed_bytes + c->pair_capacity * int64_t(2 * sizeof(int32_t) + sizeof(int64_t)) + c->out_capacity * int64_t(sizeof(double));
 }
@@ -41,38 +33,20 @@ int bal_cov_prepare(ceres_hip_bal* p) {
   if (p->cov) return 0;
   ceres_hip_solver* s = p->s;
   const int64_t no = p->no;
-  std::vector<int32_t> rcam(no), rpt(no), rfpos(no);
-  HIP_TRY(s, hipMemcpyAsync(rcam.data(), p->d_row_cam, sizeof(int32_t) * no, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipMemcpyAsync(rpt.data(), p->d_row_pt, sizeof(int32_t) * no, hipMemcpyDeviceToHost, s->stream));
-  if (p->has_const) HIP_TRY(s, hipMemcpyAsync(rfpos.data(), p->d_row_fpos, sizeof(int32_t) * no, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  if (!p->has_const) for (int64_t r = 0; r < no; ++r) rfpos[r] = int32_t(6 * p->n_rows_e + 2 * int64_t(p->cw) * r);
-  auto pt_col = [&](int q) { return p->has_const ? p->pt_col[q] : q; };
-  auto cam_col = [&](int c) { return p->has_const ? p->cam_col[c] : c; };
+  BalHostRows H;
+  TRY(bal_fetch_rows(p, kRowCam | kRowPt | kRowFpos, H));
   // per free point its rows with a free camera, in row order (the rows of a point are consecutive and carry their E cell at 6 r)
-  std::vector<int32_t> ptr(size_t(p->nfp) + 1, 0), epos, fpos, ccol;
-  for (int64_t r = 0; r < no; ++r) {
-    const int pc = pt_col(rpt[r]), cc = cam_col(rcam[r]);
-    if (pc < 0 || cc < 0) continue;
+  const BalGrouping by_pt = bal_group_by(no, p->nfp, [&](int64_t r) { return bal_camera_column(p, H.cam[r]) >= 0 ? bal_point_column(p, H.pt[r]) : -1; });
+  std::vector<int32_t> epos, fpos = bal_gather(by_pt.perm, H.fpos.data()), ccol;
+  epos.reserve(fpos.size()); ccol.reserve(fpos.size());
+  for (int32_t r : by_pt.perm) {
     if (r >= p->n_rows_e) return fail(s, CERES_HIP_E_INVALID, "covariance: a row with a free point behind the rows with an E cell");
-    ++ptr[size_t(pc) + 1];
-  }
-  for (int q = 0; q < p->nfp; ++q) ptr[size_t(q) + 1] += ptr[q];
-  const size_t ne = size_t(ptr[p->nfp]);
-  epos.resize(ne); fpos.resize(ne); ccol.resize(ne);
-  {
-    std::vector<int32_t> fill(ptr.begin(), ptr.end() - 1);
-    for (int64_t r = 0; r < no; ++r) {
-      const int pc = pt_col(rpt[r]), cc = cam_col(rcam[r]);
-      if (pc < 0 || cc < 0) continue;
-      const int32_t e = fill[pc]++;
-      epos[e] = int32_t(6 * r); fpos[e] = rfpos[r]; ccol[e] = cc;
-    }
+    epos.push_back(int32_t(6 * int64_t(r))); ccol.push_back(bal_camera_column(p, H.cam[r]));
   }
   std::unique_ptr<BalCovariance> c(new BalCovariance);
   const int64_t before = s->device_bytes;
   const size_t n = size_t(s->hs.num_cols_f);
-  TRY(dev_upload(s, &c->d_pt_ptr, ptr)); TRY(dev_upload(s, &c->d_ent_epos, epos)); TRY(dev_upload(s, &c->d_ent_fpos, fpos)); TRY(dev_upload(s, &c->d_ent_ccol, ccol));
+  TRY(dev_upload(s, &c->d_pt_ptr, by_pt.ptr)); TRY(dev_upload(s, &c->d_ent_epos, epos)); TRY(dev_upload(s, &c->d_ent_fpos, fpos)); TRY(dev_upload(s, &c->d_ent_ccol, ccol));
   TRY(dev_alloc(s, &c->d_cinv, size_t(9) * p->nfp)); TRY(dev_alloc(s, &c->d_ppiv, size_t(p->nfp)));
   TRY(dev_alloc(s, &c->d_lam, n)); TRY(dev_alloc(s, &c->d_min, 4)); TRY(dev_alloc(s, &c->d_flag, 1));
   TRY(dev_alloc(s, &c->d_W, n * n));
@@ -86,14 +60,14 @@ int bal_cov_reserve(ceres_hip_bal* p, int64_t pairs, int64_t out) {
   ceres_hip_solver* s = p->s;
   BalCovariance* c = p->cov;
   if (pairs > c->pair_capacity) {
-    cov_release(s, c->d_code_a, c->pair_capacity * int64_t(sizeof(int32_t))); cov_release(s, c->d_code_b, c->pair_capacity * int64_t(sizeof(int32_t)));
-    cov_release(s, c->d_off, c->pair_capacity * int64_t(sizeof(int64_t)));
+    dev_release(s, c->d_code_a, c->pair_capacity * int64_t(sizeof(int32_t))); dev_release(s, c->d_code_b, c->pair_capacity * int64_t(sizeof(int32_t)));
+    dev_release(s, c->d_off, c->pair_capacity * int64_t(sizeof(int64_t)));
     c->d_code_a = c->d_code_b = nullptr; c->d_off = nullptr; c->pair_capacity = 0;
     TRY(dev_alloc(s, &c->d_code_a, size_t(pairs))); TRY(dev_alloc(s, &c->d_code_b, size_t(pairs))); TRY(dev_alloc(s, &c->d_off, size_t(pairs)));
     c->pair_capacity = pairs;
   }
   if (out > c->out_capacity) {
-    cov_release(s, c->d_out, c->out_capacity * int64_t(sizeof(double)));
+    dev_release(s, c->d_out, c->out_capacity * int64_t(sizeof(double)));
     c->d_out = nullptr; c->out_capacity = 0;
     TRY(dev_alloc(s, &c->d_out, size_t(out)));
     c->out_capacity = out;
@@ -127,11 +101,11 @@ int bal_covariance_impl(ceres_hip_bal* p, const ceres_hip_covariance_options& o,
   int64_t total = 0;
   auto code = [&](int32_t blk, int* dim) {
     if (blk < p->np) {
-      const int q = p->has_const ? p->pt_col[blk] : blk;
+      const int q = bal_point_column(p, blk);
       *dim = 3;
       return q >= 0 ? 4 * q + int(kCovPoint) : int(kCovConstPoint);
     }
-    const int cam = blk - p->np, q = p->has_const ? p->cam_col[cam] : cam;
+    const int q = bal_camera_column(p, blk - p->np);
     *dim = p->cw;
     return q >= 0 ? 4 * q + int(kCovCamera) : int(kCovConstCamera);
   };

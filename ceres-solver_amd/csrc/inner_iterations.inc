@@ -159,31 +159,23 @@ int bal_inner_plan_reduced(ceres_hip_bal* p, BalInner& I, int form_env) {
   const int np = p->np, nc = p->nc;
   const int64_t na = int64_t(p->all_cam.size());
   if (!I.d_blocks) {
-    std::vector<int32_t> pt_ptr(static_cast<size_t>(np) + 1, 0), cam_ptr(static_cast<size_t>(nc) + 1, 0);
-    for (int64_t i = 0; i < na; ++i) { ++pt_ptr[p->all_pt[i] + 1]; ++cam_ptr[p->all_cam[i] + 1]; }
-    I.pt_count.assign(pt_ptr.begin() + 1, pt_ptr.end());
-    for (int q = 0; q < np; ++q) pt_ptr[q + 1] += pt_ptr[q];
-    for (int c = 0; c < nc; ++c) cam_ptr[c + 1] += cam_ptr[c];
-    std::vector<int32_t> pcam(static_cast<size_t>(na)), cpt(static_cast<size_t>(na));
-    std::vector<double> pobs(2 * static_cast<size_t>(na)), cobs(2 * static_cast<size_t>(na));
-    std::vector<int32_t> curp(pt_ptr.begin(), pt_ptr.end() - 1), curc(cam_ptr.begin(), cam_ptr.end() - 1);
-    for (int64_t i = 0; i < na; ++i) {
-      const size_t a = size_t(curp[p->all_pt[i]]++), b = size_t(curc[p->all_cam[i]]++);
-      pcam[a] = p->all_cam[i]; pobs[2 * a] = p->all_obs[2 * i]; pobs[2 * a + 1] = p->all_obs[2 * i + 1];
-      cpt[b] = p->all_pt[i]; cobs[2 * b] = p->all_obs[2 * i]; cobs[2 * b + 1] = p->all_obs[2 * i + 1];
-    }
+    const BalGrouping by_pt = bal_group_by(na, np, [&](int64_t i) { return p->all_pt[i]; }), by_cam = bal_group_by(na, nc, [&](int64_t i) { return p->all_cam[i]; });
+    I.pt_count.resize(static_cast<size_t>(np));
+    for (int q = 0; q < np; ++q) I.pt_count[q] = by_pt.ptr[q + 1] - by_pt.ptr[q];
+    const std::vector<int32_t> pcam = bal_gather(by_pt, p->all_cam.data()), cpt = bal_gather(by_cam, p->all_pt.data());
+    const std::vector<double> pobs = bal_gather(by_pt, p->all_obs.data(), 2), cobs = bal_gather(by_cam, p->all_obs.data(), 2);
     int32_t* pc = nullptr;
-    double *po = nullptr, *co = nullptr;
+    double2* po = nullptr;
     TRY(dev_alloc(s, &I.d_blocks, static_cast<size_t>(np) + nc));
     TRY(dev_alloc(s, &I.d_iters, static_cast<size_t>(np) + nc));
-    TRY(dev_upload(s, &I.d_pt_ptr, pt_ptr));
+    TRY(dev_upload(s, &I.d_pt_ptr, by_pt.ptr));
     TRY(dev_upload(s, &pc, pcam));
-    TRY(dev_upload(s, &po, pobs));
-    TRY(dev_upload(s, &I.d_cam_ptr, cam_ptr));
+    TRY(dev_upload_pixels(s, &po, pobs));
+    TRY(dev_upload(s, &I.d_cam_ptr, by_cam.ptr));
     TRY(dev_upload(s, &I.d_cam_pt, cpt));
-    TRY(dev_upload(s, &co, cobs));
-    I.d_pt_cam = pc; I.d_pt_obs = reinterpret_cast<double2*>(po); I.d_cam_obs = reinterpret_cast<double2*>(co);
-    HIP_TRY(s, hipStreamSynchronize(s->stream));
+    TRY(dev_upload_pixels(s, &I.d_cam_obs, cobs));
+    I.d_pt_cam = pc; I.d_pt_obs = po;
+    HIP_TRY(s, hipStreamSynchronize(s->stream));   // (the uploads read host vectors that go out of scope here)
   }
   if (I.kind != p->inner_blocks) {
     std::vector<int32_t> fcam, fpt;   // the reduced program's residual blocks that join two free blocks: the graph's edges
@@ -206,55 +198,40 @@ int bal_inner_plan(ceres_hip_bal* p) {
   const int np = p->np, nc = p->nc;
   if (p->has_const) return bal_inner_plan_reduced(p, I, form_env);
   const int64_t no = p->no;
-  std::vector<int32_t> rcam, rpt;
+  BalHostRows H;
   if (!I.d_blocks) {
     I.d_pt_cam = p->d_row_cam; I.d_pt_obs = p->d_row_obs;   // the lists every kind uses: point row ranges, the camera-major list, iteration counts
-    rcam.resize(static_cast<size_t>(no)); rpt.resize(static_cast<size_t>(no));
-    HIP_TRY(s, hipMemcpy(rcam.data(), p->d_row_cam, sizeof(int32_t) * no, hipMemcpyDeviceToHost));
-    HIP_TRY(s, hipMemcpy(rpt.data(), p->d_row_pt, sizeof(int32_t) * no, hipMemcpyDeviceToHost));
-    std::vector<int32_t> pt_ptr(static_cast<size_t>(np) + 1, 0);   // rows are grouped by point
-    for (int64_t r = 0; r < no; ++r) ++pt_ptr[rpt[r] + 1];
-    I.pt_count.assign(pt_ptr.begin() + 1, pt_ptr.end());
-    for (int q = 0; q < np; ++q) pt_ptr[q + 1] += pt_ptr[q];
+    // the fused path's camera-major list (point and pixel of every entry), where it covers the rows: its camera ranges are the plan's
+    const std::vector<int32_t>& cp = s->plan.cam_ptr;
+    const bool plans = p->d_cm_obs && p->d_cm_pt && cp.size() == static_cast<size_t>(nc) + 1 && cp[nc] == no;
+    TRY(bal_fetch_rows(p, kRowCam | kRowPt | (plans ? 0 : kRowPixel), H));
+    const BalGrouping by_pt = bal_group_by(no, np, [&](int64_t r) { return H.pt[r]; });   // rows are grouped by point
+    I.pt_count.resize(static_cast<size_t>(np));
+    for (int q = 0; q < np; ++q) I.pt_count[q] = by_pt.ptr[q + 1] - by_pt.ptr[q];
     TRY(dev_alloc(s, &I.d_blocks, static_cast<size_t>(np) + nc));
     TRY(dev_alloc(s, &I.d_iters, static_cast<size_t>(np) + nc));
-    TRY(dev_upload(s, &I.d_pt_ptr, pt_ptr));
-    const std::vector<int32_t>& cp = s->plan.cam_ptr;
-    if (p->d_cm_obs && p->d_cm_pt && cp.size() == static_cast<size_t>(nc) + 1 && cp[nc] == no) {
-      // the fused path's camera-major list (point and pixel of every entry): its camera ranges are the plan's
+    TRY(dev_upload(s, &I.d_pt_ptr, by_pt.ptr));
+    BalGrouping by_cam;   // else: rows in camera order, stable
+    std::vector<int32_t> cpt;
+    std::vector<double> cobs;
+    if (plans) {
       TRY(dev_upload(s, &I.d_cam_ptr, cp));
       I.d_cam_pt = p->d_cm_pt; I.d_cam_obs = p->d_cm_obs;
-    } else {   // rows in camera order, stable
-      std::vector<double> robs(2 * static_cast<size_t>(no));
-      HIP_TRY(s, hipMemcpy(robs.data(), p->d_row_obs, sizeof(double) * 2 * no, hipMemcpyDeviceToHost));
-      std::vector<int32_t> cam_ptr(static_cast<size_t>(nc) + 1, 0), cpt(static_cast<size_t>(no));
-      std::vector<double> cobs(2 * static_cast<size_t>(no));
-      for (int64_t r = 0; r < no; ++r) ++cam_ptr[rcam[r] + 1];
-      for (int c = 0; c < nc; ++c) cam_ptr[c + 1] += cam_ptr[c];
-      std::vector<int32_t> cur(cam_ptr.begin(), cam_ptr.end() - 1);
-      for (int64_t r = 0; r < no; ++r) {
-        const int32_t q = cur[rcam[r]]++;
-        cpt[q] = rpt[r]; cobs[2 * static_cast<size_t>(q)] = robs[2 * r]; cobs[2 * static_cast<size_t>(q) + 1] = robs[2 * r + 1];
-      }
-      double* co = nullptr;
-      TRY(dev_upload(s, &I.d_cam_ptr, cam_ptr));
+    } else {
+      by_cam = bal_group_by(no, nc, [&](int64_t r) { return H.cam[r]; });
+      cpt = bal_gather(by_cam, H.pt.data()); cobs = bal_gather(by_cam, H.pixel.data(), 2);
+      TRY(dev_upload(s, &I.d_cam_ptr, by_cam.ptr));
       TRY(dev_upload(s, &I.d_cam_pt, cpt));
-      TRY(dev_upload(s, &co, cobs));
-      I.d_cam_obs = reinterpret_cast<double2*>(co);
+      TRY(dev_upload_pixels(s, &I.d_cam_obs, cobs));
     }
-    HIP_TRY(s, hipStreamSynchronize(s->stream));   // (the host vectors above go out of scope)
+    HIP_TRY(s, hipStreamSynchronize(s->stream));   // (the uploads read host vectors that go out of scope here)
   }
   if (I.kind != p->inner_blocks) {
-    // the ordering is a function of the structure alone: rebuilt from the rows (camera, point per row)
-    if (rcam.empty() && !(p->inner_blocks == CERES_HIP_INNER_AUTOMATIC && !I.automatic.empty())) {
-      rcam.resize(static_cast<size_t>(no)); rpt.resize(static_cast<size_t>(no));
-      HIP_TRY(s, hipMemcpy(rcam.data(), p->d_row_cam, sizeof(int32_t) * no, hipMemcpyDeviceToHost));
-      HIP_TRY(s, hipMemcpy(rpt.data(), p->d_row_pt, sizeof(int32_t) * no, hipMemcpyDeviceToHost));
-    }
     if (p->inner_blocks == CERES_HIP_INNER_AUTOMATIC && !I.automatic.empty()) {
       I.group = I.automatic; I.num_groups = I.automatic_groups;
-    } else {
-      I.num_groups = inner_ordering(nc, np, no, rcam.data(), rpt.data(), p->inner_blocks, I.group);
+    } else {   // the ordering is a function of the structure alone: rebuilt from the rows (camera, point per row)
+      if (H.cam.empty()) TRY(bal_fetch_rows(p, kRowCam | kRowPt, H));
+      I.num_groups = inner_ordering(nc, np, no, H.cam.data(), H.pt.data(), p->inner_blocks, I.group);
       if (p->inner_blocks == CERES_HIP_INNER_AUTOMATIC) { I.automatic = I.group; I.automatic_groups = I.num_groups; }
     }
   }

@@ -433,42 +433,29 @@ constexpr int kLsMaxSlots = 12;
 
 // give the history and the per-slot scalars back before a larger rank's replace them
 void ls_release_history(ceres_hip_solver* s, BalLineSearch* ls) {
-  auto release = [&](void* q, int64_t bytes) {
-    if (!q) return;
-    auto it = std::find(s->allocs.begin(), s->allocs.end(), q);
-    if (it != s->allocs.end()) s->allocs.erase(it);
-    (void)hipFree(q);
-    s->device_bytes -= bytes;
-  };
   const int64_t cap = std::max(ls->lbfgs_capacity, 1);
-  release(ls->lbfgs_history, ls->lbfgs_bytes);
-  release(ls->L.sy, cap * int64_t(sizeof(double))); release(ls->L.alpha, cap * int64_t(sizeof(double)));
-  release(ls->L.order, cap * int64_t(sizeof(int32_t)));
+  dev_release(s, ls->lbfgs_history, ls->lbfgs_bytes);
+  dev_release(s, ls->L.sy, cap * int64_t(sizeof(double))); dev_release(s, ls->L.alpha, cap * int64_t(sizeof(double)));
+  dev_release(s, ls->L.order, cap * int64_t(sizeof(int32_t)));
   ls->lbfgs_history = nullptr; ls->L.sy = nullptr; ls->L.alpha = nullptr; ls->L.order = nullptr; ls->L.S = nullptr; ls->L.Y = nullptr;
   ls->lbfgs_capacity = 0; ls->lbfgs_bytes = 0;
 }
 
 BalFreeBlocks ls_blocks(const ceres_hip_bal* p) { return BalFreeBlocks{p->ls->d_blocks, p->nfp, p->nfc}; }
 
-// The point pass's row_pdst and long-point list, the camera pass's lists and chunks: a counting sort of the rows by camera.
+// The point pass's row_pdst and long-point list, the camera pass's lists and chunks: the rows grouped by camera (bal_group_by).
 int bal_ls_prepare(ceres_hip_bal* p) {
   if (p->ls) return 0;
   ceres_hip_solver* s = p->s;
   if (p->n_t > int64_t(INT32_MAX) || p->no > int64_t(INT32_MAX) - 64) return fail(s, CERES_HIP_E_UNSUPPORTED, "line search: more than 2^31 tangent entries or rows");
   const int64_t no = p->no;
-  std::vector<int32_t> rcam(no), rpt(no);
-  std::vector<double> robs(2 * no);
-  HIP_TRY(s, hipMemcpyAsync(rcam.data(), p->d_row_cam, sizeof(int32_t) * no, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipMemcpyAsync(rpt.data(), p->d_row_pt, sizeof(int32_t) * no, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipMemcpyAsync(robs.data(), p->d_row_obs, sizeof(double) * 2 * no, hipMemcpyDeviceToHost, s->stream));
-  HIP_TRY(s, hipStreamSynchronize(s->stream));
-  auto pt_col = [&](int q) { return p->has_const ? p->pt_col[q] : q; };
-  auto cam_col = [&](int c) { return p->has_const ? p->cam_col[c] : c; };
+  BalHostRows H;
+  TRY(bal_fetch_rows(p, kRowCam | kRowPt | kRowPixel, H));
   std::unique_ptr<BalLineSearch> ls(new BalLineSearch);
   // point pass
   std::vector<int32_t> pdst(no), long_dst, long_w0, long_w1;
   std::vector<char> seen(size_t(p->nfp), 0);
-  for (int64_t r = 0; r < no; ++r) { const int pc = pt_col(rpt[r]); pdst[r] = pc >= 0 ? 3 * pc : -1; }
+  for (int64_t r = 0; r < no; ++r) { const int pc = bal_point_column(p, H.pt[r]); pdst[r] = pc >= 0 ? 3 * pc : -1; }
   for (int64_t a = 0; a < no;) {
     int64_t b = a + 1;
     while (b < no && pdst[b] == pdst[a]) ++b;
@@ -481,42 +468,28 @@ int bal_ls_prepare(ceres_hip_bal* p) {
   }
   for (char c : seen) if (!c) return fail(s, CERES_HIP_E_UNSUPPORTED, "line search: a free point without a row");
   // camera pass: the rows of every free camera in ascending order, cut into chunks of 64
-  std::vector<int32_t> cptr(size_t(p->nfc) + 1, 0);
-  for (int64_t r = 0; r < no; ++r) { const int cc = cam_col(rcam[r]); if (cc >= 0) ++cptr[cc + 1]; }
-  for (int c = 0; c < p->nfc; ++c) {
-    if (cptr[c + 1] == 0) return fail(s, CERES_HIP_E_UNSUPPORTED, "line search: a free camera without a row");
-    cptr[c + 1] += cptr[c];
-  }
-  const int64_t nf = cptr[p->nfc];
-  std::vector<int32_t> fill(cptr.begin(), cptr.end() - 1), cm_pt(nf), cam_of(p->nfc);
-  std::vector<double> cm_obs(2 * nf);
-  for (int64_t r = 0; r < no; ++r) {
-    const int cc = cam_col(rcam[r]);
-    if (cc < 0) continue;
-    const int64_t e = fill[cc]++;
-    cam_of[cc] = rcam[r];
-    cm_pt[e] = rpt[r]; cm_obs[2 * e] = robs[2 * r]; cm_obs[2 * e + 1] = robs[2 * r + 1];
-  }
+  const BalGrouping by_cam = bal_group_by(no, p->nfc, [&](int64_t r) { return bal_camera_column(p, H.cam[r]); });
+  const std::vector<int32_t>& cptr = by_cam.ptr;
   std::vector<int32_t> ch_cam, ch_start, ch_len, ch_dst, fin_dst, fin_first, fin_count;
   int32_t n_partials = 0;
   for (int c = 0; c < p->nfc; ++c) {
     const int32_t len = cptr[c + 1] - cptr[c], nch = (len + 63) / 64, dst = int32_t(3 * int64_t(p->nfp) + int64_t(p->cw) * c);
+    if (len == 0) return fail(s, CERES_HIP_E_UNSUPPORTED, "line search: a free camera without a row");
     if (nch > 1) { fin_dst.push_back(dst); fin_first.push_back(n_partials); fin_count.push_back(nch); }
     for (int k = 0; k < nch; ++k) {
-      ch_cam.push_back(cam_of[c]); ch_start.push_back(cptr[c] + 64 * k); ch_len.push_back(std::min(64, len - 64 * k));
+      ch_cam.push_back(H.cam[by_cam.perm[cptr[c]]]); ch_start.push_back(cptr[c] + 64 * k); ch_len.push_back(std::min(64, len - 64 * k));
       ch_dst.push_back(nch > 1 ? -(n_partials++) - 1 : dst);
     }
   }
-  std::vector<int64_t> blocks;
-  blocks.reserve(size_t(p->nfp) + p->nfc);
-  for (int q = 0; q < p->np; ++q) if (pt_col(q) >= 0) blocks.push_back(3 * int64_t(q));
-  for (int c = 0; c < p->nc; ++c) if (cam_col(c) >= 0) blocks.push_back(3 * int64_t(p->np) + p->cs * int64_t(c));
+  const std::vector<int32_t> cm_pt = bal_gather(by_cam, H.pt.data());
+  const std::vector<double> cm_obs = bal_gather(by_cam, H.pixel.data(), 2);
+  const std::vector<int64_t> blocks = bal_free_block_offsets(p->nc, p->np, p->cs, p->cam_col, p->pt_col);   // (no constants: no maps, every block)
   LsGradArgs& G = ls->G;
   int32_t *d_pdst, *d_ldst, *d_lw0, *d_lw1, *d_ccam, *d_cstart, *d_clen, *d_cdst, *d_cmpt, *d_fdst, *d_ffirst, *d_fcount;
-  double* d_cmobs;
+  double2* d_cmobs;
   TRY(dev_upload(s, &d_pdst, pdst)); TRY(dev_upload(s, &d_ldst, long_dst)); TRY(dev_upload(s, &d_lw0, long_w0)); TRY(dev_upload(s, &d_lw1, long_w1));
   TRY(dev_upload(s, &d_ccam, ch_cam)); TRY(dev_upload(s, &d_cstart, ch_start)); TRY(dev_upload(s, &d_clen, ch_len)); TRY(dev_upload(s, &d_cdst, ch_dst));
-  TRY(dev_upload(s, &d_cmpt, cm_pt)); TRY(dev_upload(s, &d_cmobs, cm_obs));
+  TRY(dev_upload(s, &d_cmpt, cm_pt)); TRY(dev_upload_pixels(s, &d_cmobs, cm_obs));
   TRY(dev_upload(s, &d_fdst, fin_dst)); TRY(dev_upload(s, &d_ffirst, fin_first)); TRY(dev_upload(s, &d_fcount, fin_count));
   TRY(dev_upload(s, &ls->d_blocks, blocks));
   TRY(dev_alloc(s, &G.wave_parts, size_t(6 * ((no + 63) / 64))));
@@ -527,7 +500,7 @@ int bal_ls_prepare(ceres_hip_bal* p) {
   G.cam_base = 3 * int64_t(p->np);
   G.n_long = int32_t(long_dst.size()); G.long_dst = d_ldst; G.long_w0 = d_lw0; G.long_w1 = d_lw1;
   G.n_chunks = int32_t(ch_cam.size()); G.chunk_cam = d_ccam; G.chunk_start = d_cstart; G.chunk_len = d_clen; G.chunk_dst = d_cdst;
-  G.cm_pt = d_cmpt; G.cm_obs = reinterpret_cast<const double2*>(d_cmobs);
+  G.cm_pt = d_cmpt; G.cm_obs = d_cmobs;
   G.n_fin = int32_t(fin_dst.size()); G.fin_dst = d_fdst; G.fin_first = d_ffirst; G.fin_count = d_fcount;
   p->ls = ls.release();
   return 0;

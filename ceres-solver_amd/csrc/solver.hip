@@ -329,6 +329,14 @@ int dev_upload(ceres_hip_solver* s, T** p, const std::vector<T>& v) {
   if (!v.empty()) HIP_TRY(s, hipMemcpyAsync(*p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, s->stream));
   return 0;
 }
+// give one allocation of `bytes` back before the solver goes (buffers that are replaced by larger ones)
+void dev_release(ceres_hip_solver* s, void* p, int64_t bytes) {
+  if (!p) return;
+  auto it = std::find(s->allocs.begin(), s->allocs.end(), p);
+  if (it != s->allocs.end()) s->allocs.erase(it);
+  (void)hipFree(p);
+  s->device_bytes -= bytes;
+}
 void free_all(ceres_hip_solver* s) {
   for (void* p : s->allocs) (void)hipFree(p);
   s->allocs.clear();
