@@ -20,7 +20,7 @@ BAL_SHAPES_R = [(3, 3, 3), (4, 4, 2), (4, 4, 3), (4, 4, 4)]
 SOURCES = (["plan.cc", "visibility.cc", "kernels_generic.hip", "kernels_cg.hip", "kernels_bal_common.hip"] + [f"kernels_bal_shape_f{nf}_s{ns}.hip" for nf, ns in BAL_SHAPES] +
            [f"kernels_bal_shape_e{ne}_f{nf}_s0.hip" for ne, nf in BAL_SHAPES_E] +
            [f"kernels_bal_shape_r{nr}_e{ne}_f{nf}_s0.hip" for nr, ne, nf in BAL_SHAPES_R] +
-           ["kernels_schur.hip", "kernels_cluster.hip", "kernels_evaluator.hip", "kernels_quaternion.hip", "kernels_constant.hip", "kernels_subset.hip", "kernels_shared.hip", "kernels_bounds.hip", "kernels_inner.hip", "kernels_dogleg.hip", "kernels_line_search.hip", "kernels_line_search_quat.hip", "kernels_covariance.hip", "solver.hip"])
+           ["kernels_schur.hip", "kernels_cluster.hip", "kernels_evaluator.hip", "kernels_quaternion.hip", "kernels_constant.hip", "kernels_subset.hip", "kernels_shared.hip", "kernels_bounds.hip", "kernels_inner.hip", "kernels_dogleg.hip", "kernels_line_search.hip", "kernels_line_search_quat.hip", "kernels_covariance.hip", "kernels_covariance_shared.hip", "solver.hip"])
 # visibility.cc: the clustering is compared bit-for-bit with a restatement in the tests — no contraction of a * b + c into one rounding
 EXTRA_FLAGS = {"visibility.cc": ["-ffp-contract=off"]}
 HEADERS = ["common.h", "device.h", "p2p.h", "snavely.h", "bal_evaluate.h", "robust_loss.h", "bal_frontend.inc", "constant_blocks.inc", "inner_iterations.inc", "dogleg.inc", "line_search.inc", "bounds.inc", "covariance.inc", "line_search_gradient.h", "quaternion_plus.h", "reduce.h", "partial_sums.h", "bal_layout.h", "solver_comm.inc", "solver_stream.inc", "solver_ops.inc", "solver_debug.inc", "kernels_bal.inc", os.path.join("..", "..", "include", "ceres_hip.h")]

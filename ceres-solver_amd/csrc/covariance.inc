@@ -7,6 +7,9 @@
 //   factor      S~ = Lambda S Lambda, LaunchDenseCholesky, the smallest squared diagonal entry of L (the Schur stage can fail here)
 //   inverse     Lambda (L L^T)^-1 Lambda into the second n x n buffer
 //   blocks      one wavefront per requested pair, then one copy to the host
+// A handle with shared intrinsics (n_groups != 0; design/28_shared_covariance.md) runs the same stages over its own structure — the
+// eliminator forms S over poses and groups — with lists, pair codes and a blocks pass of its own (kernels_covariance_shared.hip); every
+// branch for it tests n_groups first.
 // Nothing of the solver's own state is used but its structure, its stream, the dense buffer and the eliminator's scratch, all of
 // which every DENSE_SCHUR solve rebuilds; the factorisation flag is this feature's own.
 
@@ -14,6 +17,7 @@ struct BalCovariance {
   double *d_cinv = nullptr, *d_ppiv = nullptr, *d_lam = nullptr, *d_W = nullptr, *d_min = nullptr;
   int* d_flag = nullptr;
   int32_t *d_pt_ptr = nullptr, *d_ent_epos = nullptr, *d_ent_fpos = nullptr, *d_ent_ccol = nullptr;
+  int32_t *d_ent_gpos = nullptr, *d_ent_gcol = nullptr;   // shared intrinsics: the group cell of every entry (fpos / ccol: its pose cell, -1: none)
   // per call, grown on demand: the pairs' codes and offsets, the output
   int32_t *d_code_a = nullptr, *d_code_b = nullptr;
   int64_t* d_off = nullptr;
@@ -35,18 +39,40 @@ int bal_cov_prepare(ceres_hip_bal* p) {
   const int64_t no = p->no;
   BalHostRows H;
   TRY(bal_fetch_rows(p, kRowCam | kRowPt | kRowFpos, H));
-  // per free point its rows with a free camera, in row order (the rows of a point are consecutive and carry their E cell at 6 r)
-  const BalGrouping by_pt = bal_group_by(no, p->nfp, [&](int64_t r) { return bal_camera_column(p, H.cam[r]) >= 0 ? bal_point_column(p, H.pt[r]) : -1; });
+  // per free point its rows with a free camera, in row order (the rows of a point are consecutive and carry their E cell at 6 r).
+  // Shared intrinsics: EVERY row of a point (a row of a constant pose still carries its group cell); per entry the E cell, the pose cell
+  // and its first column in S^-1 (-1, -1: the pose is constant), the group cell — behind the pose cell — and its first column
+  const bool shared = p->n_groups != 0;
+  std::vector<int32_t> gpos, gcol;
+  const BalGrouping by_pt = bal_group_by(no, p->nfp, [&](int64_t r) { return shared || bal_camera_column(p, H.cam[r]) >= 0 ? bal_point_column(p, H.pt[r]) : -1; });
   std::vector<int32_t> epos, fpos = bal_gather(by_pt.perm, H.fpos.data()), ccol;
   epos.reserve(fpos.size()); ccol.reserve(fpos.size());
   for (int32_t r : by_pt.perm) {
     if (r >= p->n_rows_e) return fail(s, CERES_HIP_E_INVALID, "covariance: a row with a free point behind the rows with an E cell");
-    epos.push_back(int32_t(6 * int64_t(r))); ccol.push_back(bal_camera_column(p, H.cam[r]));
+    epos.push_back(int32_t(6 * int64_t(r)));
+    if (!p->n_groups) { ccol.push_back(bal_camera_column(p, H.cam[r])); continue; }
+    const int cc = bal_camera_column(p, H.cam[r]);
+    ccol.push_back(cc >= 0 ? 6 * cc : -1);
+    gcol.push_back(6 * p->nfc + 3 * p->group_of[H.cam[r]]);
+  }
+  if (p->n_groups) {   // (bal_layout: a row's pose cell and group cell back to back behind the E cells, in row order)
+    std::vector<int32_t> row_gpos(size_t(no), 0);
+    int64_t next = 6 * p->n_rows_e;
+    for (int64_t r = 0; r < no; ++r) {
+      if (H.fpos[r] >= 0) {
+        if (H.fpos[r] != next) return fail(s, CERES_HIP_E_INVALID, "covariance: a pose cell is not where the layout of shared intrinsics puts it");
+        next += 12;
+      }
+      row_gpos[r] = int32_t(next); next += 6;
+    }
+    if (next != bal_num_values(p)) return fail(s, CERES_HIP_E_INVALID, "covariance: the cells of the rows do not add up to the handle's values");
+    gpos = bal_gather(by_pt.perm, row_gpos.data());
   }
   std::unique_ptr<BalCovariance> c(new BalCovariance);
   const int64_t before = s->device_bytes;
   const size_t n = size_t(s->hs.num_cols_f);
   TRY(dev_upload(s, &c->d_pt_ptr, by_pt.ptr)); TRY(dev_upload(s, &c->d_ent_epos, epos)); TRY(dev_upload(s, &c->d_ent_fpos, fpos)); TRY(dev_upload(s, &c->d_ent_ccol, ccol));
+  if (p->n_groups) { TRY(dev_upload(s, &c->d_ent_gpos, gpos)); TRY(dev_upload(s, &c->d_ent_gcol, gcol)); }
   TRY(dev_alloc(s, &c->d_cinv, size_t(9) * p->nfp)); TRY(dev_alloc(s, &c->d_ppiv, size_t(p->nfp)));
   TRY(dev_alloc(s, &c->d_lam, n)); TRY(dev_alloc(s, &c->d_min, 4)); TRY(dev_alloc(s, &c->d_flag, 1));
   TRY(dev_alloc(s, &c->d_W, n * n));
@@ -100,6 +126,13 @@ int bal_covariance_impl(ceres_hip_bal* p, const ceres_hip_covariance_options& o,
   std::vector<int64_t> off(npairs);
   int64_t total = 0;
   auto code = [&](int32_t blk, int* dim) {
+    if (p->n_groups) {   // shared intrinsics: point | pose (6, constant: zeros) | group (3, never constant); the index is the first column in S^-1
+      *dim = blk >= p->np && blk < p->np + p->nc ? 6 : 3;
+      if (blk < p->np) return 4 * blk + int(kCovSharedPoint);
+      if (blk >= p->np + p->nc) return 4 * (6 * p->nfc + 3 * (blk - p->np - p->nc)) + int(kCovSharedGroup);
+      const int q = bal_camera_column(p, blk - p->np);
+      return q >= 0 ? 4 * (6 * q) + int(kCovSharedPose) : int(kCovSharedConstPose);
+    }
     if (blk < p->np) {
       const int q = bal_point_column(p, blk);
       *dim = 3;
@@ -194,12 +227,22 @@ int bal_covariance_impl(ceres_hip_bal* p, const ceres_hip_covariance_options& o,
     HIP_TRY(s, hipMemcpyAsync(c->d_code_a, code_a.data(), sizeof(int32_t) * size_t(num_pairs), hipMemcpyHostToDevice, st));
     HIP_TRY(s, hipMemcpyAsync(c->d_code_b, code_b.data(), sizeof(int32_t) * size_t(num_pairs), hipMemcpyHostToDevice, st));
     HIP_TRY(s, hipMemcpyAsync(c->d_off, off.data(), sizeof(int64_t) * size_t(num_pairs), hipMemcpyHostToDevice, st));
-    CovBlocksArgs A;
-    A.n_pairs = int(num_pairs); A.n = n;
-    A.code_a = c->d_code_a; A.code_b = c->d_code_b; A.out_off = c->d_off; A.out = c->d_out;
-    A.values = p->d_vals; A.cinv = c->d_cinv; A.sinv = c->d_W;
-    A.pt_ptr = c->d_pt_ptr; A.ent_epos = c->d_ent_epos; A.ent_fpos = c->d_ent_fpos; A.ent_ccol = c->d_ent_ccol;
-    HIP_TRY(s, LaunchCovBlocks(A, p->cw, st));
+    if (p->n_groups) {
+      CovSharedBlocksArgs A;
+      A.n_pairs = int(num_pairs); A.n = n;
+      A.code_a = c->d_code_a; A.code_b = c->d_code_b; A.out_off = c->d_off; A.out = c->d_out;
+      A.values = p->d_vals; A.cinv = c->d_cinv; A.sinv = c->d_W;
+      A.pt_ptr = c->d_pt_ptr; A.ent_epos = c->d_ent_epos; A.ent_ppos = c->d_ent_fpos; A.ent_pcol = c->d_ent_ccol;
+      A.ent_gpos = c->d_ent_gpos; A.ent_gcol = c->d_ent_gcol;
+      HIP_TRY(s, LaunchCovSharedBlocks(A, st));
+    } else {
+      CovBlocksArgs A;
+      A.n_pairs = int(num_pairs); A.n = n;
+      A.code_a = c->d_code_a; A.code_b = c->d_code_b; A.out_off = c->d_off; A.out = c->d_out;
+      A.values = p->d_vals; A.cinv = c->d_cinv; A.sinv = c->d_W;
+      A.pt_ptr = c->d_pt_ptr; A.ent_epos = c->d_ent_epos; A.ent_fpos = c->d_ent_fpos; A.ent_ccol = c->d_ent_ccol;
+      HIP_TRY(s, LaunchCovBlocks(A, p->cw, st));
+    }
     HIP_TRY(s, hipStreamSynchronize(st));   // (a failure of the pass must not leave half a result with the caller)
     TRY(down(s, blocks_out, c->d_out, size_t(total)));
   }
@@ -243,14 +286,14 @@ int ceres_hip_bal_covariance(ceres_hip_bal* p, const ceres_hip_covariance_option
   if (!std::isfinite(o.min_scaled_pivot) || o.min_scaled_pivot < 0.0) return refuse(CERES_HIP_E_INVALID, "min_scaled_pivot must be finite and >= 0");
   ceres_hip_solver* s = p->s;
   if (p->intrinsics_mask) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with fixed intrinsics");
-  if (p->n_groups) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on handles with shared intrinsics");
   if (!is_dense_schur(s)) return refuse(CERES_HIP_E_UNSUPPORTED, "the handle's linear solver is not CERES_HIP_DENSE_SCHUR");
   if (s->world > 1) return refuse(CERES_HIP_E_UNSUPPORTED, "not supported on sharded handles");
-  const int64_t num_blocks = int64_t(p->np) + p->nc;
+  const int64_t num_blocks = int64_t(p->np) + p->nc + p->n_groups;   // (shared intrinsics: the groups behind the cameras' poses)
   for (int64_t i = 0; i < num_pairs; ++i) {
     if (block_a[i] < 0 || block_a[i] >= num_blocks || block_b[i] < 0 || block_b[i] >= num_blocks)
       return refuse(CERES_HIP_E_INVALID, "pair " + std::to_string(i) + ": block index out of range [0, " + std::to_string(num_blocks) + ")");
   }
+  if (int rc = bal_shared_check(p, "ceres_hip_bal_covariance", state)) return rc;
   memset(summary, 0, sizeof(*summary));
   summary->termination_type = CERES_HIP_FAILURE;
   BAL_TRY(p, bal_covariance_impl(p, o, state, num_pairs, block_a, block_b, blocks_out, summary));

@@ -449,6 +449,22 @@ struct CovBlocksArgs {
 };
 // one wavefront per pair; cw = 9 or 10 (hipErrorInvalidValue otherwise)
 hipError_t LaunchCovBlocks(const CovBlocksArgs& P, int cw, hipStream_t stream);
+// The blocks pass of a handle with shared intrinsics (kernels_covariance_shared.hip; design/28_shared_covariance.md): three block kinds,
+// points (3), poses (6) and groups (3), and per row two camera-side cells — a pose cell (none when the pose is constant) and a group cell.
+enum CovSharedKind { kCovSharedPoint = 0, kCovSharedPose = 1, kCovSharedConstPose = 2, kCovSharedGroup = 3 };
+struct CovSharedBlocksArgs {
+  int n_pairs = 0, n = 0;                   // n = num_cols_f = 6 (free cameras) + 3 (groups), the pitch of sinv
+  // per pair: 4 x index + CovSharedKind; the index of a point is the point, of a pose or a group its first scalar column in sinv
+  const int32_t *code_a = nullptr, *code_b = nullptr;
+  const int64_t* out_off = nullptr;         // per pair: where its dim(a) x dim(b) row-major block starts in out
+  double* out = nullptr;
+  const double *values = nullptr, *cinv = nullptr, *sinv = nullptr;   // caller-layout Jacobian, C_p^-1 (9 per point), S^-1
+  // per point EVERY row of it, entries [pt_ptr[q], pt_ptr[q + 1]): E cell; pose cell and its first column in sinv (-1, -1: the pose is
+  // constant); group cell and its first column in sinv
+  const int32_t *pt_ptr = nullptr, *ent_epos = nullptr, *ent_ppos = nullptr, *ent_pcol = nullptr, *ent_gpos = nullptr, *ent_gcol = nullptr;
+};
+// one wavefront per pair
+hipError_t LaunchCovSharedBlocks(const CovSharedBlocksArgs& P, hipStream_t stream);
 
 // ---- CLUSTER_JACOBI (kernels_cluster.hip): one dense factor per cluster of F blocks ------------------
 // Clusters of at most kClusterLdsDim scalars are factored and applied one workgroup per cluster with the matrix in LDS

@@ -1563,18 +1563,27 @@ class BalProblem:
         return x, S
 
     def covariance_block_size(self, block):
-        """Tangent size of a block numbered in state order (point q is q, camera c is num_points + c): 3, or 9 / 10 for a camera."""
+        """Tangent size of a block numbered in state order (point q is q, camera c is num_points + c): 3, or 9 / 10 for a camera.  With
+        camera_groups camera c's block is its POSE (6) and group g is block num_points + num_cameras + g (3)."""
         if block < self.num_points:
             return 3
+        if self.num_intrinsics_groups:
+            return 6 if block < self.num_points + self.num_cameras else 3
         return 10 if self.camera_model == CAMERA_QUATERNION else 9
+
+    @property
+    def num_covariance_blocks(self):
+        """How many blocks ceres_hip_bal_covariance numbers: the points, the cameras and, with camera_groups, the groups behind them."""
+        return self.num_points + self.num_cameras + self.num_intrinsics_groups
 
     def covariance_raw(self, state, pairs, apply_loss_function=True, min_scaled_pivot=1e-8, out=None):
         """ceres_hip_bal_covariance without judging the outcome: (return code, flat output, CCovarianceSummary).  `out` (optional): the
-        flat output array to fill, at least the sum of dim(a) x dim(b) doubles; it is left as it is when the call fails."""
+        flat output array to fill, at least the sum of dim(a) x dim(b) doubles; it is left as it is when the call fails.  Blocks are
+        numbered as `covariance_block_size` says (with camera_groups: points, poses, then the groups)."""
         x = _f64(state, self.num_parameters)
         pr = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
         a, b = np.ascontiguousarray(pr[:, 0]), np.ascontiguousarray(pr[:, 1])
-        nblocks = self.num_points + self.num_cameras
+        nblocks = self.num_covariance_blocks
         # (sizes of in-range blocks only: an index out of range is the library's to refuse)
         total = sum(self.covariance_block_size(int(i)) * self.covariance_block_size(int(j)) for i, j in pr
                     if 0 <= i < nblocks and 0 <= j < nblocks)
@@ -1594,6 +1603,8 @@ class BalProblem:
     def covariance(self, state, pairs, apply_loss_function=True, min_scaled_pivot=1e-8):
         """ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for the (a, b) block pairs (state order: point q is q, camera c
         is num_points + c): (J^T J)^-1 of the reduced program at state, in the Schur form on the device (DENSE_SCHUR handles only).
+        With camera_groups the columns are [points | poses of the free cameras | groups]: camera c's block is its 6-wide pose, group g
+        is block num_points + num_cameras + g (3 wide, never constant), and a pair with a constant pose is zeros.
         Returns (list of dim(a) x dim(b) arrays, CCovarianceSummary); pairs with a constant block are zeros.  Raises HipError with the
         summary's message when the problem is rank deficient (a pivot of the unit-diagonal-scaled point blocks or Schur complement is
         not above min_scaled_pivot) — ceres_hip_bal_covariance in include/ceres_hip.h."""

@@ -152,6 +152,7 @@ class HipBalProblem {
                                                           camera_is_constant.empty() ? nullptr : camera_is_constant.data(),
                                                           point_is_constant.empty() ? nullptr : point_is_constant.data());
     if (!handle_) throw std::runtime_error(std::string(ceres_hip_bal_last_error(nullptr)));
+    num_blocks_ = int64_t(d.num_points) + d.num_cameras;
     ceres_hip_bal_sizes(handle_, &num_parameters_, &num_residuals_, &num_jacobian_values_);
     ceres_hip_bal_num_effective_parameters(handle_, &num_effective_parameters_);
   }
@@ -164,6 +165,8 @@ class HipBalProblem {
   int NumEffectiveParameters() const { return int(num_effective_parameters_); }   // Evaluator::NumEffectiveParameters: the gradient's length
   int CameraTangentSize() const { return camera_tangent_size_; }   // Jacobian columns per free camera (Manifold::TangentSize of the block)
   int NumIntrinsicsGroups() const { return num_intrinsics_groups_; }   // shared intrinsics: the 3-wide blocks behind the poses (0: none)
+  // The blocks Covariance numbers: points, cameras and, with shared intrinsics, the groups behind them
+  int64_t NumCovarianceBlocks() const { return num_blocks_ + num_intrinsics_groups_; }
   // What Program::RemoveFixedBlocks left: rows kept, rows with an E cell (they come first), rows removed (both blocks constant), free
   // cameras, free points; any pointer may be null
   bool ReducedSizes(int64_t* num_rows, int64_t* num_rows_e, int64_t* num_rows_removed, int32_t* num_free_cameras, int32_t* num_free_points) const {
@@ -230,7 +233,8 @@ class HipBalProblem {
   }
   // ceres::Covariance::Compute + GetCovarianceBlockInTangentSpace for the (a, b) block pairs, numbered in state order (point q is q,
   // camera c is num_points + c): blocks_out = the dim(a) x dim(b) row-major blocks back to back (3 per point, 9 or 10 per camera; zeros
-  // for a pair with a constant block).  DENSE_SCHUR handles only.  Options from ceres_hip_covariance_default_options.  A refused call
+  // for a pair with a constant block).  With camera_group: camera c's block is its 6-wide POSE and group g is block
+  // num_points + num_cameras + g (3 wide, never constant) — NumCovarianceBlocks() blocks in all.  DENSE_SCHUR handles only.  Options from ceres_hip_covariance_default_options.  A refused call
   // throws; a rank-deficient problem returns with termination_type = CERES_HIP_FAILURE and its message, blocks_out untouched.
   ceres_hip_covariance_summary Covariance(const ceres_hip_covariance_options& options, const double* state,
                                           const std::vector<int32_t>& block_a, const std::vector<int32_t>& block_b, double* blocks_out) {
@@ -269,6 +273,7 @@ class HipBalProblem {
   int64_t num_parameters_ = 0, num_residuals_ = 0, num_jacobian_values_ = 0, num_effective_parameters_ = 0;
   int camera_tangent_size_ = 9;
   int32_t num_intrinsics_groups_ = 0;
+  int64_t num_blocks_ = 0;   // points + cameras
 };
 
 }  // namespace ceres_hip

@@ -584,10 +584,11 @@ ceres_hip_bal* ceres_hip_bal_create_with_fixed_intrinsics(const ceres_hip_option
  * > num_cameras, a group id out of range, an unused group id, and what ceres_hip_bal_create_with_constant_blocks refuses.
  * On such a handle ceres_hip_bal_evaluate, ceres_hip_bal_minimize (LEVENBERG_MARQUARDT on ITERATIVE_SCHUR, CGNR and DENSE_SCHUR, both
  * DOGLEG types on DENSE_SCHUR), ceres_hip_bal_set_loss, ceres_hip_bal_sizes, ceres_hip_bal_reduced_sizes,
- * ceres_hip_bal_get_row_order and ceres_hip_bal_fixed_cost work as usual.  CERES_HIP_E_UNSUPPORTED, with a message that says "shared
- * intrinsics": ceres_hip_bal_set_inner_iterations with anything but NONE, ceres_hip_bal_inner_iterate,
- * ceres_hip_bal_evaluate_gradient, ceres_hip_bal_minimize_line_search, ceres_hip_bal_covariance, ceres_hip_bal_set_bounds with a
- * finite bound, ceres_hip_debug_bal_evaluate_tiles_timing, and ceres_hip_bal_minimize on a sharded handle. */
+ * ceres_hip_bal_get_row_order and ceres_hip_bal_fixed_cost work as usual, and so does ceres_hip_bal_covariance on a DENSE_SCHUR
+ * handle (poses, points and groups: see there).  CERES_HIP_E_UNSUPPORTED, with a message that says "shared intrinsics":
+ * ceres_hip_bal_set_inner_iterations with anything but NONE, ceres_hip_bal_inner_iterate, ceres_hip_bal_evaluate_gradient,
+ * ceres_hip_bal_minimize_line_search, ceres_hip_bal_set_bounds with a finite bound, ceres_hip_debug_bal_evaluate_tiles_timing, and
+ * ceres_hip_bal_minimize on a sharded handle. */
 ceres_hip_bal* ceres_hip_bal_create_with_shared_intrinsics(const ceres_hip_options* options, int32_t camera_model, int32_t num_cameras,
                                                            int32_t num_points, int64_t num_observations, const int32_t* camera_index,
                                                            const int32_t* point_index, const double* observations,
@@ -848,6 +849,15 @@ int ceres_hip_debug_bal_bounded_step(ceres_hip_bal* p, const double* state, cons
  * camera); a pair that involves a constant block is all zeros (covariance_impl.cc:143-165).  Not offered: lifting to the ambient space of
  * a manifold camera, null_space_rank and the pseudo-inverse, sharded handles, handles whose linear solver is not CERES_HIP_DENSE_SCHUR,
  * handles with fixed intrinsics (ceres_hip_bal_create_with_fixed_intrinsics: CERES_HIP_E_UNSUPPORTED).
+ * SHARED INTRINSICS (ceres_hip_bal_create_with_shared_intrinsics, DENSE_SCHUR; design/28_shared_covariance.md).  The same matrix of the
+ * handle's own Jacobian: unscaled, no LM diagonal, loss-corrected unless apply_loss_function = 0, columns [points | poses of the free
+ * cameras | groups].  The camera side of the Schur form then has two cells per row: with a_k the pose columns of observation k (none
+ * when the pose is constant) and g_k its group's, Y_k = C_p^-1 E_k^T [F_k^pose | F_k^grp] and cols_k = {a_k .. a_k + 5, g_k .. g_k + 2},
+ *     pose / group - pose / group: the sub-block of S^-1;   point p - pose / group t: -sum_k Y_k S^-1[cols_k, t];
+ *     point p - point q: delta_pq C_p^-1 + sum_{k,l} Y_k S^-1[cols_k, cols_l] Y_l^T.
+ * Blocks: point q is q (3), the POSE of camera c is num_points + c (6), group g is num_points + num_cameras + g (3).  A pair with a
+ * constant pose is zeros; a group is never constant, even when all its cameras' poses are.  The state's groups must be bit-identical
+ * (CERES_HIP_E_INVALID before any device call, as ceres_hip_bal_evaluate answers).  Everything below holds unchanged.
  * RANK.  An unpivoted Cholesky does not notice a lost gauge, so S and every C_p are factored with a unit diagonal (S~ = Lambda S Lambda,
  * Lambda = diag(S)^-1/2; S^-1 = Lambda S~^-1 Lambda) and the call FAILS when a pivot is not above min_scaled_pivot, or when a diagonal
  * entry is not positive (a point all of whose rows a loss switched off).  This guard is a property of the inputs — on bundle-adjustment
@@ -868,7 +878,8 @@ typedef struct ceres_hip_covariance_summary {
   int64_t device_bytes;          /* what this feature holds on the handle (the second n x n buffer, the point blocks, the lists) */
   char    message[256];
 } ceres_hip_covariance_summary;
-/* Blocks are numbered in state order: point q is q, camera c is num_points + c.  blocks_out: the concatenation, in pair order, of
+/* Blocks are numbered in state order: point q is q, camera c is num_points + c (on a handle with shared intrinsics group g is
+ * num_points + num_cameras + g; on every other handle such an index is out of range).  blocks_out: the concatenation, in pair order, of
  * dim(a) x dim(b) row-major blocks; the pair (b, a) gives the exact transpose of (a, b); a pair may repeat.  options NULL: the defaults.
  * The handle's loss, camera model and constant masks are honoured as ceres_hip_bal_evaluate honours them; the solver's loaded values are
  * overwritten as by that call; the loss, the inner-iteration and strategy settings and a later ceres_hip_bal_minimize are not affected.
